@@ -8,6 +8,11 @@ decimating PT bank -> Viterbi -> error count).  N > 1: one process per GPU under
 every rank runs its own independent trial blocks (weak scaling, no data-path collective);
 the only exchange is the final all-reduce of the error counters (RCCL over xGMI).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the line
+can carry (per-stage times and the roofline, steady state, overlapped streams, the BER sweep, the
+CPU baseline, per-rank figures) runs only with --full.  --dump-outputs DIR writes what the last
+timed step computed (see dump_outputs).
 """
 import argparse
 import json
@@ -220,170 +225,65 @@ def _cpu_trial_timed(pool, jobs) -> dict:
             "bit_errors": sum(r[2] for r in res), "compared": sum(r[3] for r in res)}
 
 
-def main() -> None:
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--nsym", type=int, default=10_000_000)
-    ap.add_argument("--sps", type=int, default=8)
-    ap.add_argument("--ebn0", type=float, default=10.0)
-    ap.add_argument("--detector", default="PT")
-    ap.add_argument("--waveform", default="soqpsk", choices=["soqpsk", "multih", "pcmfm"],
-                    help="soqpsk: BASELINE configs[1] (the headline metric); multih: configs[2], ARTM multi-h CPM through the "
-                         "16-state generic CPM trellis detector; pcmfm: PCM/FM through the same detector family")
-    ap.add_argument("--states", type=int, default=16, choices=[16, 64, 256],
-                    help="--waveform multih: 16 = the reduced design BASELINE configs[2] names (Lp 2, NC 4); 64 = every phase state "
-                         "for the two-symbol pulse (Lp 2, NC 16, N_S = p M^(Lp-1): notes/cpm/cpm.md:128-140), 0.2 dB better, one wave per detector; "
-                         "256 = the full trellis (3-symbol pulse, 64 matched filters per symbol: 1 KB of rows per symbol), one workgroup per detector")
-    ap.add_argument("--fuse", type=int, default=175,
-                    help="bit 0: fused modulator (FIR + phase scan in one pass); bit 1: AWGN inside the MF bank; "
-                         "bit 2: detector-packed 32 B rows between bank and detector; bit 3: modulator + channel + bank in one "
-                         "kernel (no baseband samples in HBM); bit 4: PRBS + precoder through the generic kernels; bit 5: the "
-                         "detector and the error count of a block on the context's side stream, beside the next block's front "
-                         "end (15 = one block after the other); 0 = every stage its own kernel")
-    ap.add_argument("--streams", type=int, default=1,
-                    help="independent trial blocks in flight on separate HIP streams (own workspace + context each)")
-    ap.add_argument("--overlap-streams", type=int, default=3,
-                    help="after the timed region (single GPU, --streams 1): the same K steps again with this many independent "
-                         "blocks in flight on separate HIP streams, reported as `overlapped` (0 = skip)")
-    ap.add_argument("--event-every", type=int, default=4,
-                    help="record the per-stage HIP events on every E-th timed step only (the last step always)")
-    ap.add_argument("--vit-warmup", type=int, default=-1,
-                    help="detector chunk warm-up in rows (= detector calls before a chunk's own first call), any waveform; "
-                         "-1: by Eb/N0 (waveforms_amd.link.operating_point_warmup), 0: library default")
-    ap.add_argument("--cpu-sample", type=int, default=1 << 21, help="symbols per core, compiled port")
-    ap.add_argument("--cpu-loop-sample", type=int, default=1 << 16, help="symbols per core, faithful-loop form")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
-                    help="a wf_ctx option for every context of this run (include/wfhip.h wf_option, lower-case name without "
-                         "the WF_OPT_ prefix): e.g. --opt cpm_form=1 (row form), --opt cpm_chunk_calls=320, --opt det_final_verify=1")
-    ap.add_argument("--ber-points", default="0:12",
-                    help="SOQPSK at 8 sps: after the timed region, the BER sweep of BASELINE configs[3] (these Eb/N0 points x "
-                         "--ber-symbols) through the same link, reported as `ber_curve` with its offset in dB from the reference's "
-                         "golden curve — the second half of BASELINE's metric ('none' = skip)")
-    ap.add_argument("--ber-symbols", type=float, default=1e8, help="symbols per point of that sweep")
-    ap.add_argument("--steady-steps", type=int, default=2000,
-                    help="after the timed region (single GPU): this many more steps in one go, reported as `steady_state` — long "
-                         "enough (>= 1 s) that clock ramp and the 13 ms timed window can be told apart (0 = skip)")
-    args = ap.parse_args()
-
-    from waveforms_amd.bert import init_ranks, spawn_ranks
-
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: start the N ranks ourselves, as child processes, before
-        # anything here has touched the GPU; rank 0 prints the JSON line on the inherited stdout
-        raise SystemExit(spawn_ranks(str(Path(__file__).resolve()), args.gpus, sys.argv[1:]))
-    import torch
-
-    if int(os.environ.get("WORLD_SIZE", 1)) != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
-    # Rehearsal switch for a 1-GPU box: WF_BENCH_REHEARSAL=1 puts every rank on cuda:0 and uses
-    # gloo for the two collectives, so the N > 1 code path can be exercised without N GPUs.
-    rank, world, dist, coll_dev = init_ranks(rehearsal=os.environ.get("WF_BENCH_REHEARSAL") == "1")
+def cpm_link_forms(link, det_info: list):
+    """What wf_cpm_link_run will launch for ``link``: wf_cpm_link_form's four numbers {front end, detector form, calls per chunk,
+    warm-up calls} and the detector kernel's name; ``det_info`` receives {form, ring slots, calls per chunk, warm-up calls}."""
+    import ctypes as _ct
 
     from waveforms_amd import _hip
-    from waveforms_amd.link import SOQPSKLink, operating_point_warmup, soqpsk_warmup_param
+    from waveforms_amd.viterbi.cpm import detector_kernel_name
 
-    _hip.apply_option_args(args.opt)
-    nstreams = max(1, args.streams)
-    cpm = args.waveform != "soqpsk"
+    link_form = (_ct.c_int * 4)()
+    _hip.check(_hip.lib().wf_cpm_link_form(link._ctx, _ct.byref(link.cfg), link_form))
+    det_kernel = detector_kernel_name(link.spec, link.layout()["calls"], link.cfg.warmup, ctx=link._ctx, info4=det_info)
+    if link_form[0] == 2 and link_form[1] == 1:
+        det_info[:] = [1, 3, int(link_form[2]), int(link_form[3])]
+    return [int(v) for v in link_form], det_kernel
+
+
+DUMP_SAMPLE = 1 << 22     # entries per dumped array at most: longer ones are a fixed, seeded sample of their positions, in order
+
+
+def dump_outputs(out_dir: Path, link, blocks: int, counts, cpm: bool) -> None:
+    """--dump-outputs: what a caller of the timed path receives from its last step, as ``out_dir/<name>.npy``.
+
+    error_counts.npy (float64): (symbol errors, bit errors, symbols compared) over the timed steps, as ``link.result()`` gives them.
+    decided_bits.npy, decided_symbols.npy (SOQPSK) / decided_symbols.npy (CPM), float32: the detector's decisions of the last
+    block, the positions the error count compares, read from the link's workspace.  ``blocks`` = blocks this link has run:
+    a pipelined link (fuse bit 5) keeps two sets of intermediates in its workspace and uses them in turn, one block each,
+    starting with the first (wf_link_run / wf_cpm_link_run)."""
+    import numpy as np
+
+    from waveforms_amd import _hip
+
+    lay = link.layout()
     if cpm:
-        from waveforms_amd.link import CPMLink
-        from waveforms_amd.viterbi.cpm import detector_kernel_name
-
-        # detector chunk warm-up rows: by operating point (waveforms_amd.link.operating_point_warmup), or --vit-warmup
-        wide = args.waveform == "multih" and args.states != 16
-        cwu = args.vit_warmup if args.vit_warmup >= 0 else (0 if wide else operating_point_warmup(args.waveform, args.ebn0))
-        big_spec = None
-        if wide:
-            from waveforms_amd.viterbi import cpm as _cpm
-            big_spec = _cpm.ARTM_64 if args.states == 64 else _cpm.ARTM_256
-        links = [CPMLink(args.nsym, args.sps, waveform=args.waveform, spec=big_spec, private_ctx=nstreams > 1, fuse=args.fuse, warmup=cwu)      # (bits 1, 3, 5 apply)
-                 for _ in range(nstreams)]
-        bits_per_sym = links[0].spec.bits_per_symbol
+        link_form, _ = cpm_link_forms(link, [0, 0, 0, 0])
+        quad_samples = link_form[0] == 2 and link_form[1] == 3      # the 256-state samples form runs its blocks one after the other
+        piped = bool(link.cfg.fuse & 32) and lay["calls"] > 0 and not quad_samples
+        first = max(int(link.cfg.skip_head), 0) + int(link.cfg.det.D) - 1
+        m = max(lay["calls"] - first, 0)
+        arrays = {"decided_symbols": (lay["off_decisions"] + first, np.uint8)}
     else:
-        # detector chunk warm-up rows: by operating point (16 at Eb/N0 >= 6 dB, else the library default of 32), or
-        # --vit-warmup: a matter of speed only (chunks that miss it are repaired on the device)
-        wu_rows = args.vit_warmup if args.vit_warmup >= 0 else operating_point_warmup("soqpsk", args.ebn0)
-        wu = soqpsk_warmup_param(wu_rows)
-        links = [SOQPSKLink(args.nsym, args.sps, detector=args.detector, fuse=args.fuse, private_ctx=nstreams > 1, warmup=wu)
-                 for _ in range(nstreams)]
-        bits_per_sym = 1
-    streams = [torch.cuda.Stream() for _ in range(nstreams)] if nstreams > 1 else [torch.cuda.current_stream()]
-    link = links[0]
-    slots = 64
-    assert args.steps >= 1
+        piped = bool(link.cfg.fuse & 32) and bool(lay["one_kernel_front_end"]) and lay["calls"] > 0
+        m = min(max(lay["calls"] - 2, 0), link.nsym)       # decision of call k + 2 is symbol k (detector length 2)
+        # (wf_link_layout's offsets 2 and 3, which SOQPSKLink.layout names off_bits / off_syms, are those of the decisions)
+        arrays = {"decided_bits": (lay["off_bits"] + 2, np.uint8), "decided_symbols": (lay["off_syms"] + 2, np.int8)}
+    base = (blocks - 1) % 2 * (link.workspace_bytes // 2) if piped else 0
+    _hip.torch().cuda.synchronize()
+    pick = np.sort(np.random.default_rng(0).choice(m, DUMP_SAMPLE, replace=False)) if m > DUMP_SAMPLE else slice(None)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "error_counts.npy", np.asarray(counts, dtype=np.float64))
+    for name, (off, dtype) in arrays.items():
+        raw = link.workspace[base + off: base + off + m].cpu().numpy().view(dtype)
+        np.save(out_dir / f"{name}.npy", raw[pick].astype(np.float32))
 
-    every = max(1, args.event_every)
 
-    def instrumented(k: int) -> bool:
-        return k % every == every - 1 or k == args.steps - 1
-
-    def step(k: int, timed: bool) -> None:
-        # every (rank, step) is its own trial block: distinct PRBS segment and Philox subsequence
-        block = k * world + rank
-        with torch.cuda.stream(streams[k % nstreams]):
-            links[k % nstreams].run_block(args.ebn0, seed=1, stream_id=block & 0xFFFFFFFF,
-                                          skip_bits=(block % 4096) * args.nsym * bits_per_sym,
-                                          event_slot=(k % slots) if timed and instrumented(k) else -1)
-
-    def fence() -> None:
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    for k in range(args.warmup):
-        step(-1 - k, False)
-    torch.cuda.synchronize()
-    for l in links:
-        l.reset_counts()
-    fence()
-    t0 = time.perf_counter()
-    for k in range(args.steps):
-        step(k, True)
-    fence()
-    elapsed = time.perf_counter() - t0
-    rank_ms = [elapsed / args.steps * 1e3]
-    if dist is not None:
-        # every rank's own time (all_gather of one double), so that the first real N-GPU run shows imbalance
-        mine = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
-        gathered = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(gathered, mine)
-        rank_ms = [float(t.item()) / args.steps * 1e3 for t in gathered]
-        t = mine.clone()
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-
-    se = be = compared = 0
-    for l in links:
-        a_, b_, c_ = l.result()
-        se, be, compared = se + a_, be + b_, compared + c_
-    counts = torch.tensor([se, be, compared], dtype=torch.int64, device=coll_dev)
-    collective = None
-    if dist is not None:
-        own = [int(v) for v in counts.cpu().tolist()]
-        torch.cuda.synchronize()
-        dist.barrier()
-        tc = time.perf_counter()
-        dist.all_reduce(counts, op=dist.ReduceOp.SUM)     # the one collective of the job
-        if coll_dev != "cpu":
-            torch.cuda.synchronize()
-        all_reduce_us = (time.perf_counter() - tc) * 1e6
-        # what ran, as the ranks themselves saw it — so that the first real N-GPU run proves its own collective: the
-        # backend, the group size, which physical device each rank drove, every rank's own count (their sum must be the
-        # reduced total) and the wall time of the all-reduce
-        props = torch.cuda.get_device_properties(torch.cuda.current_device())
-        ident = {"rank": rank, "local_device": torch.cuda.current_device(), "name": props.name,
-                 "pci": "%04x:%02x:%02x" % (getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0), getattr(props, "pci_device_id", 0)),
-                 "uuid": str(getattr(props, "uuid", "")), "compared": own[2], "bit_errors": own[1]}
-        seen = [None] * world
-        dist.all_gather_object(seen, ident)
-        collective = {"backend": dist.get_backend(), "world_seen": dist.get_world_size(), "all_reduce_us": round(all_reduce_us, 1),
-                      "devices": seen, "sum_of_rank_counts_equals_reduced": sum(d["bit_errors"] for d in seen) == int(counts[1].item()),
-                      "distinct_devices": len({(d["pci"], d["uuid"]) for d in seen})}
-    se, be, compared = (int(v) for v in counts.cpu().tolist())
-
+def stage_roofline(args, links, nstreams: int, slots: int, instrumented, link_form, det_kernel):
+    """--full: per-stage times of the HIP events recorded inside the timed steps, and the roofline of the dominant stage's
+    kernel (committed profiles under profiles/ for its traffic and instruction counts)."""
+    cpm = args.waveform != "soqpsk"
+    bits_per_sym = links[0].spec.bits_per_symbol if cpm else 1
     # per-stage kernel time from the HIP events recorded inside the timed region
     ev_steps = [k for k in range(max(0, args.steps - slots), args.steps) if instrumented(k)]
     acc = {}
@@ -391,15 +291,11 @@ def main() -> None:
         for name, ms in links[k % nstreams].stage_ms(k % slots).items():
             acc[name] = acc.get(name, 0.0) + ms / len(ev_steps)
     bps = stage_bytes_per_symbol(args.sps)
-    det_info = [0, 0, 0, 0]           # generic CPM detector: {form, ring slots, calls per chunk, warm-up calls} as the library will launch it
     if cpm:
         nf = links[0].spec.nfilt
         # bits -> symbols -> c128 samples -> noisy samples in place -> nf complex rows -> one decision byte
         bps = {"prbs": bits_per_sym, "map": bits_per_sym + 1, "modulate": 1 + 16 * args.sps, "awgn": 32 * args.sps,
                "mfbank": 16 * args.sps + 16 * nf, "viterbi": 16 * nf + 1, "count": 2}
-        import ctypes as _ct
-        link_form = (_ct.c_int * 4)()
-        _hip.check(_hip.lib().wf_cpm_link_form(links[0]._ctx, _ct.byref(links[0].cfg), link_form))
         samples_form = link_form[0] == 2
         if samples_form:
             # fuse bit 7 in effect (round 6): the "modulate" slot timed modulator + channel with the noisy SAMPLES stored (1 B in,
@@ -422,7 +318,7 @@ def main() -> None:
         STAGE_KERNEL.update({"mfbank": f"cpm_mf_rows_kernel<{nf}, {9 if args.sps == 8 else 0}, {'true' if links[0].cfg.fuse & 2 else 'false'}>",
                              # (the profiles time every kernel ALONE — link fuse 15 —, where the lane form launches the instantiation that
                              #  claims a SIMD's registers; the pipelined link runs the plain one: same code, same counters but for the claim)
-                             "viterbi": detector_kernel_name(links[0].spec, links[0].layout()["calls"], links[0].cfg.warmup, ctx=links[0]._ctx, info4=det_info),
+                             "viterbi": det_kernel,
                              "map": "symbol_map_kernel",
                              "modulate": "mod_main_kernel<4, true, false>"})
         if samples_form and link_form[1] == 1:
@@ -430,7 +326,6 @@ def main() -> None:
             k1 = links[0].spec.K[1] if len(links[0].spec.K) > 1 else links[0].spec.K[0]
             STAGE_KERNEL["viterbi"] = (f"cpm_lane_kernel<lane_spec<{links[0].spec.M}, {links[0].spec.Lp}, {links[0].spec.NC}, {links[0].spec.p}, "
                                        f"{len(links[0].spec.K)}, {links[0].spec.K[0]}, {k1}>, 3, true, true, true>")
-            det_info[:] = [1, 3, int(link_form[2]), int(link_form[3])]
     one_kernel = not cpm and bool(links[0].layout()["one_kernel_front_end"])     # asked from the library (wf_link_layout)
     if one_kernel:      # fuse bit 3: the "fir" slot times modulator + channel + bank; symbols in, packed rows out
         acc["mod+awgn+mfbank"] = acc.pop("fir")
@@ -510,8 +405,196 @@ def main() -> None:
             if v_:
                 st["valu_issue_frac"] = v_["valu_issue_frac"]
 
+    return stages, roofline
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--nsym", type=int, default=10_000_000)
+    ap.add_argument("--sps", type=int, default=8)
+    ap.add_argument("--ebn0", type=float, default=10.0)
+    ap.add_argument("--detector", default="PT")
+    ap.add_argument("--waveform", default="soqpsk", choices=["soqpsk", "multih", "pcmfm"],
+                    help="soqpsk: BASELINE configs[1] (the headline metric); multih: configs[2], ARTM multi-h CPM through the "
+                         "16-state generic CPM trellis detector; pcmfm: PCM/FM through the same detector family")
+    ap.add_argument("--states", type=int, default=16, choices=[16, 64, 256],
+                    help="--waveform multih: 16 = the reduced design BASELINE configs[2] names (Lp 2, NC 4); 64 = every phase state "
+                         "for the two-symbol pulse (Lp 2, NC 16, N_S = p M^(Lp-1): notes/cpm/cpm.md:128-140), 0.2 dB better, one wave per detector; "
+                         "256 = the full trellis (3-symbol pulse, 64 matched filters per symbol: 1 KB of rows per symbol), one workgroup per detector")
+    ap.add_argument("--fuse", type=int, default=175,
+                    help="bit 0: fused modulator (FIR + phase scan in one pass); bit 1: AWGN inside the MF bank; "
+                         "bit 2: detector-packed 32 B rows between bank and detector; bit 3: modulator + channel + bank in one "
+                         "kernel (no baseband samples in HBM); bit 4: PRBS + precoder through the generic kernels; bit 5: the "
+                         "detector and the error count of a block on the context's side stream, beside the next block's front "
+                         "end (15 = one block after the other); 0 = every stage its own kernel")
+    ap.add_argument("--streams", type=int, default=1,
+                    help="independent trial blocks in flight on separate HIP streams (own workspace + context each)")
+    ap.add_argument("--overlap-streams", type=int, default=3,
+                    help="after the timed region (single GPU, --streams 1): the same K steps again with this many independent "
+                         "blocks in flight on separate HIP streams, reported as `overlapped` (0 = skip)")
+    ap.add_argument("--event-every", type=int, default=4,
+                    help="record the per-stage HIP events on every E-th timed step only (the last step always)")
+    ap.add_argument("--vit-warmup", type=int, default=-1,
+                    help="detector chunk warm-up in rows (= detector calls before a chunk's own first call), any waveform; "
+                         "-1: by Eb/N0 (waveforms_amd.link.operating_point_warmup), 0: library default")
+    ap.add_argument("--cpu-sample", type=int, default=1 << 21, help="symbols per core, compiled port")
+    ap.add_argument("--cpu-loop-sample", type=int, default=1 << 16, help="symbols per core, faithful-loop form")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
+                    help="a wf_ctx option for every context of this run (include/wfhip.h wf_option, lower-case name without "
+                         "the WF_OPT_ prefix): e.g. --opt cpm_form=1 (row form), --opt cpm_chunk_calls=320, --opt det_final_verify=1")
+    ap.add_argument("--ber-points", default="0:12",
+                    help="SOQPSK at 8 sps: after the timed region, the BER sweep of BASELINE configs[3] (these Eb/N0 points x "
+                         "--ber-symbols) through the same link, reported as `ber_curve` with its offset in dB from the reference's "
+                         "golden curve — the second half of BASELINE's metric ('none' = skip)")
+    ap.add_argument("--ber-symbols", type=float, default=1e8, help="symbols per point of that sweep")
+    ap.add_argument("--steady-steps", type=int, default=2000,
+                    help="after the timed region (single GPU): this many more steps in one go, reported as `steady_state` — long "
+                         "enough (>= 1 s) that clock ramp and the 13 ms timed window can be told apart (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-stage HIP events inside the timed steps "
+                         "(stages, roofline), steady state, overlapped streams, the BER sweep, the CPU baseline and the per-rank "
+                         "figures of N > 1 (the options above that name them apply only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+
+    from waveforms_amd.bert import init_ranks, spawn_ranks
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # plain `python bench.py --gpus N`: start the N ranks ourselves, as child processes, before
+        # anything here has touched the GPU; rank 0 prints the JSON line on the inherited stdout
+        raise SystemExit(spawn_ranks(str(Path(__file__).resolve()), args.gpus, sys.argv[1:]))
+    import torch
+
+    if int(os.environ.get("WORLD_SIZE", 1)) != args.gpus:
+        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
+    # Rehearsal switch for a 1-GPU box: WF_BENCH_REHEARSAL=1 puts every rank on cuda:0 and uses
+    # gloo for the two collectives, so the N > 1 code path can be exercised without N GPUs.
+    rank, world, dist, coll_dev = init_ranks(rehearsal=os.environ.get("WF_BENCH_REHEARSAL") == "1")
+
+    from waveforms_amd import _hip
+    from waveforms_amd.link import SOQPSKLink, operating_point_warmup, soqpsk_warmup_param
+
+    _hip.apply_option_args(args.opt)
+    nstreams = max(1, args.streams)
+    cpm = args.waveform != "soqpsk"
+    if cpm:
+        from waveforms_amd.link import CPMLink
+
+        # detector chunk warm-up rows: by operating point (waveforms_amd.link.operating_point_warmup), or --vit-warmup
+        wide = args.waveform == "multih" and args.states != 16
+        cwu = args.vit_warmup if args.vit_warmup >= 0 else (0 if wide else operating_point_warmup(args.waveform, args.ebn0))
+        big_spec = None
+        if wide:
+            from waveforms_amd.viterbi import cpm as _cpm
+            big_spec = _cpm.ARTM_64 if args.states == 64 else _cpm.ARTM_256
+        links = [CPMLink(args.nsym, args.sps, waveform=args.waveform, spec=big_spec, private_ctx=nstreams > 1, fuse=args.fuse, warmup=cwu)      # (bits 1, 3, 5 apply)
+                 for _ in range(nstreams)]
+        bits_per_sym = links[0].spec.bits_per_symbol
+    else:
+        # detector chunk warm-up rows: by operating point (16 at Eb/N0 >= 6 dB, else the library default of 32), or
+        # --vit-warmup: a matter of speed only (chunks that miss it are repaired on the device)
+        wu_rows = args.vit_warmup if args.vit_warmup >= 0 else operating_point_warmup("soqpsk", args.ebn0)
+        wu = soqpsk_warmup_param(wu_rows)
+        links = [SOQPSKLink(args.nsym, args.sps, detector=args.detector, fuse=args.fuse, private_ctx=nstreams > 1, warmup=wu)
+                 for _ in range(nstreams)]
+        bits_per_sym = 1
+    streams = [torch.cuda.Stream() for _ in range(nstreams)] if nstreams > 1 else [torch.cuda.current_stream()]
+    link = links[0]
+    slots = 64
+    assert args.steps >= 1
+
+    every = max(1, args.event_every)
+    blocks_run = [0] * nstreams      # blocks queued on each link (dump_outputs finds the last one's set of intermediates by it)
+
+    def instrumented(k: int) -> bool:
+        return args.full and (k % every == every - 1 or k == args.steps - 1)
+
+    def step(k: int, timed: bool) -> None:
+        # every (rank, step) is its own trial block: distinct PRBS segment and Philox subsequence
+        block = k * world + rank
+        with torch.cuda.stream(streams[k % nstreams]):
+            links[k % nstreams].run_block(args.ebn0, seed=1, stream_id=block & 0xFFFFFFFF,
+                                          skip_bits=(block % 4096) * args.nsym * bits_per_sym,
+                                          event_slot=(k % slots) if timed and instrumented(k) else -1)
+        blocks_run[k % nstreams] += 1
+
+    def fence() -> None:
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for k in range(args.warmup):
+        step(-1 - k, False)
+    torch.cuda.synchronize()
+    for l in links:
+        l.reset_counts()
+    fence()
+    t0 = time.perf_counter()
+    for k in range(args.steps):
+        step(k, True)
+    fence()
+    elapsed = time.perf_counter() - t0
+    rank_ms = [elapsed / args.steps * 1e3]
+    if dist is not None:
+        mine = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
+        if args.full:
+            # every rank's own time (all_gather of one double), so that the first real N-GPU run shows imbalance
+            gathered = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(gathered, mine)
+            rank_ms = [float(t.item()) / args.steps * 1e3 for t in gathered]
+        t = mine.clone()
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+    se = be = compared = 0
+    for l in links:
+        a_, b_, c_ = l.result()
+        se, be, compared = se + a_, be + b_, compared + c_
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on these links: the workspace still holds the last timed step's intermediates
+        dump_outputs(Path(args.dump_outputs), links[(args.steps - 1) % nstreams], blocks_run[(args.steps - 1) % nstreams],
+                     (se, be, compared), cpm)
+    counts = torch.tensor([se, be, compared], dtype=torch.int64, device=coll_dev)
+    collective = None
+    if dist is not None:
+        own = [int(v) for v in counts.cpu().tolist()]
+        torch.cuda.synchronize()
+        dist.barrier()
+        tc = time.perf_counter()
+        dist.all_reduce(counts, op=dist.ReduceOp.SUM)     # the one collective of the job
+        if coll_dev != "cpu":
+            torch.cuda.synchronize()
+        all_reduce_us = (time.perf_counter() - tc) * 1e6
+    if dist is not None and args.full:
+        # what ran, as the ranks themselves saw it — so that the first real N-GPU run proves its own collective: the
+        # backend, the group size, which physical device each rank drove, every rank's own count (their sum must be the
+        # reduced total) and the wall time of the all-reduce
+        props = torch.cuda.get_device_properties(torch.cuda.current_device())
+        ident = {"rank": rank, "local_device": torch.cuda.current_device(), "name": props.name,
+                 "pci": "%04x:%02x:%02x" % (getattr(props, "pci_domain_id", 0), getattr(props, "pci_bus_id", 0), getattr(props, "pci_device_id", 0)),
+                 "uuid": str(getattr(props, "uuid", "")), "compared": own[2], "bit_errors": own[1]}
+        seen = [None] * world
+        dist.all_gather_object(seen, ident)
+        collective = {"backend": dist.get_backend(), "world_seen": dist.get_world_size(), "all_reduce_us": round(all_reduce_us, 1),
+                      "devices": seen, "sum_of_rank_counts_equals_reduced": sum(d["bit_errors"] for d in seen) == int(counts[1].item()),
+                      "distinct_devices": len({(d["pci"], d["uuid"]) for d in seen})}
+    se, be, compared = (int(v) for v in counts.cpu().tolist())
+
+    det_info = [0, 0, 0, 0]           # generic CPM detector: {form, ring slots, calls per chunk, warm-up calls} as the library will launch it
+    link_form = det_kernel = None
+    if cpm:
+        link_form, det_kernel = cpm_link_forms(links[0], det_info)
+    stages = roofline = None
+    if args.full:
+        stages, roofline = stage_roofline(args, links, nstreams, slots, instrumented, link_form, det_kernel)
+
     steady = None
-    if nstreams == 1 and args.steady_steps > 0:      # (N > 1: every rank runs its own, reported per rank below)
+    if args.full and nstreams == 1 and args.steady_steps > 0:      # (N > 1: every rank runs its own, reported per rank below)
         from waveforms_amd import device as _dev0
         for l in links:
             l.reset_counts()
@@ -539,7 +622,7 @@ def main() -> None:
     # (examples/soqpsk_detection.py:200-216 is the quantity; tests/golden/ber_golden*.csv the reference's own counts):
     # configs[3]'s sweep through the link the timed region just ran, one block after the other.
     ber_curve = None
-    if rank == 0 and not cpm and args.sps == 8 and nstreams == 1 and args.ber_points not in ("", "none") and args.detector in ("PT", "PAM"):
+    if args.full and rank == 0 and not cpm and args.sps == 8 and nstreams == 1 and args.ber_points not in ("", "none") and args.detector in ("PT", "PAM"):
         sys.path.insert(0, str(ROOT / "tools"))
         from ber_sweep import golden_curve
         from waveforms_amd.bert import ebn0_at_ber
@@ -574,7 +657,7 @@ def main() -> None:
             except ValueError:
                 ber_curve[f"delta_db_at_{target:g}"] = None
 
-    if rank == 0 and cpm and nstreams == 1 and args.ber_points not in ("", "none"):
+    if args.full and rank == 0 and cpm and nstreams == 1 and args.ber_points not in ("", "none"):
         # The CPM links have no curve in the reference (it ships no detector for them: DESIGN.md section 2): the same sweep,
         # Eb/N0 at BER 1e-3 / 1e-4 read off it, no offset to quote.  (256 states: 12 ms per block — a shorter sweep.)
         from waveforms_amd.bert import ebn0_at_ber
@@ -610,7 +693,7 @@ def main() -> None:
     # detector and the small integer kernels of its neighbours.  Reported beside `value`, never instead of it:
     # the per-kernel times above are only clean with one block at a time.
     overlapped = None
-    if world == 1 and nstreams == 1 and args.overlap_streams > 1:
+    if args.full and world == 1 and nstreams == 1 and args.overlap_streams > 1:
         n2 = args.overlap_streams
         extra = [type(links[0])(args.nsym, args.sps, **(dict(waveform=args.waveform, fuse=args.fuse, warmup=links[0].cfg.warmup)
                                                          if cpm else dict(detector=args.detector, fuse=args.fuse, warmup=links[0].cfg.warmup)),
@@ -679,9 +762,9 @@ def main() -> None:
                     # every detector chunk started from bitwise the state of the sequential detector, or was run again
                     # from it (device-side proof + repair in every launch; link.result() raises otherwise)
                     "detector_chunks_unproven": 0},
-            "roofline": roofline,
-            "stages": stages,
         }
+        if args.full:
+            out.update(roofline=roofline, stages=stages)
         if steady:
             # Two numbers a reader trips on (round-5 verdict): `value` is timed by the driver's contract over K steps that start on
             # an idle chip — the whole window sits inside the ~30 ms the clock needs under load to reach what it then holds —, the
@@ -690,7 +773,7 @@ def main() -> None:
             out["clock_ramp"] = {"timed_window_ms": round(elapsed * 1e3, 3), "timed_ms_per_step": round(elapsed / args.steps * 1e3, 4),
                                  "steady_ms_per_step": steady["ms_per_step"], "steady_over_timed": round(steady["ms_per_step"] / (elapsed / args.steps * 1e3), 4),
                                  "note": "the driver-timed K steps run inside the chip's clock ramp (~30 ms under load); steady_state is the same step over 2000 blocks"}
-        if world > 1:
+        if world > 1 and args.full:
             out["scaling_figure"] = "steady_state_per_rank (each rank's own 2000-block window); `value` over K steps + one barrier is dominated by clock ramp and launch skew"
         if overlapped:
             out["overlapped"] = overlapped
@@ -698,13 +781,13 @@ def main() -> None:
             out["steady_state"] = steady
         if ber_curve:
             out["ber_curve"] = ber_curve
-        if world > 1:
+        if world > 1 and args.full:
             out["per_rank_ms_per_step"] = [round(v, 4) for v in rank_ms]
             out["rank_time_max_over_min"] = round(max(rank_ms) / max(min(rank_ms), 1e-12), 4)
             out["collective"] = collective
             if steady_all:
                 out["steady_state_per_rank"] = steady_all
-        if not args.no_cpu_baseline:    # rank 0 only, after the timed region, at any N (the other ranks wait at the final barrier)
+        if args.full and not args.no_cpu_baseline:    # rank 0 only, after the timed region, at any N (the other ranks wait at the final barrier)
             out["cpu_baseline"] = cpu_baseline(args.sps, args.ebn0, args.cpu_sample, args.cpu_loop_sample,
                                                    args.waveform + (str(args.states) if args.waveform == "multih" and args.states != 16 else ""), gpus=world)
         print(json.dumps(out), flush=True)

@@ -194,7 +194,7 @@ def test_bench_pcmfm_at_2_db_prints_a_line():
     """`bench.py --waveform pcmfm --ebn0 2` — the command that died with a traceback in round 4 — and the same with the
     64-row warm-up forced (what the table then chose at 2 dB): a JSON line, nothing unproven."""
     for extra in ([], ["--vit-warmup", "64"]):
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--waveform", "pcmfm", "--ebn0", "2", "--steps", "3", "--warmup", "1",
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--waveform", "pcmfm", "--ebn0", "2", "--steps", "3", "--warmup", "1",
                "--steady-steps", "40", "--no-cpu-baseline", "--overlap-streams", "0", *extra]
         r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

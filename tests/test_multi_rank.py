@@ -39,7 +39,7 @@ def test_two_ranks_through_the_real_block_runner_equal_one_rank():
 
 def test_bench_gpus_2_without_torchrun_rehearsal():
     """`python bench.py --gpus 2` — the command shape the driver uses — starts its own ranks."""
-    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--nsym", "1000000",
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--nsym", "1000000", "--full",
                 "--no-cpu-baseline", "--steady-steps", "20"], {"WF_BENCH_REHEARSAL": "1"})
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["scaling"] == "weak"
     assert out["ber"]["symbols"] == 2 * 3 * (1000000 - 3)
@@ -103,7 +103,7 @@ def _gpu_count():
 def test_bench_gpus_2_real_nccl_equals_rehearsal():
     """Two ranks on two GPUs with backend nccl (= RCCL over xGMI): the all-reduced counters equal the one-GPU
     rehearsal's (both ranks on cuda:0, gloo), per-rank times are reported, the CPU baseline stays in the line."""
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--nsym", "1000000",
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--nsym", "1000000", "--full",
            "--cpu-sample", "65536", "--cpu-loop-sample", "4096"]
     real = _run(cmd)
     reh = _run(cmd + ["--no-cpu-baseline"], {"WF_BENCH_REHEARSAL": "1"})
@@ -115,13 +115,13 @@ def test_bench_gpus_2_real_nccl_equals_rehearsal():
 def test_bench_line_reports_binding_roofline_and_steady_state():
     """One-GPU line: the roofline that binds is the one in bound / frac (HBM kept as hbm_frac), the CPM path is
     asked from the library, and the long steady-state figure sits beside the driver-timed value."""
-    out = _run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--steady-steps", "200",
+    out = _run([sys.executable, "bench.py", "--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--steady-steps", "200",
                 "--overlap-streams", "0"])
     r = out["roofline"]
     assert r["bound"] in ("hbm", "valu_issue") and r["frac"] == r["binding_frac"] and 0 < r["hbm_frac"] <= 1
     if "valu_issue_frac" in r:
         assert r["frac"] == max(r["valu_issue_frac"], r["hbm_frac"])
     assert out["steady_state"]["steps"] == 200 and out["steady_state"]["value"] > 0
-    out = _run([sys.executable, "bench.py", "--waveform", "multih", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    out = _run([sys.executable, "bench.py", "--full", "--waveform", "multih", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                 "--steady-steps", "0", "--overlap-streams", "0", "--nsym", "1000000"])
     assert out["roofline"]["kernel"].startswith(("mod_chan_bank_kernel<4, 16, 8>", "cpm_viterbi_kernel<4, 2>"))

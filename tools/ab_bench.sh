@@ -19,7 +19,7 @@ for pass in 1 2; do
   i=0
   for flags in "$@"; do
     echo -n "[$flags] $BENCH_FLAGS: "
-    WF_HIP_LIBRARY=/tmp/libwfhip_abb_$i.so python3 bench.py --no-cpu-baseline --overlap-streams 0 $BENCH_FLAGS 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['steady_state']; print(d['ms_per_step'], 'steady', s['ms_per_step'], s['bit_errors'], s['detector_chunks_unproven'])"
+    WF_HIP_LIBRARY=/tmp/libwfhip_abb_$i.so python3 bench.py --full --no-cpu-baseline --overlap-streams 0 $BENCH_FLAGS 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['steady_state']; print(d['ms_per_step'], 'steady', s['ms_per_step'], s['bit_errors'], s['detector_chunks_unproven'])"
     i=$((i+1))
   done
 done

@@ -8,7 +8,7 @@ fuses = [a for a in sys.argv[1:] if a.isdigit()]
 for wl in ([], ["--detector", "PAM"], ["--sps", "10"], ["--waveform", "multih"], ["--waveform", "pcmfm"]):
     for rep in range(2):
         for f in fuses:
-            out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--overlap-streams", "0", "--fuse", f] + wl,
+            out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--overlap-streams", "0", "--fuse", f] + wl,
                                  capture_output=True, text=True)
             if out.returncode:
                 print(wl, f, "FAILED", out.stderr[-400:], flush=True)

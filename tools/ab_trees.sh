@@ -7,6 +7,6 @@ line='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); 
 for p in $(seq $passes); do
   for tree in "$root/$other" "$root"; do
     echo -n "$(basename $tree) [$*]: "
-    (cd $tree && python3 bench.py --no-cpu-baseline --overlap-streams 0 "$@" 2>/dev/null | python3 -c "$line")
+    (cd $tree && python3 bench.py --full --no-cpu-baseline --overlap-streams 0 "$@" 2>/dev/null | python3 -c "$line")
   done
 done
