@@ -82,7 +82,8 @@ typedef enum {
     WF_OPT_CPM_SAMPLES_MIN_CALLS = 7, /* wf_cpm_viterbi_detect_samples / wf_cpm_link_config.fuse bit 7, 16-state lane form: shortest burst (calls) that
                                    * takes the samples form; 0 = the library's 6e6 (below it rows + the row form are faster: one lane per chunk leaves
                                    * most of a short burst's chunks to warm-up), otherwise >= 4096 — tests run the form on bursts an oracle can follow */
-    WF_OPT_COUNT = 8
+    WF_OPT_SOFT_CHUNK_CALLS = 8,  /* wf_viterbi4_soft: rows per chunk (1 .. 8192); 0 = the library's choice (wf_viterbi4_soft_geometry) */
+    WF_OPT_COUNT = 9
 } wf_option;
 int wf_ctx_set_option(wf_ctx *ctx, int key, int64_t value);
 int wf_ctx_get_option(wf_ctx *ctx, int key, int64_t *value);
@@ -232,6 +233,32 @@ int wf_viterbi4_unmerged(wf_ctx *ctx, int64_t *h_count, int reset, void *stream)
  * loop, algorithm.py:44-101.) */
 int wf_viterbi_repaired(wf_ctx *ctx, int64_t *h_count, int reset, void *stream);
 int wf_viterbi_cascaded(wf_ctx *ctx, int64_t *h_count, int reset, void *stream);
+
+/* ---- SOQPSK 4-state soft output: max-log-MAP, per-bit LLRs ------------------------------------------------------------
+ * A burst of `ncalls` rows (free start, free end) over the trellis, the branch increments and the column schedule of
+ * SOQPSKTrellisDetector (waveforms/viterbi/algorithm.py:44-101: inc_k(b) = Re(state_exp_term[start b] * z_k[idx(out b)]),
+ * row k is section k with column k % 2, metrics minimised).  In float64 and in exactly this order of operations:
+ *   ã_0 = 0;   a'_{k+1}(s') = min_{b: end b = s'} (ã_k(start b) + inc_k(b));      ã_{k+1} = a'_{k+1} - min_s a'_{k+1}(s)
+ *   b̃_N = 0;   b'_k(s)      = min_{b: start b = s} (inc_k(b) + b̃_{k+1}(end b));   b̃_k     = b'_k - min_s b'_k(s)
+ *   d_llr[k] = λ_k = min_{b: inp b = 1} ((ã_k(start b) + inc_k(b)) + b̃_{k+1}(end b)) - min_{b: inp b = 0} (the same)
+ *   d_bits[k] = λ_k < 0  (λ > 0 favours bit 0).
+ * λ is in metric units, no scale baked in.  Alignment: transmitted bit j pairs with λ_{j+1} (the length-2 hard detector's
+ * output k + 1 is its decision on section k).  The hard decisions are the maximum-likelihood sequence under the
+ * reference's metric: they equal the long-window detector's (wf_viterbi4_detect_window, length >= 8), NOT the length-2
+ * detector's, and need not have fewer bit errors than it.
+ * d_rows: 48-byte rows (3 complex128, alpha = -2, 0, +2; 16-byte aligned) or, row_bytes = 32, the links' detector-packed
+ * rows {Re z1, Im z1, a, b} (wf_link_config.fuse bit 2).  Each call is a fresh burst.  Chunk-parallel with the proof and
+ * cascading repair of the hard detectors in BOTH directions (forward metrics at every chunk start, backward metrics at
+ * every chunk end), so the result is bitwise the definition whatever `warmup` (rows, 0 = library default) and
+ * WF_OPT_SOFT_CHUNK_CALLS are; WF_OPT_DET_REPAIR / WF_OPT_DET_FINAL_VERIFY act as for the hard detectors, and the
+ * repairs and unproven chunks (forward and backward) are counted in wf_viterbi_repaired / wf_viterbi4_unmerged.
+ * Scratch: the context's detector scratch (wf_viterbi4_soft_geometry [3] bytes).  row_bytes not 32 / 48, ncalls < 1,
+ * warmup < 0 or a NULL pointer: WF_ERR_VALUE before the context is touched. */
+int wf_viterbi4_soft(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
+                     double *d_llr, uint8_t *d_bits, void *stream);
+/* What wf_viterbi4_soft launches for this burst on this context: h_geom[0] rows per chunk, [1] chunks (= lanes),
+ * [2] warm-up rows actually used, [3] scratch bytes. */
+int wf_viterbi4_soft_geometry(wf_ctx *ctx, int64_t ncalls, int warmup, int64_t *h_geom);
 
 /* wf_viterbi4_detect + wf_count_errors in one call (fresh detector): decision k is
  * compared with reference element k - skip for 0 <= k - skip < ncompare

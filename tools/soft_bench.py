@@ -1,0 +1,124 @@
+"""Soft-output SOQPSK detector alone (wf_viterbi4_soft) on one block of link rows; prints ONE JSON line.
+
+    python tools/soft_bench.py [--calls 1e7] [--ebn0 10] [--detector PT] [--steps 20] [--warmup-steps 3] [--soft-warmup 0]
+
+The rows are what SOQPSKLink(calls, fuse=15) leaves in its workspace (detector-packed, 32 B per call: layout()["off_mf"],
+layout()["row_bytes"]); the link's own length-2 detector runs on them once, for its bit errors; the transmitted bits are
+the block's PN23 sequence.  Then the soft detector runs `--warmup-steps` untimed and `--steps` timed passes over the same
+rows: device events around the timed window, and a host clock around it that ends in a synchronise.  Reported next to the time: the launch geometry
+(wf_viterbi4_soft_geometry), chunk repairs per pass, the bit errors of λ < 0 (transmitted bit j against λ_{j+1}) beside the
+length-2 detector's, and the effective LLR scale: the c that best fits the error rate per bin of |λ| to 1 / (1 + e^{c |λ|})
+(maximum likelihood over bins 0.25 σ² wide), given as c σ² — 1 would mean λ / σ² is the exact log-likelihood ratio.
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def fit_scale(abs_llr: np.ndarray, err: np.ndarray, sigma2: float, width: float = 0.25) -> float:
+    """c σ² maximising the binned likelihood of the errors under P(error | |λ|) = 1 / (1 + e^{c |λ|})."""
+    x = abs_llr / sigma2
+    b = np.floor(x / width).astype(np.int64)
+    tot = np.bincount(b)
+    errs = np.bincount(b, weights=err.astype(np.float64), minlength=tot.size)
+    xs = np.bincount(b, weights=x, minlength=tot.size)
+    keep = tot > 0
+    tot, errs, xm = tot[keep], errs[keep], xs[keep] / tot[keep]
+
+    def nll(c):
+        return float(np.sum(errs * np.logaddexp(0.0, c * xm) + (tot - errs) * np.logaddexp(0.0, -c * xm)))
+
+    lo, hi = 0.0, 4.0                                   # golden-section search; c σ² is well inside
+    g = (np.sqrt(5.0) - 1.0) / 2.0
+    a, bb = hi - g * (hi - lo), lo + g * (hi - lo)
+    fa, fb = nll(a), nll(bb)
+    for _ in range(80):
+        if fa < fb:
+            hi, bb, fb = bb, a, fa
+            a = hi - g * (hi - lo)
+            fa = nll(a)
+        else:
+            lo, a, fa = a, bb, fb
+            bb = lo + g * (hi - lo)
+            fb = nll(bb)
+    return 0.5 * (lo + hi)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=float, default=1e7)
+    ap.add_argument("--ebn0", type=float, default=10.0)
+    ap.add_argument("--detector", default="PT", choices=["PT", "PAM"])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup-steps", type=int, default=3)
+    ap.add_argument("--soft-warmup", type=int, default=0, help="warm-up rows of the soft detector (0: library default)")
+    ap.add_argument("--opt", action="append", default=[], help="wf_ctx option key=value, e.g. soft_chunk_calls=64")
+    args = ap.parse_args()
+
+    import torch
+
+    from waveforms.glfsr import PNSequence
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+    from waveforms_amd.link import SOQPSKLink, sigma_for_ebn0
+
+    _hip.apply_option_args(args.opt)
+    torch.cuda.set_device(0)
+    nsym, sps = int(args.calls), 8
+    link = SOQPSKLink(nsym, sps, detector=args.detector, fuse=15, private_ctx=True)
+    link.run_block(args.ebn0, seed=1)
+    _hse, hbe, hm = link.result()
+    lay = link.layout()
+    rb, ncalls = lay["row_bytes"], lay["calls"]
+    rows = link.workspace[lay["off_mf"]:lay["off_mf"] + ncalls * rb].clone().view(torch.float64)
+    tx = PNSequence(23).generate(nsym, device=True)          # what the block sent (seed 1, skip 0)
+    del link
+
+    ctx = _hip.new_ctx()
+    try:
+        geom = dev.viterbi_soft_geometry(ncalls, args.soft_warmup, ctx=ctx)
+        for _ in range(args.warmup_steps):
+            llr, bits = dev.viterbi_soft(rows, True, args.soft_warmup, rb, ctx=ctx)
+        torch.cuda.synchronize()
+        dev.viterbi_repaired(reset=True, ctx=ctx)
+        dev.viterbi_unmerged(reset=True, ctx=ctx)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        e0.record()
+        for _ in range(args.steps):
+            llr, bits = dev.viterbi_soft(rows, True, args.soft_warmup, rb, ctx=ctx)
+        e1.record()
+        torch.cuda.synchronize()
+        host_ms = (time.perf_counter() - t0) * 1e3 / args.steps
+        ev_ms = e0.elapsed_time(e1) / args.steps
+        repaired = dev.viterbi_repaired(reset=True, ctx=ctx)
+        unproven = dev.viterbi_unmerged(reset=True, ctx=ctx)
+    finally:
+        _hip.free_ctx(ctx)
+
+    llr_h, bits_h, tx_h = _hip.to_host(llr), _hip.to_host(bits), _hip.to_host(tx)
+    m = min(tx_h.size, bits_h.size - 1)
+    err = bits_h[1:1 + m] != tx_h[:m]
+    sigma2 = sigma_for_ebn0(args.ebn0, sps) ** 2
+    scale = fit_scale(np.abs(llr_h[1:1 + m]), err, sigma2) if err.any() else None
+    print(json.dumps({
+        "tool": "soft_bench", "detector": args.detector, "ebn0_db": args.ebn0, "calls": ncalls, "row_bytes": rb,
+        "geometry": geom, "steps": args.steps, "warmup_steps": args.warmup_steps,
+        "ms_per_block_events": round(ev_ms, 4), "ms_per_block_host": round(host_ms, 4),
+        "gsym_per_s": round(ncalls / (ev_ms * 1e-3) / 1e9, 3),
+        "repairs_per_block": repaired / args.steps, "unproven": unproven,
+        "soft_bit_errors": int(err.sum()), "soft_compared": int(m),
+        "hard_len2_bit_errors": int(hbe), "hard_len2_compared": int(hm),
+        "llr_scale_c_sigma2": None if scale is None else round(scale, 4),
+    }))
+
+
+if __name__ == "__main__":
+    main()

@@ -24,7 +24,7 @@ WF_ERR_VALUE, WF_ERR_KEY, WF_ERR_HIP, WF_ERR_DEVICE, WF_ERR_NOMEM = -1, -2, -3, 
 WF_CPM_STATE_BYTES, WF_CPM_STREAM_STATE_BYTES = 16384, 20480      # include/wfhip.h (tests/test_cabi.py compares)
 # wf_option (include/wfhip.h): per-context options set with wf_ctx_set_option
 (WF_OPT_CPM_FORM, WF_OPT_CPM_CHUNK_CALLS, WF_OPT_DET_REPAIR, WF_OPT_DET_FINAL_VERIFY, WF_OPT_ITERATION_SERVER,
- WF_OPT_MCB_TAIL_PERMILLE, WF_OPT_PIPE_RESERVE_CUS, WF_OPT_CPM_SAMPLES_MIN_CALLS) = range(8)
+ WF_OPT_MCB_TAIL_PERMILLE, WF_OPT_PIPE_RESERVE_CUS, WF_OPT_CPM_SAMPLES_MIN_CALLS, WF_OPT_SOFT_CHUNK_CALLS) = range(9)
 
 # name -> (restype, argtypes); must list every function include/wfhip.h declares
 # (tests/test_cabi.py parses the header and compares).
@@ -58,6 +58,8 @@ SIGNATURES = {
     "wf_viterbi_cascaded": (c_int, [_P, POINTER(c_int64), c_int, _P]),
     "wf_viterbi4_detect_count": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, _P, c_int, c_int64, _P, _P]),
     "wf_viterbi4_detect": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, _P]),
+    "wf_viterbi4_soft": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P]),
+    "wf_viterbi4_soft_geometry": (c_int, [_P, c_int64, c_int, POINTER(c_int64)]),
     "wf_viterbi4_detect_window": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "wf_viterbi4_window_state_bytes": (c_int64, []),
     "wf_viterbi4_state_bytes": (c_int64, [c_int]),

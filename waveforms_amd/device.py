@@ -181,6 +181,36 @@ def viterbi_detect_window(mf_rows, length: int, differential: bool = True, warmu
     return bits[:ncalls], syms[:ncalls]
 
 
+def viterbi_soft(rows, differential: bool = True, warmup: int = 0, row_bytes: int = 48, ctx=None):
+    """Max-log-MAP soft output over the SOQPSK 4-state trellis (``wf_viterbi4_soft``; include/wfhip.h states the
+    definition) -> (llr f64[ncalls], bits u8[ncalls]) on device, one fresh burst.  ``rows``: a contiguous device
+    tensor of ncalls rows, 48 B each (float64[n, 3, 2]) or, ``row_bytes=32``, the links' detector-packed rows
+    {Re z1, Im z1, a, b}.  λ_k > 0 favours bit 0, bits_k = λ_k < 0, and transmitted bit j pairs with λ_{j+1}.
+    λ is in metric units: λ/σ² over-states the confidence of the PT and PAM metrics (see tools/soft_bench.py for the
+    fitted scale).  The hard decisions are the ML sequence, not the length-2 detector's, and can have MORE bit errors
+    than it.  Proof counters as for the hard detectors (viterbi_unmerged / viterbi_repaired)."""
+    if row_bytes not in (32, 48):
+        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    nbytes = rows.numel() * rows.element_size()
+    if nbytes % row_bytes:
+        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
+    ncalls = nbytes // row_bytes
+    llr = _hip.empty(max(ncalls, 1), "float64")
+    bits = _hip.empty(ncalls + 16, "uint8")
+    _hip.check(_hip.lib().wf_viterbi4_soft(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(row_bytes),
+                                           int(bool(differential)), int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.stream()))
+    return llr[:ncalls], bits[:ncalls]
+
+
+def viterbi_soft_geometry(ncalls: int, warmup: int = 0, ctx=None) -> dict:
+    """What ``viterbi_soft`` launches for a burst of ``ncalls`` rows on this context (``wf_viterbi4_soft_geometry``)."""
+    g = (ctypes.c_int64 * 4)()
+    _hip.check(_hip.lib().wf_viterbi4_soft_geometry(ctx if ctx is not None else _hip.ctx(), int(ncalls), int(warmup), g))
+    return dict(zip(("chunk_calls", "lanes", "warmup", "scratch_bytes"), (int(v) for v in g)))
+
+
 def viterbi_unmerged(reset: bool = True, ctx=None) -> int:
     """Chunks of the chunk-parallel detectors left UNPROVEN since the last reset (``wf_viterbi4_unmerged``;
     synchronises).  0 = every batch call reproduced the sequential detector bit for bit — which, since chunks

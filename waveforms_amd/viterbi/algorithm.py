@@ -207,6 +207,38 @@ class SOQPSKTrellisDetector:
         self.i += n                         # like iteration(): one call per row, state carried
         return out
 
+    def detect_soft_device(self, mf_rows, warmup: int = 0):
+        """Soft output: ``mf_rows`` float64[n, 3, 2] device tensor -> (llr f64[n], bits u8[n]) on device, the
+        max-log-MAP detector of include/wfhip.h (wf_viterbi4_soft) over this detector's trellis as it stands.
+
+        λ_k > 0 favours bit 0 and bits_k = λ_k < 0; transmitted bit j pairs with λ_{j+1}.  λ is in metric units:
+        with σ the per-component noise deviation, λ/σ² is over-confident for the PT and PAM metrics (they are
+        approximations: truncated pulse, overlapping filter windows), an effective scale of roughly 0.7-0.8/σ² was
+        measured — tools/soft_bench.py fits it.  The hard decisions are the maximum-likelihood sequence under the
+        reference's metric, not those of ``detect`` (length 2): they can have MORE bit errors; the LLRs are for an
+        FEC decoder.  Each call is a fresh burst (free start, free end): ``self.i``, the batch carry and the
+        per-symbol state are left untouched, and it can be mixed with either API."""
+        from waveforms_amd import _hip
+        from waveforms_amd import device as dev
+
+        if self.fsm.trellis is not SOQPSKTrellis4x2DiffEncoded and self.fsm.trellis is not SOQPSKTrellis4x2:
+            raise ValueError("SOQPSKTrellisDetector serves the two 4-state, 2-column SOQPSK trellises (state_exp_term has four entries)")
+        if self._ctx is None:
+            self._ctx = _hip.new_ctx()
+        out = dev.viterbi_soft(mf_rows, self.fsm.trellis is SOQPSKTrellis4x2DiffEncoded, warmup, 48, ctx=self._ctx)
+        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
+        if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
+            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+        return out
+
+    def detect_soft(self, mf_rows: NDArray[np.complex128], warmup: int = 0):
+        """Host in / host out soft form: complex128[n, 3] -> (llr f64[n], bits u8[n]); see ``detect_soft_device``."""
+        from waveforms_amd import _hip
+
+        rows = np.ascontiguousarray(mf_rows, dtype=np.complex128).reshape(-1, 3)
+        llr, bits = self.detect_soft_device(_hip.to_device(rows), warmup)
+        return _hip.to_host(llr), _hip.to_host(bits)
+
     def detect(self, mf_rows: NDArray[np.complex128], warmup: int = 0):
         """Host in / host out batch form: complex128[n, 3] -> (bits u8[n], symbols i8[n])."""
         from waveforms_amd import _hip
