@@ -83,7 +83,8 @@ typedef enum {
                                    * takes the samples form; 0 = the library's 6e6 (below it rows + the row form are faster: one lane per chunk leaves
                                    * most of a short burst's chunks to warm-up), otherwise >= 4096 — tests run the form on bursts an oracle can follow */
     WF_OPT_SOFT_CHUNK_CALLS = 8,  /* wf_viterbi4_soft: rows per chunk (1 .. 8192); 0 = the library's choice (wf_viterbi4_soft_geometry) */
-    WF_OPT_COUNT = 9
+    WF_OPT_CPM_SOFT_CHUNK_CALLS = 9, /* wf_cpm_soft: calls per chunk (1 .. 8192); 0 = the library's choice (wf_cpm_soft_geometry) */
+    WF_OPT_COUNT = 10
 } wf_option;
 int wf_ctx_set_option(wf_ctx *ctx, int key, int64_t value);
 int wf_ctx_get_option(wf_ctx *ctx, int key, int64_t *value);
@@ -253,7 +254,8 @@ int wf_viterbi_cascaded(wf_ctx *ctx, int64_t *h_count, int reset, void *stream);
  * WF_OPT_SOFT_CHUNK_CALLS are; WF_OPT_DET_REPAIR / WF_OPT_DET_FINAL_VERIFY act as for the hard detectors, and the
  * repairs and unproven chunks (forward and backward) are counted in wf_viterbi_repaired / wf_viterbi4_unmerged.
  * Scratch: the context's detector scratch (wf_viterbi4_soft_geometry [3] bytes).  row_bytes not 32 / 48, ncalls < 1,
- * warmup < 0 or a NULL pointer: WF_ERR_VALUE before the context is touched. */
+ * warmup < 0 or a NULL pointer: WF_ERR_VALUE before the context is touched.  (The generic CPM detectors' soft output,
+ * ARTM and PCM/FM: wf_cpm_soft, behind wf_cpm_count_errors below.) */
 int wf_viterbi4_soft(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
                      double *d_llr, uint8_t *d_bits, void *stream);
 /* What wf_viterbi4_soft launches for this burst on this context: h_geom[0] rows per chunk, [1] chunks (= lanes),
@@ -524,6 +526,36 @@ int wf_cpm_viterbi_detect_samples(wf_ctx *ctx, const wf_cpm_detector_config *det
  * (the reference's mappers are natural binary: waveforms/cpm/multih/precoder.py:22-23). */
 int wf_cpm_count_errors(wf_ctx *ctx, const uint8_t *d_decided_u, const int8_t *d_ref_alpha, int M, int64_t m,
                         int64_t *d_counts, void *stream);
+
+/* ---- generic CPM soft output: max-log-MAP, per-bit LLRs, on the full-phase trellis -----------------------------------
+ * The reduced designs (NC < p: ARTM_16, PCMFM_10) carry the phase index per survivor, which a backward recursion has no
+ * survivor to carry; the soft output is therefore defined on the FULL-PHASE trellis of the same matched filters: a spec with
+ * NC = p and S = p M^(Lp-1) <= 64 states (ARTM: the 64 states of ARTM_64, the same 16 filters per call as ARTM_16; PCM/FM:
+ * 20 states).  State s = v + p c: v the phase index, c the Lp - 1 previous symbols.  A burst of N = ncalls calls (rows),
+ * free start and free end; first_call = n0 is the global index of its first call.  Section k (global call n = n0 + k) has
+ * the branches (s, u), u = 0 .. M-1, whose increment, end state, tilt, leaving-symbol modulation index and pre-start variant
+ * are exactly those of cpm_oracle.c at call n:
+ *   inc_k(s, u) = -fma(cos_r, Re Z_k[u + M c], sin_r * Im Z_k[u + M c]),  (cos_r, sin_r) = d_rot_cs[r],  r = (2 v - tilt(n)) mod 2p.
+ * In float64 and in exactly this order of operations:
+ *   ã_0 = 0;  a'_{k+1}(e) = min_{(s,u) -> e} (ã_k(s) + inc_k(s,u)) (+inf if no branch);   ã_{k+1} = a'_{k+1} - min_e a'_{k+1}(e)
+ *   b̃_N = 0;  b'_k(s)     = min_u (inc_k(s,u) + b̃_{k+1}(e(s,u)));                         b̃_k     = b'_k - min_s b'_k(s)
+ *   λ_{k,i} = min_{(s,u): bit_i(u) = 1} ((ã_k(s) + inc_k(s,u)) + b̃_{k+1}(e(s,u))) - min_{(s,u): bit_i(u) = 0} (the same)
+ *   d_llr[lgM k + i] = λ_{k,i},   d_bits[lgM k + i] = λ_{k,i} < 0
+ * Bit i of U is MSB first (the natural binary of the reference's mappers, waveforms/cpm/multih/precoder.py:22-23).  Section
+ * k's input is the symbol whose filter column opens at call k (wf_cpm_viterbi_detect decides it at call k + D - 1), so
+ * transmitted bit j pairs with λ[j].  λ > 0 favours bit 0; λ is in metric units, no scale baked in.
+ * d_rows_ri: ncalls x M^Lp complex128, 16-byte aligned (the rows wf_cpm_viterbi_detect reads); det->D is ignored.  Each call
+ * is a fresh burst.  Chunk-parallel with the proof and cascading repair of the hard detectors in BOTH directions, so the
+ * result is bitwise the definition whatever `warmup` (calls, 0 = library default) and WF_OPT_CPM_SOFT_CHUNK_CALLS are;
+ * WF_OPT_DET_REPAIR / WF_OPT_DET_FINAL_VERIFY act as for the hard detectors, repairs and unproven chunks (both directions)
+ * are counted in wf_viterbi_repaired / wf_viterbi4_unmerged.  Scratch: the context's detector scratch
+ * (wf_cpm_soft_geometry [3] bytes).  A NULL pointer, ncalls < 1, first_call < 0, warmup < 0, M not 2 / 4, nh not 1 / 2,
+ * Lp outside 1 .. 3, NC != p or more than 64 states (ARTM_256): WF_ERR_VALUE before the context is touched. */
+int wf_cpm_soft(wf_ctx *ctx, const wf_cpm_detector_config *det, const double *d_rot_cs, const double *d_rows_ri,
+                int64_t ncalls, int64_t first_call, int warmup, double *d_llr, uint8_t *d_bits, void *stream);
+/* What wf_cpm_soft launches for this burst on this context: h_geom[0] calls per chunk, [1] chunks, [2] warm-up calls used,
+ * [3] scratch bytes.  Host only, no device work. */
+int wf_cpm_soft_geometry(wf_ctx *ctx, const wf_cpm_detector_config *det, int64_t ncalls, int warmup, int64_t *h_geom);
 
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter

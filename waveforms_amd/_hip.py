@@ -24,7 +24,8 @@ WF_ERR_VALUE, WF_ERR_KEY, WF_ERR_HIP, WF_ERR_DEVICE, WF_ERR_NOMEM = -1, -2, -3, 
 WF_CPM_STATE_BYTES, WF_CPM_STREAM_STATE_BYTES = 16384, 20480      # include/wfhip.h (tests/test_cabi.py compares)
 # wf_option (include/wfhip.h): per-context options set with wf_ctx_set_option
 (WF_OPT_CPM_FORM, WF_OPT_CPM_CHUNK_CALLS, WF_OPT_DET_REPAIR, WF_OPT_DET_FINAL_VERIFY, WF_OPT_ITERATION_SERVER,
- WF_OPT_MCB_TAIL_PERMILLE, WF_OPT_PIPE_RESERVE_CUS, WF_OPT_CPM_SAMPLES_MIN_CALLS, WF_OPT_SOFT_CHUNK_CALLS) = range(9)
+ WF_OPT_MCB_TAIL_PERMILLE, WF_OPT_PIPE_RESERVE_CUS, WF_OPT_CPM_SAMPLES_MIN_CALLS, WF_OPT_SOFT_CHUNK_CALLS,
+ WF_OPT_CPM_SOFT_CHUNK_CALLS) = range(10)
 
 # name -> (restype, argtypes); must list every function include/wfhip.h declares
 # (tests/test_cabi.py parses the header and compares).
@@ -93,6 +94,8 @@ SIGNATURES = {
     "wf_cpm_viterbi_detect": (c_int, [_P, _P, _P, _P, c_int64, c_int, _P, _P, _P]),
     "wf_cpm_viterbi_detect_samples": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int64, c_int64, c_int, c_int64, c_int, _P, _P, _P]),
     "wf_cpm_count_errors": (c_int, [_P, _P, _P, c_int, c_int64, _P, _P]),
+    "wf_cpm_soft": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, _P, _P, _P]),
+    "wf_cpm_soft_geometry": (c_int, [_P, _P, c_int64, c_int, POINTER(c_int64)]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

@@ -211,6 +211,40 @@ def viterbi_soft_geometry(ncalls: int, warmup: int = 0, ctx=None) -> dict:
     return dict(zip(("chunk_calls", "lanes", "warmup", "scratch_bytes"), (int(v) for v in g)))
 
 
+def cpm_soft(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None):
+    """Max-log-MAP soft output of the generic CPM trellis (``wf_cpm_soft``; include/wfhip.h states the definition) -> (llr
+    f64[n lgM], bits u8[n lgM]) on device, one fresh burst.  ``spec``: a full-phase design (NC = p, at most 64 states:
+    ``viterbi.cpm.full_phase``, e.g. ARTM_64, PCMFM_20); ``rows``: contiguous device float64[n, M^Lp, 2], the rows
+    ``wf_cpm_viterbi_detect`` reads; ``first_call``: the global index of the burst's first call.  λ > 0 favours bit 0, bits
+    = λ < 0, bit i (MSB first) of symbol j pairs with λ[lgM j + i].  ``d_rot``: the device rotation table
+    (``rotation_table(spec)``) if the caller holds one.  Proof counters as for the hard detectors (viterbi_unmerged /
+    viterbi_repaired)."""
+    from .viterbi.cpm import rotation_table
+
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    per = 2 * spec.nfilt
+    if rows.numel() % per:
+        raise ValueError(f"{rows.numel()} doubles of rows are not a whole number of {spec.nfilt}-filter rows")
+    n, lg = rows.numel() // per, spec.bits_per_symbol
+    if d_rot is None:
+        d_rot = _hip.to_device(rotation_table(spec))
+    llr = _hip.empty(max(n * lg, 1), "float64")
+    bits = _hip.empty(n * lg + 16, "uint8")
+    cfg = spec.c_config()
+    _hip.check(_hip.lib().wf_cpm_soft(ctx if ctx is not None else _hip.ctx(), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
+                                      int(first_call), int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.stream()))
+    return llr[:n * lg], bits[:n * lg]
+
+
+def cpm_soft_geometry(spec, ncalls: int, warmup: int = 0, ctx=None) -> dict:
+    """What ``cpm_soft`` launches for a burst of ``ncalls`` calls on this context (``wf_cpm_soft_geometry``)."""
+    g = (ctypes.c_int64 * 4)()
+    cfg = spec.c_config()
+    _hip.check(_hip.lib().wf_cpm_soft_geometry(ctx if ctx is not None else _hip.ctx(), ctypes.byref(cfg), int(ncalls), int(warmup), g))
+    return dict(zip(("chunk_calls", "chunks", "warmup", "scratch_bytes"), (int(v) for v in g)))
+
+
 def viterbi_unmerged(reset: bool = True, ctx=None) -> int:
     """Chunks of the chunk-parallel detectors left UNPROVEN since the last reset (``wf_viterbi4_unmerged``;
     synchronises).  0 = every batch call reproduced the sequential detector bit for bit — which, since chunks

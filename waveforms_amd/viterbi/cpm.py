@@ -27,12 +27,13 @@ for the first three rows, 4e5 for the last two; the 16-state row is reproduced b
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 from dataclasses import dataclass
 
 import numpy as np
 
-__all__ = ["CPMDetectorSpec", "ARTM_16", "ARTM_64", "ARTM_256", "PCMFM_10", "CPMTrellisDetector", "matched_filter_templates", "rotation_table", "detector_kernel_name",
-           "filter_geometry", "sigma_for_ebn0"]
+__all__ = ["CPMDetectorSpec", "ARTM_16", "ARTM_64", "ARTM_256", "PCMFM_10", "PCMFM_20", "CPMTrellisDetector", "matched_filter_templates", "rotation_table", "detector_kernel_name",
+           "filter_geometry", "sigma_for_ebn0", "full_phase"]
 
 
 @dataclass(frozen=True)
@@ -80,6 +81,14 @@ ARTM_64 = CPMDetectorSpec(M=4, p=16, K=(4, 5), Lp=2, NC=16, D=32)
 ARTM_256 = CPMDetectorSpec(M=4, p=16, K=(4, 5), Lp=3, NC=16, D=32)
 # PCMFM_NUMER / DENOM = 7 / 10 (waveforms/cpm/pcmfm/__init__.py:5-6), binary
 PCMFM_10 = CPMDetectorSpec(M=2, p=10, K=(7,), Lp=2, NC=5, D=32)
+# ... and its full-phase trellis (NC = p): 20 states on the same 4 filters — what the soft output of PCM/FM runs on
+PCMFM_20 = CPMDetectorSpec(M=2, p=10, K=(7,), Lp=2, NC=10, D=32)
+
+
+def full_phase(spec: CPMDetectorSpec) -> CPMDetectorSpec:
+    """``spec`` with every phase state in the trellis (NC = p): the trellis the soft output is defined on (include/wfhip.h,
+    wf_cpm_soft) — ARTM_16 -> ARTM_64, PCMFM_10 -> PCMFM_20, the same matched filters."""
+    return dataclasses.replace(spec, NC=spec.p)
 
 
 def detector_kernel_name(spec: "CPMDetectorSpec", ncalls: int = 10_000_000, warmup: int = 0, ctx=None, info4: list | None = None,
@@ -206,6 +215,40 @@ class CPMTrellisDetector:
                 self._d_state.copy_(keep)
             raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
         return out[:n]
+
+    def detect_soft_device(self, rows, first_call: int = 0, warmup: int = 0):
+        """Soft output, max-log-MAP (``wf_cpm_soft``; include/wfhip.h states the definition), over ``full_phase(self.spec)``:
+        the trellis of this detector's matched filters with every phase state in it, so ``CPMTrellisDetector(ARTM_16).
+        detect_soft`` gives the 64-state (ARTM_64) soft output of the same rows, and PCMFM_10 the 20-state one (PCMFM_20).
+        ``rows``: float64[n, nfilt, 2] device tensor, one fresh burst (free start, free end) whose first call has the global
+        index ``first_call`` -> (llr f64[n lgM], bits u8[n lgM]) on device.  λ > 0 favours bit 0 and bits = λ < 0; bit i
+        (MSB first) of symbol j pairs with λ[lgM j + i], symbol j being the one whose filter column opens at call j.  λ is in
+        metric units, no scale baked in.  The hard carry (``self.i``, the device state) is left untouched.  ValueError if the
+        full-phase trellis has more than 64 states (ARTM_256)."""
+        from waveforms_amd import _hip, device as dev
+
+        spec = full_phase(self.spec)
+        if spec.nstates > 64:
+            raise ValueError(f"the full-phase trellis of {self.spec} has {spec.nstates} states: the soft output serves up to 64")
+        if tuple(rows.shape[1:]) != (self.spec.nfilt, 2):
+            raise ValueError(f"rows must be [n, {self.spec.nfilt}, 2] float64")
+        if self._ctx is None:
+            self._ctx = _hip.new_ctx()
+            self._d_rot = _hip.to_device(rotation_table(self.spec))
+            self._d_state = _hip.zeros(_hip.WF_CPM_STATE_BYTES // 8, "int64")
+        out = dev.cpm_soft(rows, spec, first_call, warmup, ctx=self._ctx, d_rot=self._d_rot)
+        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
+        if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
+            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+        return out
+
+    def detect_soft(self, rows, first_call: int = 0, warmup: int = 0):
+        """Host in / host out soft form: complex128[n][M^Lp] -> (llr f64[n lgM], bits u8[n lgM]); see ``detect_soft_device``."""
+        from waveforms_amd import _hip
+
+        rows = np.ascontiguousarray(rows, dtype=np.complex128).reshape(-1, self.spec.nfilt)
+        llr, bits = self.detect_soft_device(_hip.to_device(rows), first_call, warmup)
+        return _hip.to_host(llr), _hip.to_host(bits)
 
     def detect(self, rows, warmup: int = 0) -> np.ndarray:
         from waveforms_amd import _hip
