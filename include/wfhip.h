@@ -557,6 +557,50 @@ int wf_cpm_soft(wf_ctx *ctx, const wf_cpm_detector_config *det, const double *d_
  * [3] scratch bytes.  Host only, no device work. */
 int wf_cpm_soft_geometry(wf_ctx *ctx, const wf_cpm_detector_config *det, int64_t ncalls, int warmup, int64_t *h_geom);
 
+/* ---- LDPC codes: systematic encoder and layered normalized min-sum decoder ------------------------------------------
+ * A code is an opaque handle made once on the host.  H has n variables and m checks, numbered in LAYER order: check c's
+ * edges are h_edge_var[h_check_ptr[c] .. h_check_ptr[c+1]) (table order), layer l holds checks h_layer_ptr[l] ..
+ * h_layer_ptr[l+1].  Transmitted position t (0 .. n_tx-1) carries variable h_tx_var[t]: this one table is the bit
+ * interleaver and the puncturing map (a variable it does not name is punctured).  h_info_var: the k information
+ * variables, in message order; h_parity_gen: (n - k) rows of ceil(k / 64) words, row r for the r-th NON-information
+ * variable in increasing order, bit i of word w (LSB first) multiplying message bit 64 w + i (parity = A u over GF(2));
+ * NULL makes a decode-only code.  Checked on the host before any device memory is touched (WF_ERR_VALUE): 2 <= n <= 32768,
+ * every check degree 2 .. 32, no variable twice in a check or in two checks of one layer, tx_var a bijection onto the
+ * variables it names, info_var distinct and in range.  The tables are uploaded into device memory the handle owns
+ * (synchronous); wf_ldpc_code_free releases it (synchronous). */
+typedef struct wf_ldpc_code wf_ldpc_code;
+int wf_ldpc_code_create(wf_ctx *ctx, int32_t n, int32_t m, const int32_t *h_check_ptr, const int32_t *h_edge_var,
+                        int32_t nlayers, const int32_t *h_layer_ptr, int32_t n_tx, const int32_t *h_tx_var, int32_t k,
+                        const int32_t *h_info_var, const uint64_t *h_parity_gen, wf_ldpc_code **out);
+int wf_ldpc_code_free(wf_ldpc_code *code);
+/* d_info: ncw x k bits (u8 0 / 1) -> d_tx: ncw x n_tx bits in transmit order (codeword b, position t = variable
+ * tx_var[t]).  Decode-only code: WF_ERR_VALUE. */
+int wf_ldpc_encode(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_t *d_info, int64_t ncw, uint8_t *d_tx, void *stream);
+/* Codeword b's LLR for transmitted position t is d_llr[b n_tx + t], λ > 0 favouring bit 0 (as the soft detectors give it;
+ * the caller aligns by offsetting the pointer: for wf_viterbi4_soft, transmitted bit j is λ_{j+1}).  Per codeword, in
+ * float32 and in exactly this order:
+ *   L_v = (float)(scale * λ[src v]) (product in float64, then rounded); L_v = 0 for a punctured v; R_e = 0.
+ *   Iteration 0: x̂_v = [L_v < 0]; if H x̂ = 0 the codeword is done with iters = 0.
+ *   For t = 1 .. max_iter, for each layer in order, for each check c of the layer, edges e in table order:
+ *     T_e = L_{v_e} - R_e
+ *     m1 = min |T_e|, e1 = the first e attaining it (strict <), m2 = min over e != e1 of |T_e|, S = XOR of [T_e < 0]
+ *     R_e = (float)(alpha * (e == e1 ? m2 : m1)), negated when S XOR [T_e < 0]
+ *     L_{v_e} = T_e + R_e
+ *   After each full iteration x̂ = [L < 0]; if H x̂ = 0 the codeword stops with iters = t.  Otherwise iters = max_iter
+ *   and the codeword is not converged.  A codeword that has stopped is never updated again.
+ * Outputs (each may be NULL): d_info_bits ncw x k (x̂ at the information variables), d_post ncw x n (L, by variable),
+ * d_iters ncw.  With d_ref_info (ncw x k bits), d_counts[0..3] are ADDED: information bit errors, codewords with any
+ * information bit error, codewords not converged, iterations summed.  Asynchronous on `stream`; the check state of a code
+ * too large for LDS lives in the context's detector scratch (wf_ldpc_decode_geometry).  A NULL code / ctx / d_llr,
+ * ncw < 1, max_iter outside 1 .. 10000, scale or alpha not finite and positive, d_ref_info without d_counts: WF_ERR_VALUE. */
+int wf_ldpc_decode(wf_ctx *ctx, const wf_ldpc_code *code, const double *d_llr, int64_t ncw, double scale, float alpha,
+                   int max_iter, uint8_t *d_info_bits, float *d_post, int32_t *d_iters,
+                   const uint8_t *d_ref_info, int64_t *d_counts, void *stream);
+/* What wf_ldpc_decode launches for ncw codewords: h_geom[0] check-state form (0: LDS, 1: context scratch), [1] codewords
+ * per workgroup G, [2] workgroups per launch (the scratch form decodes a longer batch in several launches), [3] dynamic
+ * LDS bytes per workgroup, [4] scratch bytes.  Host only. */
+int wf_ldpc_decode_geometry(wf_ctx *ctx, const wf_ldpc_code *code, int64_t ncw, int64_t *h_geom);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

@@ -1,0 +1,87 @@
+"""Coded BER / FER curve of the LDPC-coded SOQPSK-TG chain (waveforms_amd/encoding/coded.py) and the decoder's speed; prints
+ONE JSON line.
+
+    python tools/coded_ber.py [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N] [--detector PT] [--steps 5]
+
+Eb/N0 is per information bit.  Per point: coded BER and FER, codewords not converged, mean iterations, and the soft
+detector's uncoded BER (λ < 0 against the coded bits) on the same channel bits.  Each block is one burst of
+``--block-codewords`` codewords; blocks run until ``--codewords`` have been decoded.  Timing: ``--steps`` more blocks at the
+point, each stage bracketed by device events (encode, front end = PRBS + precoder + modulator + channel + matched filters,
+soft detector, decode); the decoder's throughput is information bits / decode time.
+"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--code", default="demo", choices=["demo", "demo16k"])
+    ap.add_argument("--ebn0", type=float, nargs="+", default=[4.0, 5.0, 6.0, 7.0, 8.0])
+    ap.add_argument("--codewords", type=int, default=20000)
+    ap.add_argument("--block-codewords", type=int, default=0, help="codewords per burst (0: about 1e7 channel bits)")
+    ap.add_argument("--detector", default="PT", choices=["PT", "PAM"])
+    ap.add_argument("--max-iter", type=int, default=50)
+    ap.add_argument("--alpha", type=float, default=0.75)
+    ap.add_argument("--steps", type=int, default=5)
+    args = ap.parse_args()
+
+    import torch
+
+    from waveforms_amd import device as dev
+    from waveforms_amd.encoding import ldpc
+    from waveforms_amd.encoding.coded import CodedSOQPSKLink
+
+    torch.cuda.set_device(0)
+    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
+    per = args.block_codewords or max(1, int(1e7) // code.n_tx)
+    per = min(per, args.codewords)
+    link = CodedSOQPSKLink(code, per, detector=args.detector, alpha=args.alpha, max_iter=args.max_iter)
+    out = {"tool": "coded_ber", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
+           "alpha": args.alpha, "max_iter": args.max_iter, "block_codewords": per,
+           "geometry": dev.ldpc_decode_geometry(code, per), "points": []}
+    for e in args.ebn0:
+        link.reset_counts()
+        b = 0
+        while b * per < args.codewords:
+            link.run_block(e, seed=1, stream_id=b)
+            b += 1
+        be, fe, nc, m, mean_it = link.result()
+        ue, um = link.uncoded_result()
+        ncw = b * per
+        # timing: the same stages, one event pair each, over --steps further blocks
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ms = np.zeros(4)
+        for s in range(args.steps):
+            ev[0].record()
+            info = link.info_bits(b + s)
+            tx = dev.ldpc_encode(code, info)
+            ev[1].record()
+            rows, _ = link.front_end(tx, e, 1, b + s)
+            ev[2].record()
+            llr, _ = link.soft(rows)
+            ev[3].record()
+            dev.ldpc_decode(code, llr, scale=link.llr_scale, alpha=args.alpha, max_iter=args.max_iter)
+            ev[4].record()
+            torch.cuda.synchronize()
+            ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(4)]
+        ms /= max(args.steps, 1)
+        out["points"].append({
+            "ebn0_info_db": e, "ebn0_channel_db": round(e + 10 * np.log10(code.k / code.n_tx), 3), "codewords": ncw,
+            "coded_ber": be / m, "fer": fe / ncw, "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
+            "mean_iters": round(mean_it, 3), "uncoded_ber": ue / um,
+            "ms_per_block": {"encode": round(ms[0], 4), "front_end": round(ms[1], 4), "soft_detector": round(ms[2], 4),
+                             "decode": round(ms[3], 4)},
+            "decode_info_gbps": round(per * code.k / (ms[3] * 1e-3) / 1e9, 3) if ms[3] > 0 else None,
+        })
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -96,6 +96,12 @@ SIGNATURES = {
     "wf_cpm_count_errors": (c_int, [_P, _P, _P, c_int, c_int64, _P, _P]),
     "wf_cpm_soft": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, _P, _P, _P]),
     "wf_cpm_soft_geometry": (c_int, [_P, _P, c_int64, c_int, POINTER(c_int64)]),
+    "wf_ldpc_code_create": (c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, ctypes.c_int32,
+                                    _P, _P, POINTER(c_void_p)]),
+    "wf_ldpc_code_free": (c_int, [_P]),
+    "wf_ldpc_encode": (c_int, [_P, _P, _P, c_int64, _P, _P]),
+    "wf_ldpc_decode": (c_int, [_P, _P, _P, c_int64, c_double, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P]),
+    "wf_ldpc_decode_geometry": (c_int, [_P, _P, c_int64, POINTER(c_int64)]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

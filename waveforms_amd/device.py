@@ -307,3 +307,45 @@ def cpm_count_errors(decided_u, ref_alpha, M: int, m: int, counts=None):
     _hip.check(_hip.lib().wf_cpm_count_errors(_hip.ctx(), _hip.ptr(decided_u), _hip.ptr(ref_alpha), M, m, _hip.ptr(counts),
                                               _hip.stream()))
     return counts
+
+
+def ldpc_encode(code, d_info):
+    """LDPC encoder (``wf_ldpc_encode``): device messages (ncw x k bits, u8) -> transmitted bits (ncw x n_tx, u8) in
+    transmit order.  ``code``: a :class:`waveforms_amd.encoding.ldpc.LDPCCode`."""
+    if not d_info.is_contiguous() or d_info.numel() % code.k or d_info.numel() == 0:
+        raise ValueError(f"messages must be a contiguous whole number of k = {code.k} bits")
+    ncw = d_info.numel() // code.k
+    out = _hip.empty((ncw, code.n_tx), "uint8")
+    _hip.check(_hip.lib().wf_ldpc_encode(_hip.ctx(), code.handle(), _hip.ptr(d_info), ncw, _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def ldpc_decode(code, d_llr, scale: float = 1.0, alpha: float = 0.75, max_iter: int = 50, ref_info=None, counts=None,
+                want_post: bool = False) -> dict:
+    """Layered normalized min-sum decoding (``wf_ldpc_decode``; include/wfhip.h states the definition) of ncw codewords:
+    ``d_llr`` contiguous float64, codeword b's λ for transmitted position t at [b n_tx + t], λ > 0 favouring bit 0.  Returns
+    {"info_bits": u8 ncw x k, "iters": int32 ncw, "post": float32 ncw x n or None, "counts": the int64[4] counts or None}.
+    With ``ref_info`` (device ncw x k bits) the decoder ADDS to ``counts`` (fresh zeros if None): information bit errors,
+    codewords with an information bit error, codewords not converged, iterations summed."""
+    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
+        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
+    ncw = d_llr.numel() // code.n_tx
+    info = _hip.empty((ncw, code.k), "uint8")
+    iters = _hip.empty(ncw, "int32")
+    post = _hip.torch().empty((ncw, code.n), dtype=_hip.torch().float32, device="cuda") if want_post else None
+    if ref_info is not None:
+        if ref_info.numel() != ncw * code.k or not ref_info.is_contiguous():
+            raise ValueError("ref_info must hold ncw x k contiguous bits")
+        if counts is None:
+            counts = _hip.zeros(4, "int64")
+    _hip.check(_hip.lib().wf_ldpc_decode(_hip.ctx(), code.handle(), _hip.ptr(d_llr), ncw, float(scale), float(alpha), int(max_iter),
+                                         _hip.ptr(info), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ref_info),
+                                         _hip.ptr(counts) if ref_info is not None else None, _hip.stream()))
+    return {"info_bits": info, "iters": iters, "post": post, "counts": counts if ref_info is not None else None}
+
+
+def ldpc_decode_geometry(code, ncw: int) -> dict:
+    """What ``ldpc_decode`` launches for ``ncw`` codewords (``wf_ldpc_decode_geometry``)."""
+    g = (ctypes.c_int64 * 5)()
+    _hip.check(_hip.lib().wf_ldpc_decode_geometry(_hip.ctx(), code.handle(), int(ncw), g))
+    return dict(zip(("state_in_scratch", "codewords_per_workgroup", "workgroups", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
