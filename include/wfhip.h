@@ -262,6 +262,25 @@ int wf_viterbi4_soft(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_
  * [2] warm-up rows actually used, [3] scratch bytes. */
 int wf_viterbi4_soft_geometry(wf_ctx *ctx, int64_t ncalls, int warmup, int64_t *h_geom);
 
+/* wf_viterbi4_soft with a per-row prior on the input bit and EXTRINSIC output: the inner detector of iterative detection
+ * and decoding.  Everything of wf_viterbi4_soft holds (rows, alignment, warm-up, chunking, options, counters, scratch:
+ * wf_viterbi4_soft_geometry describes this call too) with, in float64 and in exactly this order of operations:
+ *   π_k = apriori_scale * (double)d_apriori[k]                               (0 when d_apriori is NULL)
+ *   inc'_k(b) = inc_k(b) + π_k when inp b = 1, inc_k(b) otherwise            (one float64 addition)
+ *   ã, b̃: the recursions of wf_viterbi4_soft with inc' in place of inc
+ *   d_ext[k]  = λᵉ_k = min_{b: inp b = 1} ((ã_k(start b) + inc_k(b)) + b̃_{k+1}(end b)) - min_{b: inp b = 0} (the same)
+ *               (the CHANNEL-only inc_k in section k: the prior of bit k is never added, so none is subtracted)
+ *   d_bits[k] = (λᵉ_k + π_k) < 0
+ * π > 0 favours bit 0, as λ does.  d_apriori: ncalls float32 (4-byte aligned), finite; row k's prior is d_apriori[k], so the
+ * prior of transmitted bit j goes to d_apriori[j + 1].  With d_apriori NULL the result is bitwise wf_viterbi4_soft's.
+ * A prior may be negative, so an increment inc' may be negative or -0; the implementation relies on this instead of on
+ * non-negative increments: a normalised metric ã, b̃ is x - min x, which is >= +0 and never -0, a sum with an operand that
+ * is not -0 is not -0, so no operand of a min is ever -0, equal operands are bitwise equal and the min does not depend
+ * on the order in which a machine takes it.  Rows and priors must be finite.  apriori_scale not finite, or any
+ * argument wf_viterbi4_soft refuses: WF_ERR_VALUE before the context is touched. */
+int wf_viterbi4_soft_apriori(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
+                             const float *d_apriori, double apriori_scale, double *d_ext, uint8_t *d_bits, void *stream);
+
 /* wf_viterbi4_detect + wf_count_errors in one call (fresh detector): decision k is
  * compared with reference element k - skip for 0 <= k - skip < ncompare
  * (examples/soqpsk_detection.py:201-209: skip = length); counts are ADDED to d_counts[0..1]. */
@@ -600,6 +619,26 @@ int wf_ldpc_decode(wf_ctx *ctx, const wf_ldpc_code *code, const double *d_llr, i
  * per workgroup G, [2] workgroups per launch (the scratch form decodes a longer batch in several launches), [3] dynamic
  * LDS bytes per workgroup, [4] scratch bytes.  Host only. */
 int wf_ldpc_decode_geometry(wf_ctx *ctx, const wf_ldpc_code *code, int64_t ncw, int64_t *h_geom);
+/* wf_ldpc_decode with a per-codeword freeze state and an extrinsic output: the outer decoder of iterative detection and
+ * decoding, called once per outer pass.  d_state: ncw bytes, in and out (0 = open, 1 = frozen).  Per codeword b:
+ *   state 1 on entry: NOTHING of the codeword is read or written (d_info_bits, d_ext, d_post, d_iters and the state keep
+ *     what an earlier call left) and it costs no decoding work.
+ *   state 0: decoded exactly as wf_ldpc_decode defines (same float32 order, cold start R = 0, iteration 0 is the syndrome
+ *     of the input).  d_iters[b] is INCREASED by the iterations used (max_iter when not converged).  If the codeword
+ *     stopped with H x̂ = 0 (at any iteration 0 .. max_iter): state <- 1 and d_ext[b ext_stride + t] = x̂_{v_t} ? -ext_sat :
+ *     +ext_sat.  Otherwise d_ext[b ext_stride + t] = min(max(L_{v_t} - Lch_{v_t}, -ext_clip), +ext_clip) with
+ *     Lch_v = (float)(scale * λ) as the decoder loaded it and the subtraction in float32 (v_t = tx_var[t]).
+ * A punctured variable has no d_ext entry.  ext_stride >= n_tx lets the call write straight into a burst's prior buffer
+ * (wf_viterbi4_soft_apriori: d_ext = prior + 1, ext_stride = n_tx for codewords sent back to back).  d_info_bits, d_post
+ * and d_iters may be NULL.  ext_clip > 0 (INFINITY: no clip), ext_sat finite and > 0, d_state and d_ext not NULL, and the
+ * argument checks of wf_ldpc_decode: WF_ERR_VALUE otherwise.  Launch geometry: wf_ldpc_decode_geometry. */
+int wf_ldpc_decode_ext(wf_ctx *ctx, const wf_ldpc_code *code, const double *d_llr, int64_t ncw, double scale, float alpha,
+                       int max_iter, uint8_t *d_state, uint8_t *d_info_bits, float *d_post, int32_t *d_iters, float *d_ext,
+                       int64_t ext_stride, float ext_clip, float ext_sat, void *stream);
+/* The four counts of wf_ldpc_decode after the last outer pass, ADDED to d_counts[0..3]: information bit errors of
+ * d_info_bits against d_ref_info (ncw x k bits each), codewords with one, codewords whose d_state is 0, d_iters summed. */
+int wf_ldpc_count(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_t *d_info_bits, const uint8_t *d_ref_info,
+                  const uint8_t *d_state, const int32_t *d_iters, int64_t ncw, int64_t *d_counts, void *stream);
 
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter

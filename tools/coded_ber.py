@@ -2,12 +2,18 @@
 ONE JSON line.
 
     python tools/coded_ber.py [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N] [--detector PT] [--steps 5]
+                              [--outer N --inner M --damping D]
 
 Eb/N0 is per information bit.  Per point: coded BER and FER, codewords not converged, mean iterations, and the soft
 detector's uncoded BER (λ < 0 against the coded bits) on the same channel bits.  Each block is one burst of
 ``--block-codewords`` codewords; blocks run until ``--codewords`` have been decoded.  Timing: ``--steps`` more blocks at the
 point, each stage bracketed by device events (encode, front end = PRBS + precoder + modulator + channel + matched filters,
 soft detector, decode); the decoder's throughput is information bits / decode time.
+
+With ``--outer N`` (> 0) every point also runs the iterative chain (IterativeSOQPSKLink: N outer passes of ``--inner`` decoder
+iterations, prior scaled by ``--damping``) on the SAME blocks, next to the one-pass curve: BER / FER and open codewords after
+every pass, total inner iterations, and the time per block split into the detector passes and the decoder passes (each pass
+bracketed by device events; the first detector pass is the plain detector).
 """
 import argparse
 import json
@@ -30,13 +36,16 @@ def main() -> None:
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--alpha", type=float, default=0.75)
     ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--outer", type=int, default=0, help="outer passes of the iterative chain (0: one-pass curve only)")
+    ap.add_argument("--inner", type=int, default=5, help="decoder iterations per outer pass")
+    ap.add_argument("--damping", type=float, default=0.7, help="scale of the prior fed back to the detector")
     args = ap.parse_args()
 
     import torch
 
     from waveforms_amd import device as dev
     from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CodedSOQPSKLink
+    from waveforms_amd.encoding.coded import CodedSOQPSKLink, IterativeSOQPSKLink
 
     torch.cuda.set_device(0)
     code = ldpc.demo_code(128 if args.code == "demo" else 1024)
@@ -46,6 +55,12 @@ def main() -> None:
     out = {"tool": "coded_ber", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
            "alpha": args.alpha, "max_iter": args.max_iter, "block_codewords": per,
            "geometry": dev.ldpc_decode_geometry(code, per), "points": []}
+    idd = None
+    if args.outer > 0:
+        idd = IterativeSOQPSKLink(code, per, detector=args.detector, alpha=args.alpha, outer=args.outer, inner=args.inner,
+                                  damping=args.damping, per_pass=True)
+        out["iterative"] = {"outer": idd.outer, "inner": idd.inner, "damping": idd.damping, "ext_sat": idd.ext_sat,
+                            "ext_clip": None if np.isinf(idd.ext_clip) else idd.ext_clip}
     for e in args.ebn0:
         link.reset_counts()
         b = 0
@@ -72,6 +87,38 @@ def main() -> None:
             torch.cuda.synchronize()
             ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(4)]
         ms /= max(args.steps, 1)
+        it_point = None
+        if idd is not None:
+            idd.reset_counts()
+            for blk in range(b):
+                idd.run_block(e, seed=1, stream_id=blk)
+            ibe, ife, inc, im, imean = idd.result()
+            passes = idd.pass_results()
+            # timing: front end once (not timed again), then every pass bracketed
+            pev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * idd.outer + 1)]
+            det_ms, dec_ms = np.zeros(idd.outer), np.zeros(idd.outer)
+            for s in range(args.steps):
+                tx = dev.ldpc_encode(code, idd.info_bits(b + s))
+                rows, _ = idd.front_end(tx, e, 1, b + s)
+                idd.begin(int(rows.shape[0]))
+                pev[0].record()
+                for o in range(idd.outer):
+                    ext, _ = idd.detect(rows, first=o == 0)
+                    pev[2 * o + 1].record()
+                    idd.decode(ext)
+                    pev[2 * o + 2].record()
+                torch.cuda.synchronize()
+                det_ms += [pev[2 * o].elapsed_time(pev[2 * o + 1]) for o in range(idd.outer)]
+                dec_ms += [pev[2 * o + 1].elapsed_time(pev[2 * o + 2]) for o in range(idd.outer)]
+            det_ms /= max(args.steps, 1)
+            dec_ms /= max(args.steps, 1)
+            it_point = {
+                "coded_ber": ibe / im, "fer": ife / ncw, "info_bit_errors": ibe, "codeword_errors": ife, "open": inc,
+                "total_inner_iters_mean": round(imean, 3),
+                "per_pass": [{"info_bit_errors": p[0], "codeword_errors": p[1], "open": p[2], "iters_mean": round(p[3], 3)} for p in passes],
+                "ms_per_block": {"detector_passes": [round(v, 4) for v in det_ms], "decoder_passes": [round(v, 4) for v in dec_ms],
+                                 "detector_total": round(float(det_ms.sum()), 4), "decoder_total": round(float(dec_ms.sum()), 4)},
+            }
         out["points"].append({
             "ebn0_info_db": e, "ebn0_channel_db": round(e + 10 * np.log10(code.k / code.n_tx), 3), "codewords": ncw,
             "coded_ber": be / m, "fer": fe / ncw, "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
@@ -79,6 +126,7 @@ def main() -> None:
             "ms_per_block": {"encode": round(ms[0], 4), "front_end": round(ms[1], 4), "soft_detector": round(ms[2], 4),
                              "decode": round(ms[3], 4)},
             "decode_info_gbps": round(per * code.k / (ms[3] * 1e-3) / 1e9, 3) if ms[3] > 0 else None,
+            **({"iterative": it_point} if it_point is not None else {}),
         })
     print(json.dumps(out))
 

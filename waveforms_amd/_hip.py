@@ -61,6 +61,7 @@ SIGNATURES = {
     "wf_viterbi4_detect": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, _P]),
     "wf_viterbi4_soft": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P]),
     "wf_viterbi4_soft_geometry": (c_int, [_P, c_int64, c_int, POINTER(c_int64)]),
+    "wf_viterbi4_soft_apriori": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_double, _P, _P, _P]),
     "wf_viterbi4_detect_window": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "wf_viterbi4_window_state_bytes": (c_int64, []),
     "wf_viterbi4_state_bytes": (c_int64, [c_int]),
@@ -102,6 +103,9 @@ SIGNATURES = {
     "wf_ldpc_encode": (c_int, [_P, _P, _P, c_int64, _P, _P]),
     "wf_ldpc_decode": (c_int, [_P, _P, _P, c_int64, c_double, ctypes.c_float, c_int, _P, _P, _P, _P, _P, _P]),
     "wf_ldpc_decode_geometry": (c_int, [_P, _P, c_int64, POINTER(c_int64)]),
+    "wf_ldpc_decode_ext": (c_int, [_P, _P, _P, c_int64, c_double, ctypes.c_float, c_int, _P, _P, _P, _P, _P, c_int64, ctypes.c_float,
+                           ctypes.c_float, _P]),
+    "wf_ldpc_count": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, _P, _P]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),
@@ -292,7 +296,7 @@ def device_check() -> None:
 
 
 # ------------------------------------------------------------------ buffers
-_NP2T = {"uint8": "uint8", "int8": "int8", "float64": "float64", "int64": "int64", "int32": "int32"}
+_NP2T = {"uint8": "uint8", "int8": "int8", "float64": "float64", "int64": "int64", "int32": "int32", "float32": "float32"}
 
 
 def empty(n, dtype: str):

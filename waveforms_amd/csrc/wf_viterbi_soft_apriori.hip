@@ -1,0 +1,274 @@
+// wf_viterbi_soft_apriori.hip — the max-log-MAP SOQPSK detector of wf_viterbi_soft.hip with a per-row prior on the input bit
+// and EXTRINSIC output (include/wfhip.h, wf_viterbi4_soft_apriori, states the definition): the inner half of iterative
+// detection and decoding.
+//
+//   π_k = scale * (double)prior[k];   inc'_k(b) = inc_k(b) + π_k for the branches whose input bit is 1 (one float64 addition)
+//   ã, b̃: the recursions of the plain detector over inc';   λᵉ_k from (ã_k + inc_k) + b̃_{k+1}: the CHANNEL increment.
+//
+// Signed zeros: a prior can make an increment negative or -0, but a normalised metric is o - min(o) >= +0 and is never -0
+// (x - x = +0 in round-to-nearest), and a sum with one operand that is not -0 is not -0 either.  So no value that reaches
+// an fmin is -0, equal values are bitwise equal, and fmin restates the definition's strict compare whatever the order of
+// its operands.  Rows and priors are finite, so there is no NaN.
+//
+// The four-launch structure, the scratch layout and the chunk proof are those of wf_viterbi_soft.hip (wf_viterbi_soft.h
+// holds what the two files share).  Every kernel here also needs the input bit of a branch, so all of them carry the
+// DIFF template argument.  The prior is read the way the rows are, by each lane along its own chunk, but 32 B at a time
+// into a register window (soft_prior_win): 4 B per row beside the row's 32 / 48 B.
+#include "wf_viterbi_soft.h"
+
+#include <cmath>
+
+struct soft_prior {
+    const float *p;
+    double scale;
+    int64_t n;          // rows of the burst = values at p
+    int vec;            // p is 16-byte aligned: windows are filled by two float4 loads
+};
+
+// A lane's window on the prior: the 8 consecutive values of the 32-byte group its row lies in, refilled when the row
+// leaves the group (either direction).  A lane walks its own chunk, so a scalar load per row would touch the lane's
+// line of the prior on EVERY row beside the row's own lines; the window touches it once per 8 rows.
+struct soft_prior_win {
+    float v[8];
+    int64_t base = -8;
+};
+
+__device__ __forceinline__ double soft_prior_at(const soft_prior &pr, soft_prior_win &w, int64_t k)
+{
+    const int64_t g = k & ~(int64_t)7;
+    if (g != w.base) {
+        w.base = g;
+        if (pr.vec && g + 8 <= pr.n) {
+            const float4 a = *reinterpret_cast<const float4 *>(pr.p + g), b = *reinterpret_cast<const float4 *>(pr.p + g + 4);
+            w.v[0] = a.x; w.v[1] = a.y; w.v[2] = a.z; w.v[3] = a.w;
+            w.v[4] = b.x; w.v[5] = b.y; w.v[6] = b.z; w.v[7] = b.w;
+        } else {        // the burst's last group, or an unaligned prior: value by value, never past row n - 1
+#pragma unroll
+            for (int j = 0; j < 8; ++j) w.v[j] = g + j < pr.n ? pr.p[g + j] : 0.0f;
+        }
+    }
+    const int j = (int)(k & 7);
+    float x = w.v[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) x = j == i ? w.v[i] : x;
+    return pr.scale * (double)x;
+}
+
+// inc' of the branch that enters end state e as the first (ia) / second (ib) listed one; start states as in soft_sums
+template <int COL, int DIFF>
+__device__ __forceinline__ void soft_ap_incs(const vit_comp &q, double pi, double ia[4], double ib[4])
+{
+    if (COL == 0) {
+        ia[0] = -q.i1; ia[1] = -q.r1; ia[2] = -q.b; ia[3] = -q.a;
+        ib[0] = q.a;   ib[1] = q.b;   ib[2] = q.r1; ib[3] = q.i1;
+    } else {
+        ia[0] = -q.i1; ia[1] = -q.a;  ia[2] = q.r1; ia[3] = q.b;
+        ib[0] = -q.b;  ib[1] = -q.r1; ib[2] = q.a;  ib[3] = q.i1;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (soft_inp<COL, DIFF>(e, 0)) ia[e] += pi;
+        if (soft_inp<COL, DIFF>(e, 1)) ib[e] += pi;
+    }
+}
+
+// ã_k -> ã_{k+1} over inc'
+template <int COL, int DIFF>
+__device__ __forceinline__ void soft_ap_fwd(double m[4], const vit_comp &q, double pi)
+{
+    double ia[4], ib[4], o[4];
+    soft_ap_incs<COL, DIFF>(q, pi, ia, ib);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int sa = COL == 0 ? (e & 1) : (e & 2), sb = COL == 0 ? (e & 1) + 2 : (e & 2) + 1;
+        o[e] = fmin(m[sa] + ia[e], m[sb] + ib[e]);
+    }
+    soft_normalise(o, m);
+}
+
+// b̃_{k+1} -> b̃_k over inc': start state s leaves to e0 / e1 as the sec-th listed branch into each
+template <int COL, int DIFF>
+__device__ __forceinline__ void soft_ap_bwd(double b[4], const vit_comp &q, double pi)
+{
+    double ia[4], ib[4], o[4];
+    soft_ap_incs<COL, DIFF>(q, pi, ia, ib);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int sec = COL == 0 ? s >> 1 : s & 1;
+        const int e0 = COL == 0 ? (s & 1) : (s & 2), e1 = COL == 0 ? (s & 1) + 2 : (s & 2) + 1;
+        o[s] = fmin((sec ? ib[e0] : ia[e0]) + b[e0], (sec ? ib[e1] : ia[e1]) + b[e1]);
+    }
+    soft_normalise(o, b);
+}
+
+template <bool PACKED, int DIFF>
+__device__ __forceinline__ void soft_ap_fwd_row(double m[4], const double *rows, const soft_prior &pr, soft_prior_win &w, int64_t k)
+{
+    const double pi = soft_prior_at(pr, w, k);
+    if (k & 1) soft_ap_fwd<1, DIFF>(m, vit_components<1, PACKED>(soft_row<PACKED>(rows, k)), pi);
+    else soft_ap_fwd<0, DIFF>(m, vit_components<0, PACKED>(soft_row<PACKED>(rows, k)), pi);
+}
+
+template <bool PACKED, int DIFF>
+__device__ __forceinline__ void soft_ap_bwd_row(double b[4], const double *rows, const soft_prior &pr, soft_prior_win &w, int64_t k)
+{
+    const double pi = soft_prior_at(pr, w, k);
+    if (k & 1) soft_ap_bwd<1, DIFF>(b, vit_components<1, PACKED>(soft_row<PACKED>(rows, k)), pi);
+    else soft_ap_bwd<0, DIFF>(b, vit_components<0, PACKED>(soft_row<PACKED>(rows, k)), pi);
+}
+
+// The chunk's own rows forward from m = ã_a: ã_k of every row stored (lane-interleaved), m left at ã_e.
+template <bool PACKED, int DIFF>
+__device__ __forceinline__ void soft_ap_fwd_chunk(const double *rows, const soft_prior &pr, soft_prior_win &w, int64_t a, int64_t e, int64_t c, int64_t nch,
+                                                  double *alpha, double m[4])
+{
+    for (int64_t k = a; k < e; ++k) {
+        soft_put4(alpha + 4 * ((k - a) * nch + c), m);
+        soft_ap_fwd_row<PACKED, DIFF>(m, rows, pr, w, k);
+    }
+}
+
+template <bool PACKED, int DIFF>
+__global__ __launch_bounds__(SOFT_THREADS) void soft_ap_bounds_kernel(const double *__restrict__ rows, soft_prior pr, int64_t n, int ch, int warmup,
+                                                                    int64_t nch, double *__restrict__ fedge, double *__restrict__ bedge,
+                                                                    double *__restrict__ alpha)
+{
+    if (blockIdx.x == 0 && threadIdx.x < VIT_HDR) {        // lists empty, nobody arrived (both directions)
+        reinterpret_cast<uint64_t *>(fedge + 8 * nch)[threadIdx.x] = 0;
+        reinterpret_cast<uint64_t *>(bedge + 8 * nch)[threadIdx.x] = 0;
+    }
+    const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
+    if (c >= nch) return;
+    const int64_t a = c * ch, e = a + ch < n ? a + ch : n;
+    soft_prior_win w;
+    double m[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t k = a - warmup > 0 ? a - warmup : 0; k < a; ++k) soft_ap_fwd_row<PACKED, DIFF>(m, rows, pr, w, k);
+    soft_put4(fedge + 8 * c, m);
+    soft_ap_fwd_chunk<PACKED, DIFF>(rows, pr, w, a, e, c, nch, alpha, m);
+    soft_put4(fedge + 8 * c + 4, m);
+
+    double b[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t k = (e + warmup < n ? e + warmup : n) - 1; k >= e; --k) soft_ap_bwd_row<PACKED, DIFF>(b, rows, pr, w, k);
+    const int64_t cm = nch - 1 - c;                        // mirrored record index
+    soft_put4(bedge + 8 * cm, b);
+    for (int64_t k = e - 1; k >= a; --k) soft_ap_bwd_row<PACKED, DIFF>(b, rows, pr, w, k);
+    soft_put4(bedge + 8 * cm + 4, b);
+}
+
+// soft_rerun of wf_viterbi_soft.hip over inc'
+template <bool PACKED, bool BWD, int DIFF>
+__device__ __forceinline__ bool soft_ap_rerun(const double *__restrict__ rows, const soft_prior &pr, int64_t n, int ch, int64_t nch,
+                                              double *__restrict__ edge, double *__restrict__ alpha, int64_t r)
+{
+    double *rec = edge + 8 * r;
+    double m[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        m[q] = __hip_atomic_load(rec - 4 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (r >= 1: record 0 is exact)
+        rec[q] = m[q];
+    }
+    const int64_t c = BWD ? nch - 1 - r : r;
+    const int64_t a = c * ch, e = a + ch < n ? a + ch : n;
+    soft_prior_win w;
+    if (BWD)
+        for (int64_t k = e - 1; k >= a; --k) soft_ap_bwd_row<PACKED, DIFF>(m, rows, pr, w, k);
+    else
+        soft_ap_fwd_chunk<PACKED, DIFF>(rows, pr, w, a, e, c, nch, alpha, m);
+    bool changed = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        changed |= __double_as_longlong(rec[4 + q]) != __double_as_longlong(m[q]);
+        rec[4 + q] = m[q];
+    }
+    return changed;
+}
+
+template <bool PACKED, bool BWD, int DIFF>
+__global__ __launch_bounds__(256) void soft_ap_fixup_kernel(const double *__restrict__ rows, soft_prior pr, int64_t n, int ch, double *__restrict__ edge,
+                                                            int64_t nch, double *__restrict__ alpha, unsigned long long *__restrict__ unmerged, int mode)
+{
+    if (!vit_fixup_verify(edge, nch, unmerged, mode)) return;
+    vit_fixup_rounds(edge, nch, unmerged, [&](int64_t r) { return soft_ap_rerun<PACKED, BWD, DIFF>(rows, pr, n, ch, nch, edge, alpha, r); });
+}
+
+template <bool PACKED, int DIFF>
+__global__ __launch_bounds__(SOFT_THREADS) void soft_ap_llr_kernel(const double *__restrict__ rows, soft_prior pr, int64_t n, int ch, int64_t nch,
+                                                                 const double *__restrict__ bedge, const double *__restrict__ alpha,
+                                                                 double *__restrict__ ext, uint8_t *__restrict__ bits)
+{
+    const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
+    if (c >= nch) return;
+    const int64_t a = c * ch, e = a + ch < n ? a + ch : n;
+    double b[4], m[4];
+    soft_prior_win w;
+    soft_get4(bedge + 8 * (nch - 1 - c), b);               // b̃_e, proven
+    for (int64_t k = e - 1; k >= a; --k) {
+        soft_get4(alpha + 4 * ((k - a) * nch + c), m);     // ã_k (of inc')
+        const double2 *z = soft_row<PACKED>(rows, k);
+        const double pi = soft_prior_at(pr, w, k);
+        double lam;
+        if (k & 1) {
+            const vit_comp q = vit_components<1, PACKED>(z);
+            lam = soft_llr<1, DIFF>(m, b, q);              // the channel's inc in section k
+            soft_ap_bwd<1, DIFF>(b, q, pi);
+        } else {
+            const vit_comp q = vit_components<0, PACKED>(z);
+            lam = soft_llr<0, DIFF>(m, b, q);
+            soft_ap_bwd<0, DIFF>(b, q, pi);
+        }
+        ext[k] = lam;
+        bits[k] = lam + pi < 0.0 ? 1 : 0;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+template <bool PACKED, int DIFF>
+static int soft_ap_run(wf_ctx *ctx, const double *rows, const soft_prior &pr, int64_t n, const soft_geom &g, double *ext, uint8_t *bits, hipStream_t s)
+{
+    double *fedge = ctx->d_vit_edge, *bedge = fedge + g.off_b, *alpha = fedge + g.off_alpha;
+    const unsigned grid = (unsigned)((g.nch + SOFT_THREADS - 1) / SOFT_THREADS);
+    hipLaunchKernelGGL((soft_ap_bounds_kernel<PACKED, DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, pr, n, g.ch, g.warmup, g.nch, fedge, bedge,
+                       alpha);
+    WF_LAUNCH_CHECK();
+    if (g.nch > 1) {
+        // repair, count only, or repair and count behind it: as wf_viterbi_soft.hip (soft_run)
+        const unsigned fgrid = (unsigned)wf_grid_for(g.nch - 1, 256, 1024);
+        const int passes = ctx->opt[WF_OPT_DET_REPAIR] == 0 && ctx->opt[WF_OPT_DET_FINAL_VERIFY] ? 2 : 1;
+        for (int pass = 0; pass < passes; ++pass) {
+            const int mode = pass == 0 && ctx->opt[WF_OPT_DET_REPAIR] == 0 ? 1 : 0;
+            hipLaunchKernelGGL((soft_ap_fixup_kernel<PACKED, false, DIFF>), dim3(fgrid), dim3(256), 0, s, rows, pr, n, g.ch, fedge, g.nch, alpha,
+                               ctx->d_vit_unmerged, mode);
+            WF_LAUNCH_CHECK();
+            hipLaunchKernelGGL((soft_ap_fixup_kernel<PACKED, true, DIFF>), dim3(fgrid), dim3(256), 0, s, rows, pr, n, g.ch, bedge, g.nch, alpha,
+                               ctx->d_vit_unmerged, mode);
+            WF_LAUNCH_CHECK();
+        }
+    }
+    hipLaunchKernelGGL((soft_ap_llr_kernel<PACKED, DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, pr, n, g.ch, g.nch, bedge, alpha, ext, bits);
+    WF_LAUNCH_CHECK();
+    return WF_OK;
+}
+
+extern "C" int wf_viterbi4_soft_apriori(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
+                                        const float *d_apriori, double apriori_scale, double *d_ext, uint8_t *d_bits, void *stream)
+{
+    WF_REQUIRE(ctx && d_rows && d_ext && d_bits, "wf_viterbi4_soft_apriori: NULL argument");
+    WF_REQUIRE(ncalls >= 1 && warmup >= 0, "wf_viterbi4_soft_apriori: bad argument");
+    WF_REQUIRE(row_bytes == 32 || row_bytes == 48, "wf_viterbi4_soft_apriori: row_bytes must be 32 (packed) or 48 (3 complex128)");
+    WF_REQUIRE(std::isfinite(apriori_scale), "wf_viterbi4_soft_apriori: apriori_scale must be finite");
+    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_ext) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(d_apriori) & 3) == 0,
+               "wf_viterbi4_soft_apriori: rows must be 16-byte, ext 8-byte and the prior 4-byte aligned");
+    if (!d_apriori)            // π = 0: the plain detector (bitwise: ã + (inc + 0) = ã + inc, since ã is never -0)
+        return wf_viterbi4_soft(ctx, d_rows, ncalls, row_bytes, differential, warmup, d_ext, d_bits, stream);
+    const soft_geom g = soft_geometry(ctx, ncalls, warmup);
+    WF_REQUIRE((g.nch + SOFT_THREADS - 1) / SOFT_THREADS < (1ll << 31), "wf_viterbi4_soft_apriori: burst too long for one launch");
+    WF_HIP(hipSetDevice(ctx->device));
+    const int rc = wf_ctx_reserve_vit(ctx, g.words);
+    if (rc) return rc;
+    hipStream_t s = wf_stream(stream);
+    const soft_prior pr{d_apriori, apriori_scale, ncalls, (reinterpret_cast<uintptr_t>(d_apriori) & 15) == 0 ? 1 : 0};
+    if (row_bytes == 32)
+        return differential ? soft_ap_run<true, 1>(ctx, d_rows, pr, ncalls, g, d_ext, d_bits, s) : soft_ap_run<true, 0>(ctx, d_rows, pr, ncalls, g, d_ext, d_bits, s);
+    return differential ? soft_ap_run<false, 1>(ctx, d_rows, pr, ncalls, g, d_ext, d_bits, s) : soft_ap_run<false, 0>(ctx, d_rows, pr, ncalls, g, d_ext, d_bits, s);
+}

@@ -211,6 +211,32 @@ def viterbi_soft_geometry(ncalls: int, warmup: int = 0, ctx=None) -> dict:
     return dict(zip(("chunk_calls", "lanes", "warmup", "scratch_bytes"), (int(v) for v in g)))
 
 
+def viterbi_soft_apriori(rows, apriori=None, apriori_scale: float = 1.0, differential: bool = True, warmup: int = 0,
+                         row_bytes: int = 48, ctx=None):
+    """``viterbi_soft`` with a per-row prior and extrinsic output (``wf_viterbi4_soft_apriori``; include/wfhip.h states
+    the definition) -> (ext f64[ncalls], bits u8[ncalls]) on device.  ``apriori``: a contiguous device float32 tensor of
+    ncalls values (row k's prior at [k]: transmitted bit j's at [j + 1]) or None (= ``viterbi_soft``, bitwise);
+    π = ``apriori_scale`` * apriori > 0 favours bit 0.  ``ext`` leaves the prior of its own bit out (it is what an outer
+    decoder is fed); ``bits`` are the decisions of ext + π.  Geometry: ``viterbi_soft_geometry``."""
+    if row_bytes not in (32, 48):
+        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    nbytes = rows.numel() * rows.element_size()
+    if nbytes % row_bytes:
+        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
+    ncalls = nbytes // row_bytes
+    if apriori is not None:
+        if apriori.dtype != _hip.torch().float32 or not apriori.is_contiguous() or apriori.numel() != ncalls:
+            raise ValueError(f"apriori must be {ncalls} contiguous float32 values (one per row)")
+    ext = _hip.empty(max(ncalls, 1), "float64")
+    bits = _hip.empty(ncalls + 16, "uint8")
+    _hip.check(_hip.lib().wf_viterbi4_soft_apriori(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(row_bytes),
+                                                   int(bool(differential)), int(warmup), _hip.ptr(apriori), float(apriori_scale),
+                                                   _hip.ptr(ext), _hip.ptr(bits), _hip.stream()))
+    return ext[:ncalls], bits[:ncalls]
+
+
 def cpm_soft(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None):
     """Max-log-MAP soft output of the generic CPM trellis (``wf_cpm_soft``; include/wfhip.h states the definition) -> (llr
     f64[n lgM], bits u8[n lgM]) on device, one fresh burst.  ``spec``: a full-phase design (NC = p, at most 64 states:
@@ -342,6 +368,57 @@ def ldpc_decode(code, d_llr, scale: float = 1.0, alpha: float = 0.75, max_iter: 
                                          _hip.ptr(info), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ref_info),
                                          _hip.ptr(counts) if ref_info is not None else None, _hip.stream()))
     return {"info_bits": info, "iters": iters, "post": post, "counts": counts if ref_info is not None else None}
+
+
+def ldpc_decode_ext(code, d_llr, state, ext, ext_stride: int | None = None, scale: float = 1.0, alpha: float = 0.75, max_iter: int = 5,
+                    ext_clip: float = float("inf"), ext_sat: float = 50.0, info_bits=None, iters=None, want_post: bool = False,
+                    post=None) -> dict:
+    """One outer pass of the decoder in iterative detection and decoding (``wf_ldpc_decode_ext``; include/wfhip.h states the
+    definition).  ``d_llr``: contiguous float64, ncw x n_tx, as for ``ldpc_decode``.  ``state``: device u8[ncw], in / out
+    (0 open, 1 frozen: such a codeword is not touched).  ``ext``: a device float32 tensor (or a view into a prior buffer)
+    that receives codeword b's extrinsic values at [b ext_stride + t] (``ext_stride`` default n_tx).  ``info_bits``
+    (u8 ncw x k) and ``iters`` (int32 ncw, INCREASED) are updated in place for the open codewords; fresh zeros when None.
+    Returns {"info_bits", "iters", "post" (float32 ncw x n, only open codewords written, or None), "state", "ext"}."""
+    torch = _hip.torch()
+    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
+        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
+    ncw = d_llr.numel() // code.n_tx
+    stride = code.n_tx if ext_stride is None else int(ext_stride)
+    if stride < code.n_tx:
+        raise ValueError(f"ext_stride {stride} is below n_tx = {code.n_tx}")
+    if state.dtype != torch.uint8 or state.numel() != ncw or not state.is_contiguous():
+        raise ValueError("state must hold ncw contiguous bytes")
+    if ext.dtype != torch.float32 or not ext.is_contiguous() or ext.numel() < (ncw - 1) * stride + code.n_tx:
+        raise ValueError("ext must be contiguous float32 with room for (ncw - 1) ext_stride + n_tx values")
+    if info_bits is None:
+        info_bits = _hip.zeros((ncw, code.k), "uint8")
+    elif info_bits.dtype != torch.uint8 or info_bits.numel() != ncw * code.k or not info_bits.is_contiguous():
+        raise ValueError("info_bits must hold ncw x k contiguous bytes")
+    if iters is None:
+        iters = _hip.zeros(ncw, "int32")
+    elif iters.dtype != torch.int32 or iters.numel() != ncw or not iters.is_contiguous():
+        raise ValueError("iters must hold ncw contiguous int32")
+    if post is None and want_post:
+        post = torch.zeros((ncw, code.n), dtype=torch.float32, device="cuda")
+    _hip.check(_hip.lib().wf_ldpc_decode_ext(_hip.ctx(), code.handle(), _hip.ptr(d_llr), ncw, float(scale), float(alpha), int(max_iter),
+                                             _hip.ptr(state), _hip.ptr(info_bits), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ext), stride,
+                                             float(ext_clip), float(ext_sat), _hip.stream()))
+    return {"info_bits": info_bits, "iters": iters, "post": post, "state": state, "ext": ext}
+
+
+def ldpc_count(code, info_bits, ref_info, state, iters, counts=None):
+    """``counts`` (device int64[4], fresh zeros if None) += information bit errors, codewords with one, codewords still
+    open, iterations summed (``wf_ldpc_count``): the counts of ``ldpc_decode`` after the last ``ldpc_decode_ext`` pass."""
+    ncw = int(state.numel())
+    if info_bits.numel() != ncw * code.k or ref_info.numel() != ncw * code.k or iters.numel() != ncw:
+        raise ValueError("info_bits and ref_info must hold ncw x k bits, iters ncw values")
+    if not (info_bits.is_contiguous() and ref_info.is_contiguous() and state.is_contiguous() and iters.is_contiguous()):
+        raise ValueError("arguments must be contiguous")
+    if counts is None:
+        counts = _hip.zeros(4, "int64")
+    _hip.check(_hip.lib().wf_ldpc_count(_hip.ctx(), code.handle(), _hip.ptr(info_bits), _hip.ptr(ref_info), _hip.ptr(state), _hip.ptr(iters),
+                                        ncw, _hip.ptr(counts), _hip.stream()))
+    return counts
 
 
 def ldpc_decode_geometry(code, ncw: int) -> dict:

@@ -1,5 +1,6 @@
 """Coded SOQPSK-TG chain on the GPU: info bits -> LDPC encode -> SOQPSK-TG modulate + AWGN + PT / PAM bank -> max-log-MAP
-soft detector (``viterbi_soft``) -> LDPC decode -> error counts.
+soft detector (``viterbi_soft``) -> LDPC decode -> error counts (``CodedSOQPSKLink``), and the same chain closed into a
+loop: soft detector with a prior <-> LDPC decoder with extrinsic output (``IterativeSOQPSKLink``).
 
 Every stage is an existing device entry point (waveforms_amd.device); nothing leaves the GPU inside a block.  The fused
 ``SOQPSKLink`` is not used and not changed.
@@ -120,3 +121,88 @@ class CodedSOQPSKLink:
     def uncoded_result(self) -> tuple[int, int]:
         """(bit errors of λ < 0 against the coded bits, coded bits compared) over the same blocks."""
         return int(self.uncoded.cpu()[1]), self.blocks * self.nbits
+
+
+class IterativeSOQPSKLink(CodedSOQPSKLink):
+    """``CodedSOQPSKLink`` with iterative detection and decoding: same block layout, PN23 information bits, noise keys,
+    Eb/N0 convention and result tuples; the front end runs once per block, then ``outer`` passes of
+
+        soft detector with the burst's prior buffer (``viterbi_soft_apriori``, apriori_scale = ``damping``)
+        -> ``ldpc_decode_ext`` (``inner`` iterations from a cold start) writing the next prior at offset +1, stride n_tx
+
+    and one ``ldpc_count``.  A codeword whose syndrome is zero is FROZEN: its prior becomes ±``ext_sat`` by its decisions and
+    later passes leave it alone (without this a converged codeword would hand back zero extrinsic and be decoded from
+    scratch on the next pass, and the loop oscillates).  Row 0 and the tail rows keep prior 0.  Max-log-MAP and
+    normalized min-sum are both scale-invariant, so the loop needs no noise-variance scale (``llr_scale`` stays 1).
+
+    ``ext_sat`` / ``ext_clip`` are in the detector's metric units, which grow linearly with ``sps`` (the matched filters
+    sum sps + 1 unit-magnitude taps): the defaults are ext_sat = 6.25 sps (50 at sps 8, where mean |λ| is about 11 at
+    4.5 dB) and no clip.  ``outer`` is fixed per block and nothing synchronises with the host inside one; every pass is
+    queued even when every codeword is already frozen (the decoder's workgroups then retire at once, the detector
+    still runs).  ``per_pass=True`` also accumulates the four counts after every pass (``pass_results``)."""
+
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
+                 damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False) -> None:
+        if outer < 1 or inner < 1:
+            raise ValueError("outer and inner must be at least 1")
+        if not (math.isfinite(damping) and damping > 0.0):
+            raise ValueError("damping must be finite and positive")
+        self.outer, self.inner, self.damping = int(outer), int(inner), float(damping)
+        self.ext_sat = 6.25 * int(sps) if ext_sat is None else float(ext_sat)
+        self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
+        if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
+            raise ValueError("ext_sat must be finite and positive, ext_clip positive")
+        super().__init__(code, ncw, sps, detector, alpha, max_iter=inner)
+        self.per_pass = bool(per_pass)
+        self.pass_counts = _hip.zeros((self.outer, 4), "int64")
+        self.prior = self.state = self.iters = self.decided = None
+
+    # ---------------------------------------------------------------- stages
+    def begin(self, nrows: int) -> None:
+        """Fresh loop state of one block: prior 0 on every row, every codeword open, no iterations."""
+        if self.prior is None or self.prior.numel() != nrows:
+            self.prior = _hip.zeros(nrows, "float32")
+            self.state = _hip.zeros(self.ncw, "uint8")
+            self.iters = _hip.zeros(self.ncw, "int32")
+            self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
+        else:
+            for t in (self.prior, self.state, self.iters, self.decided):
+                t.zero_()
+
+    def detect(self, rows, first: bool = False):
+        """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
+        of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
+        ext, bits = dev.viterbi_soft_apriori(rows, None if first else self.prior, self.damping)
+        return ext[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
+
+    def decode(self, ext) -> None:
+        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place."""
+        dev.ldpc_decode_ext(self.code, ext, self.state, self.prior[1:1 + self.nbits], self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
+                            max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
+
+    # ---------------------------------------------------------------- blocks
+    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
+        info = self.info_bits(stream_id)
+        tx = dev.ldpc_encode(self.code, info)
+        rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
+        self.begin(int(rows.shape[0]))
+        for o in range(self.outer):
+            ext, hard = self.detect(rows, first=o == 0)
+            if o == 0:
+                dev.count_errors(syms, syms, hard, tx.reshape(-1), self.nbits, self.uncoded)
+            self.decode(ext)
+            if self.per_pass:
+                dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.pass_counts[o])
+        dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.counts)
+        self.blocks += 1
+
+    def reset_counts(self) -> None:
+        super().reset_counts()
+        self.pass_counts.zero_()
+
+    def pass_results(self) -> list[tuple[int, int, int, float]]:
+        """Per outer pass (``per_pass=True``): (information bit errors, codeword errors, codewords still open, mean
+        iterations so far) over the blocks run - synchronises."""
+        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
+        ncw = self.blocks * self.ncw
+        return [(int(be), int(fe), int(nc), (int(its) / ncw if ncw else 0.0)) for be, fe, nc, its in self.pass_counts.cpu().tolist()]
