@@ -576,6 +576,39 @@ int wf_cpm_soft(wf_ctx *ctx, const wf_cpm_detector_config *det, const double *d_
  * [3] scratch bytes.  Host only, no device work. */
 int wf_cpm_soft_geometry(wf_ctx *ctx, const wf_cpm_detector_config *det, int64_t ncalls, int warmup, int64_t *h_geom);
 
+/* wf_cpm_soft with a per-bit prior and EXTRINSIC per-bit output: the inner detector of iterative detection and decoding for
+ * ARTM and PCM/FM.  Everything of wf_cpm_soft holds unchanged (full-phase spec with NC = p and at most 64 states, rows,
+ * first_call, "transmitted bit j pairs with λ[j]", warm-up, chunk-parallel proof and cascading repair in both directions,
+ * WF_OPT_CPM_SOFT_CHUNK_CALLS, WF_OPT_DET_REPAIR / WF_OPT_DET_FINAL_VERIFY, counters, scratch: wf_cpm_soft_geometry
+ * describes this call too) with, in float64 and in exactly this order of operations, lgM = log2 M, bit i of u MSB first:
+ *   π_{k,i}     = apriori_scale * (double)d_apriori[lgM k + i]                  (0 when d_apriori is NULL)
+ *   Π_k(u)      = the sum of π_{k,i} over the bits i of u that are 1            (M = 4, u = 3: ONE addition π_{k,0} + π_{k,1})
+ *   inc'_k(s,u) = inc_k(s,u) + Π_k(u) when u != 0, inc_k(s,u) when u = 0        (one float64 addition)
+ *   ã, b̃: the recursions of wf_cpm_soft with inc' in place of inc
+ *   x_{k,i}(s,u) = inc_k(s,u) + π_{k,j} when u has another bit j != i and that bit is 1, inc_k(s,u) otherwise
+ *                  (M = 2: always inc_k(s,u); M = 4: bit 0 takes π_{k,1} on u = 1, 3 and bit 1 takes π_{k,0} on u = 2, 3)
+ *   λᵉ_{k,i}    = min_{(s,u): bit_i(u) = 1} ((ã_k(s) + x_{k,i}(s,u)) + b̃_{k+1}(e(s,u))) - min_{(s,u): bit_i(u) = 0} (the same)
+ *   d_ext[lgM k + i]  = λᵉ_{k,i},    d_bits[lgM k + i] = (λᵉ_{k,i} + π_{k,i}) < 0
+ * A bit's own prior is never added into its own output (so none is subtracted); the prior of the other bit of the same
+ * quaternary symbol is: the output is extrinsic per BIT, which is what a binary decoder needs.  For M = 2 this is the rule
+ * of wf_viterbi4_soft_apriori.  π > 0 favours bit 0, as λ does.  d_apriori: lgM * ncalls float32, 4-byte aligned, indexed as
+ * d_llr is (a decoder writes the next prior of codewords sent back to back at offset 0, stride n_tx).  With d_apriori NULL
+ * the result is bitwise wf_cpm_soft's (and so it is for a prior of zeros of either sign: see below).
+ * Why the order in which a machine takes the minima does not matter although inc' may be negative or -0: a normalised metric
+ * ã, b̃ is x - min x over the states, which is >= +0 and never -0 (x - x = +0 in round-to-nearest; every state of the
+ * full-phase trellis has exactly M entering and M leaving branches, so min x is finite and no state is ever +inf).  A sum with
+ * an operand that is not -0 is not -0.  Every operand of a min is such a sum: ã_k(s) + inc', inc' + b̃_{k+1}(e), (ã_k(s) + x)
+ * + b̃_{k+1}(e).  So no operand of a min is -0, equal operands are bitwise equal, and the result does not depend on the order.
+ * An implementation may carry +inf for the lanes of a wave that hold no state: +inf plus a finite increment is +inf, never
+ * the smaller operand and never NaN.  A prior of -0 gives π = -0 or +0 by the sign of apriori_scale, Π(3) = ±0, and
+ * inc + (±0) differs from inc at most in the sign of a zero, which the next sum with ã or b̃ removes: zeros of either sign
+ * are exactly "no prior".  Rows must be finite and every π_{k,i} and Π_k(3) finite in float64 (finite float32 priors and a
+ * scale below 1e269 in magnitude guarantee it).  apriori_scale not finite, a prior that is not 4-byte aligned, or any
+ * argument wf_cpm_soft refuses: WF_ERR_VALUE before the context is touched. */
+int wf_cpm_soft_apriori(wf_ctx *ctx, const wf_cpm_detector_config *det, const double *d_rot_cs, const double *d_rows_ri,
+                        int64_t ncalls, int64_t first_call, int warmup, const float *d_apriori, double apriori_scale,
+                        double *d_ext, uint8_t *d_bits, void *stream);
+
 /* ---- LDPC codes: systematic encoder and layered normalized min-sum decoder ------------------------------------------
  * A code is an opaque handle made once on the host.  H has n variables and m checks, numbered in LAYER order: check c's
  * edges are h_edge_var[h_check_ptr[c] .. h_check_ptr[c+1]) (table order), layer l holds checks h_layer_ptr[l] ..

@@ -1,8 +1,11 @@
-"""Coded BER / FER curve of the LDPC-coded SOQPSK-TG chain (waveforms_amd/encoding/coded.py) and the decoder's speed; prints
-ONE JSON line.
+"""Coded BER / FER curve of the LDPC-coded SOQPSK-TG, ARTM multi-h or PCM/FM chain (waveforms_amd/encoding/coded.py) and the
+decoder's speed; prints ONE JSON line.
 
-    python tools/coded_ber.py [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N] [--detector PT] [--steps 5]
-                              [--outer N --inner M --damping D]
+    python tools/coded_ber.py [--waveform soqpsk|multih|pcmfm] [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N]
+                              [--detector PT] [--steps 5] [--outer N --inner M --damping D]
+
+``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
+CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
 
 Eb/N0 is per information bit.  Per point: coded BER and FER, codewords not converged, mean iterations, and the soft
 detector's uncoded BER (λ < 0 against the coded bits) on the same channel bits.  Each block is one burst of
@@ -28,6 +31,7 @@ sys.path.insert(0, str(ROOT))
 
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--waveform", default="soqpsk", choices=["soqpsk", "multih", "pcmfm"])
     ap.add_argument("--code", default="demo", choices=["demo", "demo16k"])
     ap.add_argument("--ebn0", type=float, nargs="+", default=[4.0, 5.0, 6.0, 7.0, 8.0])
     ap.add_argument("--codewords", type=int, default=20000)
@@ -45,20 +49,22 @@ def main() -> None:
 
     from waveforms_amd import device as dev
     from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CodedSOQPSKLink, IterativeSOQPSKLink
+    from waveforms_amd.encoding.coded import CodedCPMLink, CodedSOQPSKLink, IterativeCPMLink, IterativeSOQPSKLink
 
     torch.cuda.set_device(0)
     code = ldpc.demo_code(128 if args.code == "demo" else 1024)
     per = args.block_codewords or max(1, int(1e7) // code.n_tx)
     per = min(per, args.codewords)
-    link = CodedSOQPSKLink(code, per, detector=args.detector, alpha=args.alpha, max_iter=args.max_iter)
-    out = {"tool": "coded_ber", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
+    cpm = args.waveform != "soqpsk"
+    which = {"waveform": args.waveform} if cpm else {"detector": args.detector}
+    link = (CodedCPMLink if cpm else CodedSOQPSKLink)(code, per, alpha=args.alpha, max_iter=args.max_iter, **which)
+    out = {"tool": "coded_ber", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, **which,
            "alpha": args.alpha, "max_iter": args.max_iter, "block_codewords": per,
            "geometry": dev.ldpc_decode_geometry(code, per), "points": []}
     idd = None
     if args.outer > 0:
-        idd = IterativeSOQPSKLink(code, per, detector=args.detector, alpha=args.alpha, outer=args.outer, inner=args.inner,
-                                  damping=args.damping, per_pass=True)
+        idd = (IterativeCPMLink if cpm else IterativeSOQPSKLink)(code, per, alpha=args.alpha, outer=args.outer, inner=args.inner,
+                                                                damping=args.damping, per_pass=True, **which)
         out["iterative"] = {"outer": idd.outer, "inner": idd.inner, "damping": idd.damping, "ext_sat": idd.ext_sat,
                             "ext_clip": None if np.isinf(idd.ext_clip) else idd.ext_clip}
     for e in args.ebn0:

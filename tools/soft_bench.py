@@ -2,6 +2,8 @@
 
     python tools/soft_bench.py [--calls 1e7] [--ebn0 10] [--detector PT] [--steps 20] [--warmup-steps 3] [--soft-warmup 0]
     python tools/soft_bench.py --waveform multih|pcmfm [...]     the CPM soft detector (wf_cpm_soft): main_cpm
+    python tools/soft_bench.py --waveform multih|pcmfm --apriori [--apriori-sigma 8]
+                                                                 ... and one a-priori pass (wf_cpm_soft_apriori) beside it
 
 The rows are what SOQPSKLink(calls, fuse=15) leaves in its workspace (detector-packed, 32 B per call: layout()["off_mf"],
 layout()["row_bytes"]); the link's own length-2 detector runs on them once, for its bit errors; the transmitted bits are
@@ -63,6 +65,9 @@ def main() -> None:
     ap.add_argument("--opt", action="append", default=[], help="wf_ctx option key=value, e.g. soft_chunk_calls=64")
     ap.add_argument("--waveform", default="soqpsk", choices=["soqpsk", "multih", "pcmfm"],
                     help="soqpsk: wf_viterbi4_soft (above); multih / pcmfm: wf_cpm_soft on one CPMLink block's rows (main_cpm)")
+    ap.add_argument("--apriori", action="store_true",
+                    help="CPM waveforms: also time wf_cpm_soft_apriori on the same rows (random prior, and a NULL prior)")
+    ap.add_argument("--apriori-sigma", type=float, default=8.0, help="standard deviation of the random prior (clipped to +-50)")
     args = ap.parse_args()
     if args.waveform != "soqpsk":
         return main_cpm(args)
@@ -172,6 +177,7 @@ def main_cpm(args) -> None:
         ev_ms = e0.elapsed_time(e1) / args.steps
         repaired = dev.viterbi_repaired(reset=True, ctx=ctx)
         unproven = dev.viterbi_unmerged(reset=True, ctx=ctx)
+        ap = apriori_passes(args, dev, _hip, torch, rows, fspec, d_rot, ctx, ev_ms) if args.apriori else None
     finally:
         _hip.free_ctx(ctx)
 
@@ -195,7 +201,36 @@ def main_cpm(args) -> None:
         "soft_bit_errors": int(err.sum()), "hard_full_phase_bit_errors": int((hard[lo:hi] != tx[lo:hi]).sum()),
         "hard_reduced_bit_errors": int(hbe), "compared_bits": int(hi - lo),
         "llr_scale_c_sigma2": None if scale is None else round(scale, 4),
+        **({"apriori": ap} if ap is not None else {}),
     }))
+
+
+def apriori_passes(args, dev, _hip, torch, rows, fspec, d_rot, ctx, plain_ms) -> dict:
+    """--apriori: wf_cpm_soft_apriori on the same rows, same context and same step counts as the plain pass timed just
+    before: once with a random float32 prior (normal, --apriori-sigma, clipped to +-50; scale 0.7) and once with a NULL
+    prior (the plain kernels through the new entry point).  Time per pass by device events, chunk repairs per pass."""
+    n = int(rows.shape[0]) * fspec.bits_per_symbol
+    g = torch.Generator(device="cuda")
+    g.manual_seed(1)
+    prior = (args.apriori_sigma * torch.randn(n, generator=g, device="cuda", dtype=torch.float32)).clamp_(-50.0, 50.0)
+    out = {"prior_sigma": args.apriori_sigma, "scale": 0.7}
+    for name, p in (("random_prior", prior), ("null_prior", None)):
+        for _ in range(args.warmup_steps):
+            dev.cpm_soft_apriori(rows, fspec, p, 0.7, 0, args.soft_warmup, ctx=ctx, d_rot=d_rot)
+        torch.cuda.synchronize()
+        dev.viterbi_repaired(reset=True, ctx=ctx)
+        dev.viterbi_unmerged(reset=True, ctx=ctx)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.steps):
+            dev.cpm_soft_apriori(rows, fspec, p, 0.7, 0, args.soft_warmup, ctx=ctx, d_rot=d_rot)
+        e1.record()
+        torch.cuda.synchronize()
+        ms = e0.elapsed_time(e1) / args.steps
+        out[name] = {"ms_per_block_events": round(ms, 4), "ratio_to_plain": round(ms / plain_ms, 4),
+                     "repairs_per_block": dev.viterbi_repaired(reset=True, ctx=ctx) / args.steps,
+                     "unproven": dev.viterbi_unmerged(reset=True, ctx=ctx)}
+    return out
 
 
 if __name__ == "__main__":

@@ -97,6 +97,7 @@ SIGNATURES = {
     "wf_cpm_count_errors": (c_int, [_P, _P, _P, c_int, c_int64, _P, _P]),
     "wf_cpm_soft": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, _P, _P, _P]),
     "wf_cpm_soft_geometry": (c_int, [_P, _P, c_int64, c_int, POINTER(c_int64)]),
+    "wf_cpm_soft_apriori": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, _P, c_double, _P, _P, _P]),
     "wf_ldpc_code_create": (c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, _P, ctypes.c_int32, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                     _P, _P, POINTER(c_void_p)]),
     "wf_ldpc_code_free": (c_int, [_P]),

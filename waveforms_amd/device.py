@@ -263,6 +263,37 @@ def cpm_soft(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=N
     return llr[:n * lg], bits[:n * lg]
 
 
+def cpm_soft_apriori(rows, spec, apriori=None, apriori_scale: float = 1.0, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None):
+    """``cpm_soft`` with a per-bit prior and extrinsic per-bit output (``wf_cpm_soft_apriori``; include/wfhip.h states the
+    definition) -> (ext f64[n lgM], bits u8[n lgM]) on device.  ``apriori``: a contiguous device float32 tensor of n lgM
+    values indexed as the output is (bit i, MSB first, of call k at [lgM k + i]) or None (= ``cpm_soft``, bitwise);
+    π = ``apriori_scale`` * apriori > 0 favours bit 0.  ``ext`` leaves the prior of its own bit out and keeps the one of the
+    other bit of the same quaternary symbol (it is what a binary outer decoder is fed); ``bits`` are the decisions of
+    ext + π.  Geometry: ``cpm_soft_geometry``."""
+    from .viterbi.cpm import rotation_table
+
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    per = 2 * spec.nfilt
+    if rows.numel() % per:
+        raise ValueError(f"{rows.numel()} doubles of rows are not a whole number of {spec.nfilt}-filter rows")
+    n, lg = rows.numel() // per, spec.bits_per_symbol
+    if not math.isfinite(float(apriori_scale)):
+        raise ValueError("apriori_scale must be finite")
+    if apriori is not None:
+        if apriori.dtype != _hip.torch().float32 or not apriori.is_contiguous() or apriori.numel() != n * lg:
+            raise ValueError(f"apriori must be {n * lg} contiguous float32 values ({lg} per call)")
+    if d_rot is None:
+        d_rot = _hip.to_device(rotation_table(spec))
+    ext = _hip.empty(max(n * lg, 1), "float64")
+    bits = _hip.empty(n * lg + 16, "uint8")
+    cfg = spec.c_config()
+    _hip.check(_hip.lib().wf_cpm_soft_apriori(ctx if ctx is not None else _hip.ctx(), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
+                                              int(first_call), int(warmup), _hip.ptr(apriori), float(apriori_scale), _hip.ptr(ext),
+                                              _hip.ptr(bits), _hip.stream()))
+    return ext[:n * lg], bits[:n * lg]
+
+
 def cpm_soft_geometry(spec, ncalls: int, warmup: int = 0, ctx=None) -> dict:
     """What ``cpm_soft`` launches for a burst of ``ncalls`` calls on this context (``wf_cpm_soft_geometry``)."""
     g = (ctypes.c_int64 * 4)()

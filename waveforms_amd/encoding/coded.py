@@ -2,8 +2,11 @@
 soft detector (``viterbi_soft``) -> LDPC decode -> error counts (``CodedSOQPSKLink``), and the same chain closed into a
 loop: soft detector with a prior <-> LDPC decoder with extrinsic output (``IterativeSOQPSKLink``).
 
+``CodedCPMLink`` / ``IterativeCPMLink`` are the same two chains for the waveforms of the generic CPM trellis, ARTM multi-h and
+PCM/FM: mapper -> modulate -> AWGN -> matched-filter rows -> ``cpm_soft`` / ``cpm_soft_apriori`` on the full-phase trellis.
+
 Every stage is an existing device entry point (waveforms_amd.device); nothing leaves the GPU inside a block.  The fused
-``SOQPSKLink`` is not used and not changed.
+``SOQPSKLink`` and ``CPMLink`` are not used and not changed.
 """
 from __future__ import annotations
 
@@ -206,3 +209,211 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
         ncw = self.blocks * self.ncw
         return [(int(be), int(fe), int(nc), (int(its) / ncw if ncw else 0.0)) for be, fe, nc, its in self.pass_counts.cpu().tolist()]
+
+
+PAD_SYMS = 8                              # CPM chains: zero symbols after the burst's last codeword
+CPM_WAVEFORMS = {"multih": 1, "pcmfm": 2}  # -> symbol_map kind (the reference's natural-binary mappers)
+
+
+class CodedCPMLink:
+    """``CodedSOQPSKLink`` for ARTM multi-h (``waveform="multih"``) and PCM/FM (``"pcmfm"``): one block = ``ncw`` codewords of
+    ``code`` sent back to back as ONE burst from call 0, plus ``PAD_SYMS`` zero symbols.
+
+    coded bits -> ``symbol_map`` -> ``cpm_modulate`` with the waveform's modulation indices -> ``awgn`` (with the e^{-jπ/4}
+    derotation of the CPM chains) -> ``cpm_mf_rows`` with the waveform's matched-filter templates -> ``cpm_soft`` on the
+    full-phase trellis (``ARTM_64``: 64 states, ``PCMFM_20``: 20 states) -> ``ldpc_decode``.  Transmitted bit j pairs with
+    λ[j] (include/wfhip.h, wf_cpm_soft).
+
+    Eb/N0 is per INFORMATION bit: σ = ``viterbi.cpm.sigma_for_ebn0(ebn0_db + 10 log10(k / n_tx), sps, bits_per_symbol)``.
+    Information bits, noise keys and result tuples are ``CodedSOQPSKLink``'s: PN23 by ``stream_id``, counter-based AWGN keyed
+    by (``seed``, ``stream_id``); ``ebn0_db=None`` is noiseless.  ARTM carries two bits per symbol, so a code whose ``n_tx`` is
+    odd is refused for it (a codeword would end inside a symbol).  The burst is detected from a free start, before any symbol
+    has been sent: the λ of its FIRST symbol is weak and can have the wrong sign even without noise, which costs the burst's
+    first codeword at most lgM channel errors (one decoder iteration when there is no noise)."""
+
+    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50) -> None:
+        from ..viterbi import cpm
+
+        if waveform not in CPM_WAVEFORMS:
+            raise ValueError(f"unknown waveform {waveform!r}")
+        if ncw < 1:
+            raise ValueError("ncw must be at least 1")
+        if waveform == "multih":
+            from ..cpm.multih import freq_pulse_multih_irig
+
+            pulse, spec = freq_pulse_multih_irig(int(sps)), cpm.ARTM_64
+            if code.n_tx % 2:
+                raise ValueError(f"ARTM sends two bits per symbol: a code with an odd n_tx = {code.n_tx} is refused")
+        else:
+            from ..cpm.pcmfm import freq_pulse_pcmfm
+
+            pulse, spec = freq_pulse_pcmfm(int(sps)), cpm.PCMFM_20
+        self.code, self.ncw, self.sps, self.waveform, self.spec = code, int(ncw), int(sps), waveform, spec
+        self.alpha, self.max_iter = float(alpha), int(max_iter)
+        self.llr_scale = 1.0
+        lg = spec.bits_per_symbol
+        self.nbits = self.ncw * code.n_tx
+        self.nsym = self.nbits // lg + PAD_SYMS
+        pulse = np.asarray(pulse, dtype=np.float64)
+        geo = cpm.filter_geometry(pulse.size, self.sps, spec, self.nsym)
+        self.start0, self.ncalls = int(geo["start0"]), int(geo["ncalls"])
+        if self.ncalls * lg < self.nbits:
+            raise RuntimeError(f"{self.ncalls} detector calls for {self.nbits} coded bits")
+        self._d_h = _hip.to_device(spec.mod_index)
+        self._d_pulse = _hip.to_device(pulse)
+        self._d_templates = _hip.to_device(cpm.matched_filter_templates(pulse, self.sps, cpm.full_phase(spec)))
+        self._d_rot = _hip.to_device(cpm.rotation_table(spec))
+        self._pad = _hip.zeros(PAD_SYMS * lg, "uint8")
+        self._mask = generate_mask(23)
+        self.counts = _hip.zeros(4, "int64")
+        self.uncoded = _hip.zeros(2, "int64")
+        self.blocks = 0
+        code.handle()
+
+    def sigma(self, ebn0_db: float | None) -> float:
+        from ..viterbi.cpm import sigma_for_ebn0 as cpm_sigma
+
+        if ebn0_db is None:
+            return 0.0
+        return cpm_sigma(float(ebn0_db) + 10.0 * math.log10(self.code.k / self.code.n_tx), self.sps, self.spec.bits_per_symbol)
+
+    # ---------------------------------------------------------------- stages
+    def info_bits(self, stream_id: int = 0):
+        n = self.ncw * self.code.k
+        bits, _ = dev.lfsr_bits(23, self._mask, (1 << 23) - 1, n, skip=int(stream_id) * n)
+        return bits
+
+    def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst float64[ncalls, nfilt, 2], its symbols)."""
+        torch = _hip.torch()
+        bits = torch.cat((tx.reshape(-1), self._pad))
+        syms = dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
+        sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
+        received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
+        rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
+        return rows, syms
+
+    def soft(self, rows):
+        """Rows -> (λ of the coded bits, ncw x n_tx view; hard decisions of the same λ)."""
+        llr, bits = dev.cpm_soft(rows, self.spec, 0, 0, d_rot=self._d_rot)
+        return llr[:self.nbits].view(self.ncw, self.code.n_tx), bits[:self.nbits]
+
+    def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """(λ ncw x n_tx, information bits ncw x k) of one block, on the device."""
+        info = self.info_bits(stream_id)
+        tx = dev.ldpc_encode(self.code, info)
+        rows, _ = self.front_end(tx, ebn0_db, seed, stream_id)
+        llr, _ = self.soft(rows)
+        return llr.contiguous(), info.view(self.ncw, self.code.k)
+
+    def count_uncoded(self, hard, tx) -> None:
+        flat = tx.reshape(-1)
+        dev.count_errors(hard, flat, hard, flat, self.nbits, self.uncoded)     # (bits in both pairs: [1] is what is read)
+
+    # ---------------------------------------------------------------- blocks
+    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
+        """Queue one block on the current stream; the counts accumulate on the device."""
+        info = self.info_bits(stream_id)
+        tx = dev.ldpc_encode(self.code, info)
+        rows, _syms = self.front_end(tx, ebn0_db, seed, stream_id)
+        llr, hard = self.soft(rows)
+        self.count_uncoded(hard, tx)
+        dev.ldpc_decode(self.code, llr, scale=self.llr_scale, alpha=self.alpha, max_iter=self.max_iter, ref_info=info,
+                        counts=self.counts)
+        self.blocks += 1
+
+    reset_counts = CodedSOQPSKLink.reset_counts
+    result = CodedSOQPSKLink.result
+    uncoded_result = CodedSOQPSKLink.uncoded_result
+
+
+class IterativeCPMLink(CodedCPMLink):
+    """``CodedCPMLink`` with iterative detection and decoding, the loop of ``IterativeSOQPSKLink`` on the generic CPM trellis:
+    the front end runs once per block, then ``outer`` passes of
+
+        ``cpm_soft_apriori`` with the burst's prior buffer (apriori_scale = ``damping``)
+        -> ``ldpc_decode_ext`` (``inner`` iterations from a cold start) writing the next prior at offset 0, stride n_tx
+
+    and one ``ldpc_count``.  The detector's output is extrinsic per BIT: for ARTM the prior of the other bit of the same
+    quaternary symbol stays in, a bit's own never does.  Frozen codewords, ``per_pass``, ``ext_clip`` and the result tuples
+    are ``IterativeSOQPSKLink``'s; the tail calls keep prior 0.  The phase state makes a CPM modulator a recursive inner code,
+    which is where iterating pays most.
+
+    ``ext_sat`` is in the detector's metric units, which grow linearly with ``sps``.  Default, both waveforms: 6.25 sps (50
+    at sps 8), the SOQPSK loop's value.  It was chosen from the mean |λ| of one plain pass at sps 8 — about 4 for ARTM at
+    7 dB and about 16 for PCM/FM at 3 dB information Eb/N0, against 11 for SOQPSK-TG at 4.5 dB — as the value that is at
+    least three times every one of them (a frozen codeword's bits must outweigh the channel in the neighbouring sections)
+    and with which the CPU restatement of the loop reaches no frame error in 40 at both operating points
+    (tests/test_cpm_idd.py).
+
+    ``prior_warmup``: the detector's warm-up, in calls, on the passes that carry a prior (0: the library's 64).  The warm-up
+    never changes a result, only how many chunks the proof sends to the repair; a saturated prior pins the inputs, paths
+    from different phase states then stop merging, and with 64 calls EVERY chunk of a frozen block failed its proof in both
+    directions (16 232 repairs on 8 117 chunks, a pass at 1.8 - 1.9 times the plain one).  With 512 calls none did (1.04 -
+    1.09 times; INTEGRATION.md has the measurement)."""
+
+    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, outer: int = 8, inner: int = 5,
+                 damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False,
+                 prior_warmup: int = 512) -> None:
+        if outer < 1 or inner < 1:
+            raise ValueError("outer and inner must be at least 1")
+        if not (math.isfinite(damping) and damping > 0.0):
+            raise ValueError("damping must be finite and positive")
+        if prior_warmup < 0:
+            raise ValueError("prior_warmup must not be negative")
+        self.outer, self.inner, self.damping, self.prior_warmup = int(outer), int(inner), float(damping), int(prior_warmup)
+        self.ext_sat = 6.25 * int(sps) if ext_sat is None else float(ext_sat)
+        self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
+        if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
+            raise ValueError("ext_sat must be finite and positive, ext_clip positive")
+        super().__init__(code, ncw, waveform, sps, alpha, max_iter=inner)
+        self.per_pass = bool(per_pass)
+        self.pass_counts = _hip.zeros((self.outer, 4), "int64")
+        self.prior = self.state = self.iters = self.decided = None
+
+    # ---------------------------------------------------------------- stages
+    def begin(self, ncalls: int | None = None) -> None:
+        """Fresh loop state of one block: prior 0 on every bit of every call, every codeword open, no iterations."""
+        n = (self.ncalls if ncalls is None else int(ncalls)) * self.spec.bits_per_symbol
+        if self.prior is None or self.prior.numel() != n:
+            self.prior = _hip.zeros(n, "float32")
+            self.state = _hip.zeros(self.ncw, "uint8")
+            self.iters = _hip.zeros(self.ncw, "int32")
+            self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
+        else:
+            for t in (self.prior, self.state, self.iters, self.decided):
+                t.zero_()
+
+    def detect(self, rows, first: bool = False):
+        """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
+        of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
+        ext, bits = dev.cpm_soft_apriori(rows, self.spec, None if first else self.prior, self.damping, 0, 0 if first else self.prior_warmup,
+                                         d_rot=self._d_rot)
+        return ext[:self.nbits].view(self.ncw, self.code.n_tx), bits[:self.nbits]
+
+    def decode(self, ext) -> None:
+        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place."""
+        dev.ldpc_decode_ext(self.code, ext, self.state, self.prior[:self.nbits], self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
+                            max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
+
+    # ---------------------------------------------------------------- blocks
+    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
+        info = self.info_bits(stream_id)
+        tx = dev.ldpc_encode(self.code, info)
+        rows, _syms = self.front_end(tx, ebn0_db, seed, stream_id)
+        self.begin(int(rows.shape[0]))
+        for o in range(self.outer):
+            ext, hard = self.detect(rows, first=o == 0)
+            if o == 0:
+                self.count_uncoded(hard, tx)
+            self.decode(ext)
+            if self.per_pass:
+                dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.pass_counts[o])
+        dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.counts)
+        self.blocks += 1
+
+    def reset_counts(self) -> None:
+        super().reset_counts()
+        self.pass_counts.zero_()
+
+    pass_results = IterativeSOQPSKLink.pass_results

@@ -216,7 +216,7 @@ class CPMTrellisDetector:
             raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
         return out[:n]
 
-    def detect_soft_device(self, rows, first_call: int = 0, warmup: int = 0):
+    def detect_soft_device(self, rows, first_call: int = 0, warmup: int = 0, apriori=None, apriori_scale: float = 1.0):
         """Soft output, max-log-MAP (``wf_cpm_soft``; include/wfhip.h states the definition), over ``full_phase(self.spec)``:
         the trellis of this detector's matched filters with every phase state in it, so ``CPMTrellisDetector(ARTM_16).
         detect_soft`` gives the 64-state (ARTM_64) soft output of the same rows, and PCMFM_10 the 20-state one (PCMFM_20).
@@ -224,7 +224,9 @@ class CPMTrellisDetector:
         index ``first_call`` -> (llr f64[n lgM], bits u8[n lgM]) on device.  λ > 0 favours bit 0 and bits = λ < 0; bit i
         (MSB first) of symbol j pairs with λ[lgM j + i], symbol j being the one whose filter column opens at call j.  λ is in
         metric units, no scale baked in.  The hard carry (``self.i``, the device state) is left untouched.  ValueError if the
-        full-phase trellis has more than 64 states (ARTM_256)."""
+        full-phase trellis has more than 64 states (ARTM_256).  With ``apriori`` (device float32[n lgM], indexed as the output;
+        π = ``apriori_scale`` * apriori) the pass is ``wf_cpm_soft_apriori``: the output is the EXTRINSIC λᵉ and bits are the
+        decisions of λᵉ + π; None takes exactly the plain path."""
         from waveforms_amd import _hip, device as dev
 
         spec = full_phase(self.spec)
@@ -236,18 +238,24 @@ class CPMTrellisDetector:
             self._ctx = _hip.new_ctx()
             self._d_rot = _hip.to_device(rotation_table(self.spec))
             self._d_state = _hip.zeros(_hip.WF_CPM_STATE_BYTES // 8, "int64")
-        out = dev.cpm_soft(rows, spec, first_call, warmup, ctx=self._ctx, d_rot=self._d_rot)
+        if apriori is None:
+            out = dev.cpm_soft(rows, spec, first_call, warmup, ctx=self._ctx, d_rot=self._d_rot)
+        else:
+            out = dev.cpm_soft_apriori(rows, spec, apriori, apriori_scale, first_call, warmup, ctx=self._ctx, d_rot=self._d_rot)
         unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
         if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
             raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
         return out
 
-    def detect_soft(self, rows, first_call: int = 0, warmup: int = 0):
-        """Host in / host out soft form: complex128[n][M^Lp] -> (llr f64[n lgM], bits u8[n lgM]); see ``detect_soft_device``."""
+    def detect_soft(self, rows, first_call: int = 0, warmup: int = 0, apriori=None, apriori_scale: float = 1.0):
+        """Host in / host out soft form: complex128[n][M^Lp] -> (llr f64[n lgM], bits u8[n lgM]); see ``detect_soft_device``
+        (``apriori``: a host array of n lgM values, taken as float32)."""
         from waveforms_amd import _hip
 
         rows = np.ascontiguousarray(rows, dtype=np.complex128).reshape(-1, self.spec.nfilt)
-        llr, bits = self.detect_soft_device(_hip.to_device(rows), first_call, warmup)
+        if apriori is not None:
+            apriori = _hip.to_device(np.ascontiguousarray(apriori, dtype=np.float32).reshape(-1))
+        llr, bits = self.detect_soft_device(_hip.to_device(rows), first_call, warmup, apriori, apriori_scale)
         return _hip.to_host(llr), _hip.to_host(bits)
 
     def detect(self, rows, warmup: int = 0) -> np.ndarray:
