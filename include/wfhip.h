@@ -673,6 +673,51 @@ int wf_ldpc_decode_ext(wf_ctx *ctx, const wf_ldpc_code *code, const double *d_ll
 int wf_ldpc_count(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_t *d_info_bits, const uint8_t *d_ref_info,
                   const uint8_t *d_state, const int32_t *d_iters, int64_t ncw, int64_t *d_counts, void *stream);
 
+/* ---- Framed coded links: attached sync marker, randomiser, soft frame search ------------------------------------------
+ * (The reference has no coding or framing layer; these entry points are defined here.)
+ * Frame: L marker bits (1 <= L <= 64) followed by the n_tx transmitted bits of one codeword, bit t exclusive-ored with
+ * pn[t], t counted from the start of the codeword; period P = L + n_tx.  The marker is the low L bits of `marker`, sent MSB
+ * first: marker bit i = (marker >> (L - 1 - i)) & 1.  It is not randomised.  d_pn: n_tx bytes (0 / 1) in device memory,
+ * NULL = no randomiser; the package's own sequence is pn[0..7] = 1, pn[n+8] = pn[n] ^ pn[n+3] ^ pn[n+5] ^ pn[n+7]
+ * (waveforms_amd/encoding/framing.py), the ABI is not tied to it.
+ * wf_frame_build (transmit side): d_out[b P + i] = marker bit i (i < L), d_out[b P + L + t] = (d_tx[b n_tx + t] ^ pn[t]) & 1,
+ * for b < ncw: ncw x P bytes. */
+int wf_frame_build(wf_ctx *ctx, const uint8_t *d_tx, int64_t ncw, int32_t n_tx, uint64_t marker, int32_t L, const uint8_t *d_pn,
+                   uint8_t *d_out, void *stream);
+/* Soft search of the frame offset and polarity of a burst.  d_llr: nllr float64 λ, λ > 0 favouring bit 0, finite.  With
+ * s_i = +1 where marker bit i is 0 and -1 where it is 1 (s_i λ flips the sign bit: no product is rounded), in float64, every
+ * sum started from +0 and taken in exactly this order:
+ *   C(t) = sum_{i = 0 .. L-1} s_i λ[t + i],  A(t) = sum_{i = 0 .. L-1} |λ[t + i]|          (i increasing)
+ *   M+(t) = C(t) - A(t),   M-(t) = (-C(t)) - A(t)
+ *   F = (nllr - L) div P frames;  slice j holds the frames f = 32 j .. min(32 j + 32, F) - 1
+ *   S±(j, p) = sum of M±(p + f P) over the frames of slice j (f increasing);  G±(p) = sum_j S±(j, p) (j increasing), p < P
+ * M+ <= 0 is minus twice the summed |λ| of the positions that disagree with the marker; M- the same for the inverted stream.
+ * The lock is the maximum of the 2P values; ties go to + before -, then to the smallest p.  d_lock (32 bytes, 8-byte
+ * aligned) receives { int64 p̂, int64 σ (+1, or -1 for the inverted stream), double best value, double the maximum of the
+ * other 2P - 1 values } (best - other is the lock's margin); d_folded, if not NULL, the 2P values, G+(0 .. P-1) then
+ * G-(0 .. P-1).  Nothing is returned to the host.  The slice sums ((ceil(F / 32) + 1) x 2P doubles) live in the context's
+ * detector scratch, as the detectors' chunk records do: the call follows a detector on the same stream and context.
+ * L outside 1 .. 64, P <= L or P > 2^23, F < 1, a NULL ctx / d_llr / d_lock, a pointer not 8-byte aligned: WF_ERR_VALUE
+ * before the context is touched. */
+int wf_frame_search(wf_ctx *ctx, const double *d_llr, int64_t nllr, uint64_t marker, int32_t L, int64_t P, void *d_lock,
+                    double *d_folded, void *stream);
+/* Deframe: the decoder's input from a located burst.  The lock record is READ FROM DEVICE MEMORY (no host round trip); with
+ * r_t = 1 - 2 pn[t] and P = L + n_tx:
+ *   d_out[b n_tx + t] = σ r_t λ[p̂ + b P + L + t]   for b < ncw, t < n_tx   (sign flips; a position at or beyond nllr gives +0)
+ * d_out: ncw x n_tx float64, what wf_ldpc_decode / wf_ldpc_decode_ext read.  Alignment with a detector is by pointer offset,
+ * for the search, the gather and the scatter alike: d_llr = llr + 1 and d_prior = prior + 1 behind wf_viterbi4_soft, offset 0
+ * behind wf_cpm_soft. */
+int wf_frame_gather(wf_ctx *ctx, const double *d_llr, int64_t nllr, const void *d_lock, int32_t L, int32_t n_tx, const uint8_t *d_pn,
+                    int64_t ncw, double *d_out, void *stream);
+/* Reframe: the decoder's extrinsic output (wf_ldpc_decode_ext's d_ext, float32) into a detector's prior buffer:
+ *   d_prior[p̂ + b P + L + t] = σ r_t d_ext[b ext_stride + t]     for b < ncw, t < n_tx
+ *   d_prior[p̂ + b P + i]     = σ s_i marker_prior                for i < L; marker_prior = 0 leaves these positions alone
+ * A position at or beyond nprior is skipped; everything else in the buffer is left as it was.  The marker is a run of known
+ * bits: a saturated marker_prior hands it to the detector on every later pass.  ext_stride < n_tx, marker_prior not finite,
+ * L outside 1 .. 64, a NULL pointer (d_pn may be NULL): WF_ERR_VALUE before the context is touched. */
+int wf_frame_scatter(wf_ctx *ctx, const float *d_ext, int64_t ext_stride, const void *d_lock, uint64_t marker, int32_t L, int32_t n_tx,
+                     const uint8_t *d_pn, int64_t ncw, float marker_prior, float *d_prior, int64_t nprior, void *stream);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

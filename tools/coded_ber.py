@@ -3,6 +3,7 @@ decoder's speed; prints ONE JSON line.
 
     python tools/coded_ber.py [--waveform soqpsk|multih|pcmfm] [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N]
                               [--detector PT] [--steps 5] [--outer N --inner M --damping D]
+                              [--framed [--lead-bits J] [--marker-prior X]]
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -17,6 +18,13 @@ With ``--outer N`` (> 0) every point also runs the iterative chain (IterativeSOQ
 iterations, prior scaled by ``--damping``) on the SAME blocks, next to the one-pass curve: BER / FER and open codewords after
 every pass, total inner iterations, and the time per block split into the detector passes and the decoder passes (each pass
 bracketed by device events; the first detector pass is the plain detector).
+
+With ``--framed`` every point also runs the FRAMED link (waveforms_amd/encoding/framing.py: the default marker and the
+randomiser in front of every codeword, ``--lead-bits`` pseudo-random bits in front of the burst) on the same number of
+codewords per burst, next to the unframed curve and at the same information Eb/N0 (which now pays for the marker): the same
+counts, the wrong locks, the last lock record, and the times of ``frame_search``, ``frame_gather`` and ``frame_scatter`` on
+the burst (device events).  With ``--outer`` the framed iterative link runs too, the marker rows carrying
+``--marker-prior`` (default: ext_sat; 0 = no marker prior).
 """
 import argparse
 import json
@@ -43,6 +51,9 @@ def main() -> None:
     ap.add_argument("--outer", type=int, default=0, help="outer passes of the iterative chain (0: one-pass curve only)")
     ap.add_argument("--inner", type=int, default=5, help="decoder iterations per outer pass")
     ap.add_argument("--damping", type=float, default=0.7, help="scale of the prior fed back to the detector")
+    ap.add_argument("--framed", action="store_true", help="also run the framed link (sync marker + randomiser + soft frame search)")
+    ap.add_argument("--lead-bits", type=int, default=0, help="pseudo-random bits in front of the framed burst (0 .. period - 1)")
+    ap.add_argument("--marker-prior", type=float, default=None, help="prior of the marker rows in the framed loop (default ext_sat)")
     args = ap.parse_args()
 
     import torch
@@ -67,6 +78,19 @@ def main() -> None:
                                                                 damping=args.damping, per_pass=True, **which)
         out["iterative"] = {"outer": idd.outer, "inner": idd.inner, "damping": idd.damping, "ext_sat": idd.ext_sat,
                             "ext_clip": None if np.isinf(idd.ext_clip) else idd.ext_clip}
+    flink = fidd = None
+    if args.framed:
+        from waveforms_amd.encoding.framing import Framing
+
+        fr = Framing(code)
+        flink = (CodedCPMLink if cpm else CodedSOQPSKLink)(code, per, alpha=args.alpha, max_iter=args.max_iter, framing=fr,
+                                                         lead_bits=args.lead_bits, **which)
+        out["framed"] = {"marker": hex(fr.marker), "marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits}
+        if args.outer > 0:
+            fidd = (IterativeCPMLink if cpm else IterativeSOQPSKLink)(code, per, alpha=args.alpha, outer=args.outer, inner=args.inner,
+                                                                     damping=args.damping, per_pass=True, framing=fr,
+                                                                     lead_bits=args.lead_bits, marker_prior=args.marker_prior, **which)
+            out["framed"]["marker_prior"] = fidd.marker_prior
     for e in args.ebn0:
         link.reset_counts()
         b = 0
@@ -125,6 +149,47 @@ def main() -> None:
                 "ms_per_block": {"detector_passes": [round(v, 4) for v in det_ms], "decoder_passes": [round(v, 4) for v in dec_ms],
                                  "detector_total": round(float(det_ms.sum()), 4), "decoder_total": round(float(dec_ms.sum()), 4)},
             }
+        fr_point = None
+        if flink is not None:
+            flink.reset_counts()
+            for blk in range(b):
+                flink.run_block(e, seed=1, stream_id=blk)
+            fbe, ffe, fnc, fm, fmean = flink.result()
+            fue, fum = flink.uncoded_result()
+            blocks, wrong, lock = flink.sync_result()
+            # the three framing kernels on one burst's λ, each bracketed by device events
+            rows, _ = flink.front_end(dev.ldpc_encode(code, flink.info_bits(b)), e, 1, b)
+            lam = (dev.cpm_soft(rows, flink.spec, 0, 0, d_rot=flink._d_rot)[0] if cpm else dev.viterbi_soft(rows, True)[0][1:])
+            prior = torch.zeros(lam.numel(), dtype=torch.float32, device="cuda")
+            ext = torch.zeros((per, code.n_tx), dtype=torch.float32, device="cuda")
+            fev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            fms = np.zeros(3)
+            for s in range(args.steps + 1):
+                fev[0].record()
+                fr.search(lam, flink.lock)
+                fev[1].record()
+                fr.gather(lam, flink.lock, per)
+                fev[2].record()
+                fr.scatter(ext, flink.lock, prior, 50.0)
+                fev[3].record()
+                torch.cuda.synchronize()
+                if s:                                                     # (the first round warms up)
+                    fms += [fev[i].elapsed_time(fev[i + 1]) for i in range(3)]
+            fms /= max(args.steps, 1)
+            fr_point = {"ebn0_channel_db": round(e + 10 * np.log10(code.k / fr.period), 3), "coded_ber": fbe / fm, "fer": ffe / ncw,
+                        "info_bit_errors": fbe, "codeword_errors": ffe, "not_converged": fnc, "mean_iters": round(fmean, 3),
+                        "uncoded_ber": fue / fum, "blocks": blocks, "wrong_locks": wrong, "last_lock": lock, "burst_llrs": int(lam.numel()),
+                        "ms": {"frame_search": round(fms[0], 4), "frame_gather": round(fms[1], 4), "frame_scatter": round(fms[2], 4)}}
+            if fidd is not None:
+                fidd.reset_counts()
+                for blk in range(b):
+                    fidd.run_block(e, seed=1, stream_id=blk)
+                ibe, ife, inc, im, imean = fidd.result()
+                fr_point["iterative"] = {
+                    "coded_ber": ibe / im, "fer": ife / ncw, "info_bit_errors": ibe, "codeword_errors": ife, "open": inc,
+                    "total_inner_iters_mean": round(imean, 3), "wrong_locks": fidd.sync_result()[1],
+                    "per_pass": [{"info_bit_errors": p[0], "codeword_errors": p[1], "open": p[2], "iters_mean": round(p[3], 3)}
+                                 for p in fidd.pass_results()]}
         out["points"].append({
             "ebn0_info_db": e, "ebn0_channel_db": round(e + 10 * np.log10(code.k / code.n_tx), 3), "codewords": ncw,
             "coded_ber": be / m, "fer": fe / ncw, "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
@@ -133,6 +198,7 @@ def main() -> None:
                              "decode": round(ms[3], 4)},
             "decode_info_gbps": round(per * code.k / (ms[3] * 1e-3) / 1e9, 3) if ms[3] > 0 else None,
             **({"iterative": it_point} if it_point is not None else {}),
+            **({"framed": fr_point} if fr_point is not None else {}),
         })
     print(json.dumps(out))
 

@@ -107,6 +107,10 @@ SIGNATURES = {
     "wf_ldpc_decode_ext": (c_int, [_P, _P, _P, c_int64, c_double, ctypes.c_float, c_int, _P, _P, _P, _P, _P, c_int64, ctypes.c_float,
                            ctypes.c_float, _P]),
     "wf_ldpc_count": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, _P, _P]),
+    "wf_frame_build": (c_int, [_P, _P, c_int64, ctypes.c_int32, c_uint64, ctypes.c_int32, _P, _P, _P]),
+    "wf_frame_search": (c_int, [_P, _P, c_int64, c_uint64, ctypes.c_int32, c_int64, _P, _P, _P]),
+    "wf_frame_gather": (c_int, [_P, _P, c_int64, _P, ctypes.c_int32, ctypes.c_int32, _P, c_int64, _P, _P]),
+    "wf_frame_scatter": (c_int, [_P, _P, c_int64, _P, c_uint64, ctypes.c_int32, ctypes.c_int32, _P, c_int64, ctypes.c_float, _P, c_int64, _P]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

@@ -457,3 +457,79 @@ def ldpc_decode_geometry(code, ncw: int) -> dict:
     g = (ctypes.c_int64 * 5)()
     _hip.check(_hip.lib().wf_ldpc_decode_geometry(_hip.ctx(), code.handle(), int(ncw), g))
     return dict(zip(("state_in_scratch", "codewords_per_workgroup", "workgroups", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
+
+
+def _frame_pn(pn, n_tx: int):
+    torch = _hip.torch()
+    if pn is not None and (pn.dtype != torch.uint8 or pn.numel() != n_tx or not pn.is_contiguous()):
+        raise ValueError(f"pn must hold n_tx = {n_tx} contiguous bytes")
+    return pn
+
+
+def _frame_lock(lock):
+    torch = _hip.torch()
+    if lock.dtype != torch.int64 or lock.numel() != 4 or not lock.is_contiguous():
+        raise ValueError("lock must be the contiguous int64[4] record frame_search writes")
+    return lock
+
+
+def frame_build(tx, n_tx: int, marker: int, marker_bits: int = 64, pn=None):
+    """Transmit side of a framed link (``wf_frame_build``): device coded bits (ncw x n_tx, u8) -> ncw frames of
+    ``marker_bits`` marker bits (MSB first) + the codeword exclusive-ored with ``pn`` (device u8[n_tx] or None), u8
+    [ncw, marker_bits + n_tx]."""
+    if not tx.is_contiguous() or tx.numel() % n_tx or tx.numel() == 0:
+        raise ValueError(f"coded bits must be a contiguous whole number of n_tx = {n_tx} bits")
+    ncw = tx.numel() // n_tx
+    out = _hip.empty((ncw, int(marker_bits) + n_tx), "uint8")
+    _hip.check(_hip.lib().wf_frame_build(_hip.ctx(), _hip.ptr(tx), ncw, int(n_tx), int(marker) & (2 ** 64 - 1), int(marker_bits),
+                                         _hip.ptr(_frame_pn(pn, n_tx)), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def frame_search(llr, marker: int, marker_bits: int, period: int, lock=None, want_folded: bool = False):
+    """Soft frame search (``wf_frame_search``; include/wfhip.h states the definition) over a burst's λ (contiguous device
+    float64; offset the view to align with the detector).  Returns (lock, folded): ``lock`` the device int64[4] record
+    { p̂, σ = ±1, best value and best of the others as float64 bit patterns: ``lock[2:].view(torch.float64)`` }, ``folded``
+    float64[2, period] (G+ then G-) or None.  Nothing comes back to the host."""
+    torch = _hip.torch()
+    if llr.dtype != torch.float64 or not llr.is_contiguous():
+        raise ValueError("λ must be contiguous float64")
+    lock = _hip.empty(4, "int64") if lock is None else _frame_lock(lock)
+    folded = _hip.empty((2, int(period)), "float64") if want_folded and period > 0 else None
+    _hip.check(_hip.lib().wf_frame_search(_hip.ctx(), _hip.ptr(llr), int(llr.numel()), int(marker) & (2 ** 64 - 1), int(marker_bits), int(period),
+                                          _hip.ptr(lock), _hip.ptr(folded), _hip.stream()))
+    return lock, folded
+
+
+def frame_gather(llr, lock, marker_bits: int, n_tx: int, ncw: int, pn=None, out=None):
+    """Deframe (``wf_frame_gather``): the ncw x n_tx float64 decoder input of the burst ``llr`` located by ``lock`` (read on
+    the device), derandomised by ``pn`` and with the lock's polarity; positions beyond the burst give +0."""
+    torch = _hip.torch()
+    if llr.dtype != torch.float64 or not llr.is_contiguous() or llr.numel() == 0:
+        raise ValueError("λ must be contiguous float64")
+    if out is None:
+        out = _hip.empty((int(ncw), int(n_tx)), "float64")
+    elif out.dtype != torch.float64 or out.numel() != int(ncw) * int(n_tx) or not out.is_contiguous():
+        raise ValueError("out must hold ncw x n_tx contiguous float64")
+    _hip.check(_hip.lib().wf_frame_gather(_hip.ctx(), _hip.ptr(llr), int(llr.numel()), _hip.ptr(_frame_lock(lock)), int(marker_bits), int(n_tx),
+                                          _hip.ptr(_frame_pn(pn, n_tx)), int(ncw), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def frame_scatter(ext, lock, marker: int, marker_bits: int, n_tx: int, prior, pn=None, marker_prior: float = 0.0,
+                  ext_stride: int | None = None):
+    """Reframe (``wf_frame_scatter``): the decoder's extrinsic values ``ext`` (device float32, codeword b at [b ext_stride + t],
+    ``ext_stride`` default n_tx) into the burst's prior buffer ``prior`` (device float32 view, offset as the search's λ was)
+    at the lock's position, randomised by ``pn`` and with the lock's polarity; the marker positions get ±``marker_prior``
+    (0: left alone).  In place; returns ``prior``."""
+    torch = _hip.torch()
+    stride = int(n_tx) if ext_stride is None else int(ext_stride)
+    if ext.dtype != torch.float32 or not ext.is_contiguous() or ext.numel() == 0 or stride < n_tx:
+        raise ValueError("ext must be contiguous float32 and ext_stride at least n_tx")
+    ncw = (ext.numel() - int(n_tx)) // stride + 1
+    if prior.dtype != torch.float32 or not prior.is_contiguous() or prior.numel() == 0:
+        raise ValueError("prior must be contiguous float32")
+    _hip.check(_hip.lib().wf_frame_scatter(_hip.ctx(), _hip.ptr(ext), stride, _hip.ptr(_frame_lock(lock)), int(marker) & (2 ** 64 - 1),
+                                           int(marker_bits), int(n_tx), _hip.ptr(_frame_pn(pn, n_tx)), ncw, float(marker_prior), _hip.ptr(prior),
+                                           int(prior.numel()), _hip.stream()))
+    return prior

@@ -7,6 +7,12 @@ PCM/FM: mapper -> modulate -> AWGN -> matched-filter rows -> ``cpm_soft`` / ``cp
 
 Every stage is an existing device entry point (waveforms_amd.device); nothing leaves the GPU inside a block.  The fused
 ``SOQPSKLink`` and ``CPMLink`` are not used and not changed.
+
+All four classes take ``framing`` (a :class:`waveforms_amd.encoding.framing.Framing`) and ``lead_bits``: the burst is then
+``lead_bits`` pseudo-random bits, ``ncw`` frames (sync marker + randomised codeword) and the pad, and the receiver finds the
+codewords itself: ``frame_search`` over the whole burst's λ, ``frame_gather`` into the decoder's input and, in the loops,
+``frame_scatter`` of the decoder's extrinsic output (and the marker as a known-bits prior) back into the detector's prior
+buffer (``_Framed``).  With ``framing=None`` every class does exactly what it did without the keyword.
 """
 from __future__ import annotations
 
@@ -26,7 +32,68 @@ TIMING_OFFSET = {"PT": -1, "PAM": 0}      # SOQPSK-TG (examples/soqpsk_detection
 PAD_BITS = 16                             # tail after the burst's last codeword: every coded bit gets its λ
 
 
-class CodedSOQPSKLink:
+class _Framed:
+    """What a framed link adds to a coded link (``framing=None``: nothing).  ``nch`` is the number of channel bits in front
+    of the pad: ``lead_bits + ncw period`` (``ncw n_tx`` unframed).  The receiver side never reads ``lead_bits``: it is used
+    only to count, on the device, the blocks whose lock differs from it."""
+
+    def _frame_init(self, framing, lead_bits: int, bits_per_symbol: int = 1) -> None:
+        self.framing, self.lead_bits = framing, int(lead_bits)
+        self.nch, self._fill = self.nbits, None
+        if framing is None:
+            if self.lead_bits:
+                raise ValueError("lead_bits needs a framing")
+            return
+        if framing.n_tx != self.code.n_tx:
+            raise ValueError(f"the framing is for n_tx = {framing.n_tx}, the code has {self.code.n_tx}")
+        if not 0 <= self.lead_bits < framing.period:
+            raise ValueError(f"lead_bits = {lead_bits} outside 0 .. {framing.period - 1}")
+        self.nch = self.lead_bits + self.ncw * framing.period
+        fill = -self.nch % int(bits_per_symbol)                  # whole symbols: zero bits at the END of the burst
+        self._fill = _hip.zeros(fill, "uint8") if fill else None
+        self.lock = _hip.zeros(4, "int64")
+        self.sync = _hip.zeros(2, "int64")                       # blocks searched, wrong locks
+        self._true_lock = _hip.to_device(np.array([self.lead_bits, 1], dtype=np.int64))
+        self._llr_in = _hip.empty((self.ncw, self.code.n_tx), "float64")
+
+    def _rate_db(self) -> float:
+        """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""
+        return 10.0 * math.log10(self.code.k / (self.code.n_tx if self.framing is None else self.framing.period))
+
+    def channel_bits(self, tx, stream_id: int = 0):
+        """Coded bits (device ncw x n_tx) -> the burst's bits in front of the pad: the coded bits themselves, or lead bits
+        (the PN23 bits that follow the block's information bits) + ``ncw`` frames (+ a zero bit to whole symbols)."""
+        if self.framing is None:
+            return tx.reshape(-1)
+        parts = [self.framing.build(tx).reshape(-1)]
+        if self.lead_bits:
+            n = self.ncw * self.code.k
+            parts.insert(0, dev.lfsr_bits(23, self._mask, (1 << 23) - 1, self.lead_bits, skip=(int(stream_id) + 1) * n)[0])
+        if self._fill is not None:
+            parts.append(self._fill)
+        return _hip.torch().cat(parts) if len(parts) > 1 else parts[0]
+
+    def deframe(self, llr, search: bool = True):
+        """The whole burst's λ (aligned: λ[j] is channel bit j) -> the decoder's ncw x n_tx input.  ``search`` locks first
+        (once per block: the loops keep the lock of their first pass) and counts a lock that is not (lead_bits, +)."""
+        if search:
+            self.framing.search(llr, self.lock)
+            self.sync[0] += 1
+            self.sync[1] += (self.lock[:2] != self._true_lock).any()
+        return self.framing.gather(llr, self.lock, self.ncw, out=self._llr_in)
+
+    def sync_result(self) -> tuple[int, int, tuple[int, int, float, float]]:
+        """(blocks searched, wrong locks, the last lock record (p̂, σ, best value, best of the others)) - synchronises."""
+        if self.framing is None:
+            raise RuntimeError("sync_result needs a framing")
+        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
+        blocks, wrong = (int(v) for v in self.sync.cpu().tolist())
+        rec = self.lock.cpu().numpy()
+        best, other = (float(v) for v in rec[2:].view(np.float64))
+        return blocks, wrong, (int(rec[0]), int(rec[1]), best, other)
+
+
+class CodedSOQPSKLink(_Framed):
     """One block = ``ncw`` codewords of ``code`` sent back to back as ONE SOQPSK-TG burst (plus ``PAD_BITS`` zero bits).
 
     Eb/N0 is per INFORMATION bit: the channel's σ is ``sigma_for_ebn0(ebn0_db + 10 log10(k / n_tx), sps)``, i.e. the
@@ -36,7 +103,8 @@ class CodedSOQPSKLink:
     bit b ncw k.  The noise is the library's counter-based AWGN keyed by (``seed``, ``stream_id``).  Transmitted bit j
     is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
 
-    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50) -> None:
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
+                 lead_bits: int = 0) -> None:
         if detector not in TIMING_OFFSET:
             raise ValueError(f"unknown detector {detector!r}")
         if ncw < 1:
@@ -45,7 +113,8 @@ class CodedSOQPSKLink:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
         self.llr_scale = 1.0                    # (normalized min-sum does not depend on it)
         self.nbits = self.ncw * code.n_tx
-        self.nsym = self.nbits + PAD_BITS
+        self._frame_init(framing, lead_bits)
+        self.nsym = self.nch + PAD_BITS
         pulse = freq_pulse_soqpsk_tg(self.sps)
         taps = (pt_matched_filter_taps if detector == "PT" else pam_matched_filter_taps)(pulse, 0.25, self.sps)
         self._d_h = _hip.to_device(np.array([0.25]))
@@ -62,7 +131,7 @@ class CodedSOQPSKLink:
     def sigma(self, ebn0_db: float | None) -> float:
         if ebn0_db is None:
             return 0.0
-        return sigma_for_ebn0(float(ebn0_db) + 10.0 * math.log10(self.code.k / self.code.n_tx), self.sps)
+        return sigma_for_ebn0(float(ebn0_db) + self._rate_db(), self.sps)
 
     # ---------------------------------------------------------------- stages
     def info_bits(self, stream_id: int = 0):
@@ -73,12 +142,12 @@ class CodedSOQPSKLink:
     def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
         """Coded bits (device ncw x n_tx) -> matched-filter rows of the burst."""
         torch = _hip.torch()
-        bits = torch.cat((tx.reshape(-1), self._pad))
+        bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
         syms, _ = dev.fsm_encode(*self._tables, bits)
         sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
         first, ncols = dev.decimation(int(sig.shape[0]), self.sps, 2, TIMING_OFFSET[self.detector])
-        if ncols < self.nbits + 1:
-            raise RuntimeError(f"{ncols} detector rows for {self.nbits} coded bits")
+        if ncols < self.nch + 1:
+            raise RuntimeError(f"{ncols} detector rows for {self.nch} channel bits")
         rows = dev.awgn_mf_bank(sig, self._d_taps, first, self.sps, ncols, self.sigma(ebn0_db), seed, stream_id, 0,
                                 np.exp(-1j * np.pi / 4))
         return rows, syms
@@ -86,6 +155,8 @@ class CodedSOQPSKLink:
     def soft(self, rows):
         """Rows -> (λ of the coded bits, ncw x n_tx view; hard decisions of the same λ)."""
         llr, bits = dev.viterbi_soft(rows, True)
+        if self.framing is not None:
+            return self.deframe(llr[1:]), bits[1:1 + self.nch]
         return llr[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
 
     def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
@@ -103,7 +174,7 @@ class CodedSOQPSKLink:
         tx = dev.ldpc_encode(self.code, info)
         rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
         llr, hard = self.soft(rows)
-        dev.count_errors(syms, syms, hard, tx.reshape(-1), self.nbits, self.uncoded)
+        dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
         dev.ldpc_decode(self.code, llr, scale=self.llr_scale, alpha=self.alpha, max_iter=self.max_iter, ref_info=info,
                         counts=self.counts)
         self.blocks += 1
@@ -112,6 +183,8 @@ class CodedSOQPSKLink:
         self.counts.zero_()
         self.uncoded.zero_()
         self.blocks = 0
+        if self.framing is not None:
+            self.sync.zero_()
 
     def result(self) -> tuple[int, int, int, int, float]:
         """(information bit errors, codeword errors, codewords not converged, information bits compared, mean
@@ -122,8 +195,8 @@ class CodedSOQPSKLink:
         return be, fe, nc, ncw * self.code.k, (its / ncw if ncw else 0.0)
 
     def uncoded_result(self) -> tuple[int, int]:
-        """(bit errors of λ < 0 against the coded bits, coded bits compared) over the same blocks."""
-        return int(self.uncoded.cpu()[1]), self.blocks * self.nbits
+        """(bit errors of λ < 0 against the channel bits in front of the pad, bits compared) over the same blocks."""
+        return int(self.uncoded.cpu()[1]), self.blocks * self.nch
 
 
 class IterativeSOQPSKLink(CodedSOQPSKLink):
@@ -145,7 +218,8 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
     still runs).  ``per_pass=True`` also accumulates the four counts after every pass (``pass_results``)."""
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
-                 damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False) -> None:
+                 damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
+                 lead_bits: int = 0, marker_prior: float | None = None) -> None:
         if outer < 1 or inner < 1:
             raise ValueError("outer and inner must be at least 1")
         if not (math.isfinite(damping) and damping > 0.0):
@@ -155,10 +229,13 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
         if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
             raise ValueError("ext_sat must be finite and positive, ext_clip positive")
-        super().__init__(code, ncw, sps, detector, alpha, max_iter=inner)
+        self.marker_prior = self.ext_sat if marker_prior is None else float(marker_prior)
+        if not math.isfinite(self.marker_prior):
+            raise ValueError("marker_prior must be finite")
+        super().__init__(code, ncw, sps, detector, alpha, max_iter=inner, framing=framing, lead_bits=lead_bits)
         self.per_pass = bool(per_pass)
         self.pass_counts = _hip.zeros((self.outer, 4), "int64")
-        self.prior = self.state = self.iters = self.decided = None
+        self.prior = self.state = self.iters = self.decided = self.ext = None
 
     # ---------------------------------------------------------------- stages
     def begin(self, nrows: int) -> None:
@@ -168,18 +245,29 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
             self.state = _hip.zeros(self.ncw, "uint8")
             self.iters = _hip.zeros(self.ncw, "int32")
             self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
+            self.ext = None if self.framing is None else _hip.zeros((self.ncw, self.code.n_tx), "float32")
         else:
-            for t in (self.prior, self.state, self.iters, self.decided):
-                t.zero_()
+            for t in (self.prior, self.state, self.iters, self.decided, self.ext):
+                if t is not None:
+                    t.zero_()
 
     def detect(self, rows, first: bool = False):
         """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
         of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
         ext, bits = dev.viterbi_soft_apriori(rows, None if first else self.prior, self.damping)
+        if self.framing is not None:
+            return self.deframe(ext[1:], search=first), bits[1:1 + self.nch]
         return ext[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
 
     def decode(self, ext) -> None:
-        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place."""
+        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place.  Framed: the
+        extrinsic values go to the contiguous ``ext`` buffer (frozen codewords keep theirs) and ``frame_scatter`` puts all of
+        them, and ±``marker_prior`` on the marker rows, into the prior at the lock's position."""
+        if self.framing is not None:
+            dev.ldpc_decode_ext(self.code, ext, self.state, self.ext, self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
+                                max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
+            self.framing.scatter(self.ext, self.lock, self.prior[1:], self.marker_prior)
+            return
         dev.ldpc_decode_ext(self.code, ext, self.state, self.prior[1:1 + self.nbits], self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
                             max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
 
@@ -192,7 +280,7 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         for o in range(self.outer):
             ext, hard = self.detect(rows, first=o == 0)
             if o == 0:
-                dev.count_errors(syms, syms, hard, tx.reshape(-1), self.nbits, self.uncoded)
+                dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
             self.decode(ext)
             if self.per_pass:
                 dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.pass_counts[o])
@@ -215,7 +303,7 @@ PAD_SYMS = 8                              # CPM chains: zero symbols after the b
 CPM_WAVEFORMS = {"multih": 1, "pcmfm": 2}  # -> symbol_map kind (the reference's natural-binary mappers)
 
 
-class CodedCPMLink:
+class CodedCPMLink(_Framed):
     """``CodedSOQPSKLink`` for ARTM multi-h (``waveform="multih"``) and PCM/FM (``"pcmfm"``): one block = ``ncw`` codewords of
     ``code`` sent back to back as ONE burst from call 0, plus ``PAD_SYMS`` zero symbols.
 
@@ -231,7 +319,8 @@ class CodedCPMLink:
     has been sent: the λ of its FIRST symbol is weak and can have the wrong sign even without noise, which costs the burst's
     first codeword at most lgM channel errors (one decoder iteration when there is no noise)."""
 
-    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50) -> None:
+    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50, framing=None,
+                 lead_bits: int = 0) -> None:
         from ..viterbi import cpm
 
         if waveform not in CPM_WAVEFORMS:
@@ -253,12 +342,13 @@ class CodedCPMLink:
         self.llr_scale = 1.0
         lg = spec.bits_per_symbol
         self.nbits = self.ncw * code.n_tx
-        self.nsym = self.nbits // lg + PAD_SYMS
+        self._frame_init(framing, lead_bits, lg)
+        self.nsym = (self.nch + lg - 1) // lg + PAD_SYMS
         pulse = np.asarray(pulse, dtype=np.float64)
         geo = cpm.filter_geometry(pulse.size, self.sps, spec, self.nsym)
         self.start0, self.ncalls = int(geo["start0"]), int(geo["ncalls"])
-        if self.ncalls * lg < self.nbits:
-            raise RuntimeError(f"{self.ncalls} detector calls for {self.nbits} coded bits")
+        if self.ncalls * lg < self.nch:
+            raise RuntimeError(f"{self.ncalls} detector calls for {self.nch} channel bits")
         self._d_h = _hip.to_device(spec.mod_index)
         self._d_pulse = _hip.to_device(pulse)
         self._d_templates = _hip.to_device(cpm.matched_filter_templates(pulse, self.sps, cpm.full_phase(spec)))
@@ -275,7 +365,7 @@ class CodedCPMLink:
 
         if ebn0_db is None:
             return 0.0
-        return cpm_sigma(float(ebn0_db) + 10.0 * math.log10(self.code.k / self.code.n_tx), self.sps, self.spec.bits_per_symbol)
+        return cpm_sigma(float(ebn0_db) + self._rate_db(), self.sps, self.spec.bits_per_symbol)
 
     # ---------------------------------------------------------------- stages
     def info_bits(self, stream_id: int = 0):
@@ -286,7 +376,7 @@ class CodedCPMLink:
     def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
         """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst float64[ncalls, nfilt, 2], its symbols)."""
         torch = _hip.torch()
-        bits = torch.cat((tx.reshape(-1), self._pad))
+        bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
         syms = dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
         sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
         received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
@@ -296,6 +386,8 @@ class CodedCPMLink:
     def soft(self, rows):
         """Rows -> (λ of the coded bits, ncw x n_tx view; hard decisions of the same λ)."""
         llr, bits = dev.cpm_soft(rows, self.spec, 0, 0, d_rot=self._d_rot)
+        if self.framing is not None:
+            return self.deframe(llr), bits[:self.nch]
         return llr[:self.nbits].view(self.ncw, self.code.n_tx), bits[:self.nbits]
 
     def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
@@ -307,8 +399,8 @@ class CodedCPMLink:
         return llr.contiguous(), info.view(self.ncw, self.code.k)
 
     def count_uncoded(self, hard, tx) -> None:
-        flat = tx.reshape(-1)
-        dev.count_errors(hard, flat, hard, flat, self.nbits, self.uncoded)     # (bits in both pairs: [1] is what is read)
+        flat = tx.reshape(-1) if self.framing is None else self.sent
+        dev.count_errors(hard, flat, hard, flat, self.nch, self.uncoded)     # (bits in both pairs: [1] is what is read)
 
     # ---------------------------------------------------------------- blocks
     def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
@@ -354,7 +446,7 @@ class IterativeCPMLink(CodedCPMLink):
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False,
-                 prior_warmup: int = 512) -> None:
+                 prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None) -> None:
         if outer < 1 or inner < 1:
             raise ValueError("outer and inner must be at least 1")
         if not (math.isfinite(damping) and damping > 0.0):
@@ -366,10 +458,13 @@ class IterativeCPMLink(CodedCPMLink):
         self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
         if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
             raise ValueError("ext_sat must be finite and positive, ext_clip positive")
-        super().__init__(code, ncw, waveform, sps, alpha, max_iter=inner)
+        self.marker_prior = self.ext_sat if marker_prior is None else float(marker_prior)
+        if not math.isfinite(self.marker_prior):
+            raise ValueError("marker_prior must be finite")
+        super().__init__(code, ncw, waveform, sps, alpha, max_iter=inner, framing=framing, lead_bits=lead_bits)
         self.per_pass = bool(per_pass)
         self.pass_counts = _hip.zeros((self.outer, 4), "int64")
-        self.prior = self.state = self.iters = self.decided = None
+        self.prior = self.state = self.iters = self.decided = self.ext = None
 
     # ---------------------------------------------------------------- stages
     def begin(self, ncalls: int | None = None) -> None:
@@ -380,19 +475,29 @@ class IterativeCPMLink(CodedCPMLink):
             self.state = _hip.zeros(self.ncw, "uint8")
             self.iters = _hip.zeros(self.ncw, "int32")
             self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
+            self.ext = None if self.framing is None else _hip.zeros((self.ncw, self.code.n_tx), "float32")
         else:
-            for t in (self.prior, self.state, self.iters, self.decided):
-                t.zero_()
+            for t in (self.prior, self.state, self.iters, self.decided, self.ext):
+                if t is not None:
+                    t.zero_()
 
     def detect(self, rows, first: bool = False):
         """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
         of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
         ext, bits = dev.cpm_soft_apriori(rows, self.spec, None if first else self.prior, self.damping, 0, 0 if first else self.prior_warmup,
                                          d_rot=self._d_rot)
+        if self.framing is not None:
+            return self.deframe(ext, search=first), bits[:self.nch]
         return ext[:self.nbits].view(self.ncw, self.code.n_tx), bits[:self.nbits]
 
     def decode(self, ext) -> None:
-        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place."""
+        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place (framed: as
+        ``IterativeSOQPSKLink.decode``, the prior at offset 0)."""
+        if self.framing is not None:
+            dev.ldpc_decode_ext(self.code, ext, self.state, self.ext, self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
+                                max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
+            self.framing.scatter(self.ext, self.lock, self.prior, self.marker_prior)
+            return
         dev.ldpc_decode_ext(self.code, ext, self.state, self.prior[:self.nbits], self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
                             max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
 
