@@ -281,6 +281,45 @@ int wf_viterbi4_soft_geometry(wf_ctx *ctx, int64_t ncalls, int warmup, int64_t *
 int wf_viterbi4_soft_apriori(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
                              const float *d_apriori, double apriori_scale, double *d_ext, uint8_t *d_bits, void *stream);
 
+/* ---- Live windows: the detector pass of an iterative loop on the open codewords only -----------------------------------------
+ * (The reference has no coding layer; these entry points are defined here.)
+ * wf_idd_windows: which rows of a burst a detector pass still has to work on, from the decoder's freeze states, ON THE
+ * DEVICE (the loop never synchronises with the host).  d_state: ncw bytes, 0 = open, as wf_ldpc_decode_ext leaves them.
+ * Codeword b occupies the rows [a_b, e_b) of the nrows detector rows, a_b = first + b P, e_b = a_b + n_tx, with
+ * first = row_offset + p̂ + L and p̂ = the first int64 of the 32-byte lock record of wf_frame_search READ FROM DEVICE MEMORY
+ * (d_lock NULL: p̂ = 0).  Codewords sent back to back behind wf_viterbi4_soft: row_offset = 1, d_lock = NULL, L = 0, P = n_tx
+ * (coded bit j is row j + 1); framed: row_offset = 1, the lock, the marker length L, P = L + n_tx.  With the guard G >= 0 rows:
+ *   windows = []
+ *   for b = 0 .. ncw - 1 with d_state[b] == 0:
+ *       s = max(0, a_b - G) & ~1          (even: row k is trellis column k % 2, a window keeps the burst's parity)
+ *       e = min(nrows, e_b + G)
+ *       if e <= s: continue               (the span lies outside the burst: a wrong lock)
+ *       if windows and s - windows[-1].e < G:  windows[-1].e = max(windows[-1].e, e)        (merge)
+ *       else:                                  windows.append((s, e))
+ * d_table (int64, 4 + 2 ncw words, 8-byte aligned) receives [0] W = the number of windows, [1] the live rows sum (e - s),
+ * [2] the codewords with state 0, [3] 0, then the W pairs (s, e) in increasing order; the words behind the pairs are not
+ * specified.  Asynchronous on `stream`; nothing is returned to the host.  waveforms_amd/encoding/live.py states the same in
+ * numpy.  A NULL ctx / d_state / d_table, ncw < 1 or > 2^31, nrows < 1, n_tx < 1, P < n_tx, a negative row_offset, L or G, a
+ * pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_idd_windows(wf_ctx *ctx, const uint8_t *d_state, int64_t ncw, int64_t nrows, int32_t n_tx, int64_t P, int64_t row_offset,
+                   const void *d_lock, int32_t L, int64_t G, int64_t *d_table, void *stream);
+/* wf_viterbi4_soft_apriori over the windows of such a table (d_windows, read on the device; any table of this form will do:
+ * W <= max_windows windows with even starts, 0 <= s < e <= ncalls, in increasing order and disjoint).  For every window (s, e),
+ * d_ext[s .. e) and d_bits[s .. e) are BITWISE what wf_viterbi4_soft_apriori returns for the burst d_rows + s rows,
+ * ncalls = e - s, d_apriori + s: free start at s, free end at e, the same definition, the same independence of `warmup` and
+ * WF_OPT_SOFT_CHUNK_CALLS (the proof and the cascading repair run per window: a window's first chunk starts from zero
+ * metrics at s, its last one from zero at e, exact as the ends of a burst are), the same options and counters.  Rows outside
+ * every window are NOT WRITTEN; W = 0 writes nothing and runs no chunk.  d_rows, d_apriori, d_ext and d_bits are the whole
+ * burst's (ncalls rows); d_apriori must not be NULL (the first pass of a block, where no codeword is frozen, is the plain
+ * detector's).  W and the live rows are known on the device only: the launches are sized for every row live plus one
+ * partial chunk per window (max_windows of them: ncw for a table of wf_idd_windows) and so is the context's detector
+ * scratch; a lane without a live chunk leaves at once.  A table that is not of the form above raises the context's fault
+ * word (wf_ctx_check: WF_ERR_DEVICE) and no row is touched.  A NULL pointer, max_windows < 1, a table not 8-byte aligned or
+ * any argument wf_viterbi4_soft_apriori refuses: WF_ERR_VALUE before the context is touched. */
+int wf_viterbi4_soft_apriori_windows(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
+                                     const float *d_apriori, double apriori_scale, const int64_t *d_windows, int64_t max_windows,
+                                     double *d_ext, uint8_t *d_bits, void *stream);
+
 /* wf_viterbi4_detect + wf_count_errors in one call (fresh detector): decision k is
  * compared with reference element k - skip for 0 <= k - skip < ncompare
  * (examples/soqpsk_detection.py:201-209: skip = length); counts are ADDED to d_counts[0..1]. */

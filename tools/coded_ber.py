@@ -3,7 +3,7 @@ decoder's speed; prints ONE JSON line.
 
     python tools/coded_ber.py [--waveform soqpsk|multih|pcmfm] [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N]
                               [--detector PT] [--steps 5] [--outer N --inner M --damping D]
-                              [--framed [--lead-bits J] [--marker-prior X]]
+                              [--framed [--lead-bits J] [--marker-prior X]] [--live-only [--guard G]]
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -25,6 +25,13 @@ codewords per burst, next to the unframed curve and at the same information Eb/N
 counts, the wrong locks, the last lock record, and the times of ``frame_search``, ``frame_gather`` and ``frame_scatter`` on
 the burst (device events).  With ``--outer`` the framed iterative link runs too, the marker rows carrying
 ``--marker-prior`` (default: ext_sat; 0 = no marker prior).
+
+With ``--live-only`` (SOQPSK-TG, with ``--outer``) every iterative link, framed or not, gets a twin with ``live_only=True`` and
+``--guard`` rows of guard, run on the SAME blocks: its counts after every pass, what every pass worked on (windows, live rows,
+codewords open on entry, summed over the blocks), the number of codewords whose FINAL decisions differ from the full loop's,
+and the per-pass detector and decoder times of both loops from the same run: ``--steps`` timed blocks after one warm-up
+block, full and windowed alternating (device events; a windowed detector pass includes the window table, a framed one the
+gather, a framed decoder pass the scatter).
 """
 import argparse
 import json
@@ -35,6 +42,52 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
+
+
+def time_loops(links, code, ebn0, first_block, steps):
+    """Per-pass detector and decoder times (ms per block, device events) of several loops on the same blocks, the loops
+    alternating block by block; one warm-up block each, not timed -> (det[len(links), outer], dec[...])."""
+    import torch
+
+    from waveforms_amd import device as dev
+
+    outer = links[0].outer
+    pev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * outer + 1)]
+    det, dec = np.zeros((len(links), outer)), np.zeros((len(links), outer))
+    for s in range(steps + 1):
+        for i, lk in enumerate(links):
+            tx = dev.ldpc_encode(code, lk.info_bits(first_block + s))
+            rows, _ = lk.front_end(tx, ebn0, 1, first_block + s)
+            lk.begin(int(rows.shape[0]))
+            pev[0].record()
+            for o in range(outer):
+                ext, _ = lk.detect(rows, first=o == 0)
+                pev[2 * o + 1].record()
+                lk.decode(ext)
+                pev[2 * o + 2].record()
+            torch.cuda.synchronize()
+            if s:
+                det[i] += [pev[2 * o].elapsed_time(pev[2 * o + 1]) for o in range(outer)]
+                dec[i] += [pev[2 * o + 1].elapsed_time(pev[2 * o + 2]) for o in range(outer)]
+    return det / max(steps, 1), dec / max(steps, 1)
+
+
+def live_point(full, lv, differ, code, ebn0, first_block, steps, ncw):
+    """The windowed loop's part of a point: its counts (it has run the point's blocks beside ``full``), what its passes worked
+    on, the decisions that differ, and both loops' times from one alternating run."""
+    ibe, ife, inc, im, imean = lv.result()
+    det, dec = time_loops([full, lv], code, ebn0, first_block, steps)
+
+    def ms(i):
+        return {"detector_passes": [round(v, 4) for v in det[i]], "decoder_passes": [round(v, 4) for v in dec[i]],
+                "detector_total": round(float(det[i].sum()), 4), "decoder_total": round(float(dec[i].sum()), 4)}
+
+    return {"guard": lv.guard, "coded_ber": ibe / im, "fer": ife / ncw, "info_bit_errors": ibe, "codeword_errors": ife, "open": inc,
+            "total_inner_iters_mean": round(imean, 3),
+            "per_pass": [{"info_bit_errors": p[0], "codeword_errors": p[1], "open": p[2], "iters_mean": round(p[3], 3)} for p in lv.pass_results()],
+            "live_per_pass": [{"windows": w, "live_rows": r, "open_on_entry": n} for w, r, n in lv.live_results()],
+            "burst_rows": int(lv.prior.numel()), "final_decisions_differ": int(differ),
+            "ms_per_block": ms(1), "full_loop_ms_per_block_same_run": ms(0)}
 
 
 def main() -> None:
@@ -54,7 +107,11 @@ def main() -> None:
     ap.add_argument("--framed", action="store_true", help="also run the framed link (sync marker + randomiser + soft frame search)")
     ap.add_argument("--lead-bits", type=int, default=0, help="pseudo-random bits in front of the framed burst (0 .. period - 1)")
     ap.add_argument("--marker-prior", type=float, default=None, help="prior of the marker rows in the framed loop (default ext_sat)")
+    ap.add_argument("--live-only", action="store_true", help="also run the iterative loop(s) with the detector on the live windows only")
+    ap.add_argument("--guard", type=int, default=128, help="guard rows of --live-only")
     args = ap.parse_args()
+    if args.live_only and (args.waveform != "soqpsk" or args.outer < 1):
+        ap.error("--live-only is the SOQPSK-TG loop's: it needs --waveform soqpsk and --outer N")
 
     import torch
 
@@ -78,6 +135,10 @@ def main() -> None:
                                                                 damping=args.damping, per_pass=True, **which)
         out["iterative"] = {"outer": idd.outer, "inner": idd.inner, "damping": idd.damping, "ext_sat": idd.ext_sat,
                             "ext_clip": None if np.isinf(idd.ext_clip) else idd.ext_clip}
+    lidd = lfidd = None
+    if args.live_only:
+        lidd = IterativeSOQPSKLink(code, per, alpha=args.alpha, outer=args.outer, inner=args.inner, damping=args.damping, per_pass=True,
+                                   live_only=True, guard=args.guard, **which)
     flink = fidd = None
     if args.framed:
         from waveforms_amd.encoding.framing import Framing
@@ -91,6 +152,10 @@ def main() -> None:
                                                                      damping=args.damping, per_pass=True, framing=fr,
                                                                      lead_bits=args.lead_bits, marker_prior=args.marker_prior, **which)
             out["framed"]["marker_prior"] = fidd.marker_prior
+            if args.live_only:
+                lfidd = IterativeSOQPSKLink(code, per, alpha=args.alpha, outer=args.outer, inner=args.inner, damping=args.damping, per_pass=True,
+                                            framing=fr, lead_bits=args.lead_bits, marker_prior=args.marker_prior, live_only=True,
+                                            guard=args.guard, **which)
     for e in args.ebn0:
         link.reset_counts()
         b = 0
@@ -120,8 +185,14 @@ def main() -> None:
         it_point = None
         if idd is not None:
             idd.reset_counts()
+            differ = torch.zeros((), dtype=torch.int64, device="cuda")
+            if lidd is not None:
+                lidd.reset_counts()
             for blk in range(b):
                 idd.run_block(e, seed=1, stream_id=blk)
+                if lidd is not None:
+                    lidd.run_block(e, seed=1, stream_id=blk)
+                    differ += (idd.decided != lidd.decided).any(dim=1).sum()
             ibe, ife, inc, im, imean = idd.result()
             passes = idd.pass_results()
             # timing: front end once (not timed again), then every pass bracketed
@@ -149,6 +220,8 @@ def main() -> None:
                 "ms_per_block": {"detector_passes": [round(v, 4) for v in det_ms], "decoder_passes": [round(v, 4) for v in dec_ms],
                                  "detector_total": round(float(det_ms.sum()), 4), "decoder_total": round(float(dec_ms.sum()), 4)},
             }
+            if lidd is not None:
+                it_point["live_only"] = live_point(idd, lidd, differ, code, e, b, args.steps, ncw)
         fr_point = None
         if flink is not None:
             flink.reset_counts()
@@ -182,14 +255,22 @@ def main() -> None:
                         "ms": {"frame_search": round(fms[0], 4), "frame_gather": round(fms[1], 4), "frame_scatter": round(fms[2], 4)}}
             if fidd is not None:
                 fidd.reset_counts()
+                differ = torch.zeros((), dtype=torch.int64, device="cuda")
+                if lfidd is not None:
+                    lfidd.reset_counts()
                 for blk in range(b):
                     fidd.run_block(e, seed=1, stream_id=blk)
+                    if lfidd is not None:
+                        lfidd.run_block(e, seed=1, stream_id=blk)
+                        differ += (fidd.decided != lfidd.decided).any(dim=1).sum()
                 ibe, ife, inc, im, imean = fidd.result()
                 fr_point["iterative"] = {
                     "coded_ber": ibe / im, "fer": ife / ncw, "info_bit_errors": ibe, "codeword_errors": ife, "open": inc,
                     "total_inner_iters_mean": round(imean, 3), "wrong_locks": fidd.sync_result()[1],
                     "per_pass": [{"info_bit_errors": p[0], "codeword_errors": p[1], "open": p[2], "iters_mean": round(p[3], 3)}
                                  for p in fidd.pass_results()]}
+                if lfidd is not None:
+                    fr_point["iterative"]["live_only"] = live_point(fidd, lfidd, differ, code, e, b, args.steps, ncw)
         out["points"].append({
             "ebn0_info_db": e, "ebn0_channel_db": round(e + 10 * np.log10(code.k / code.n_tx), 3), "codewords": ncw,
             "coded_ber": be / m, "fer": fe / ncw, "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,

@@ -62,6 +62,8 @@ SIGNATURES = {
     "wf_viterbi4_soft": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P]),
     "wf_viterbi4_soft_geometry": (c_int, [_P, c_int64, c_int, POINTER(c_int64)]),
     "wf_viterbi4_soft_apriori": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_double, _P, _P, _P]),
+    "wf_idd_windows": (c_int, [_P, _P, c_int64, c_int64, ctypes.c_int32, c_int64, c_int64, _P, ctypes.c_int32, c_int64, _P, _P]),
+    "wf_viterbi4_soft_apriori_windows": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, c_double, _P, c_int64, _P, _P, _P]),
     "wf_viterbi4_detect_window": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "wf_viterbi4_window_state_bytes": (c_int64, []),
     "wf_viterbi4_state_bytes": (c_int64, [c_int]),

@@ -36,7 +36,7 @@ void wf_set_error(const char *fmt, ...);
 #define WF_LAUNCH_CHECK() WF_HIP(hipGetLastError())
 
 // Device fault word bits (wf_ctx::d_fault).
-enum { WF_FAULT_SCAN_TIMEOUT = 1u };
+enum { WF_FAULT_SCAN_TIMEOUT = 1u, WF_FAULT_LIVE_TABLE = 2u };   // (2: wf_viterbi4_soft_apriori_windows met a malformed window table)
 
 struct wf_lfsr_tables {
     uint64_t host[64][64];  // host[j][c] = column c of T^(2^j)

@@ -153,7 +153,7 @@ extern "C" int wf_ctx_check(wf_ctx *c, void *stream)
     unsigned f = *c->h_fault;
     if (f) {
         WF_HIP(hipMemsetAsync(c->d_fault, 0, sizeof(unsigned), wf_stream(stream)));
-        wf_set_error("device fault word 0x%x (bit0 = scan hand-off timeout)", f);
+        wf_set_error("device fault word 0x%x (bit0 = scan hand-off timeout, bit1 = malformed live-window table)", f);
         return WF_ERR_DEVICE;
     }
     return WF_OK;

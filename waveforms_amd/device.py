@@ -237,6 +237,70 @@ def viterbi_soft_apriori(rows, apriori=None, apriori_scale: float = 1.0, differe
     return ext[:ncalls], bits[:ncalls]
 
 
+def idd_windows(state, nrows: int, n_tx: int, period: int | None = None, row_offset: int = 1, lock=None, marker_bits: int = 0,
+                guard: int = 128, out=None, ctx=None):
+    """The live windows of a burst from the decoder's freeze states (``wf_idd_windows``; include/wfhip.h states the definition,
+    ``waveforms_amd.encoding.live.windows_host`` restates it) -> device int64[4 + 2 ncw]: W, live rows, open codewords, 0, then
+    W pairs (s, e).  ``state``: device u8[ncw], 0 = open.  Codeword b starts at row ``row_offset`` + p̂ + ``marker_bits`` +
+    b ``period`` (``period`` default ``n_tx``), p̂ read on the device from ``lock`` (the record of ``frame_search``; None: 0).
+    Nothing comes back to the host."""
+    torch = _hip.torch()
+    period = int(n_tx) if period is None else int(period)
+    if int(guard) < 0:
+        raise ValueError(f"guard = {guard} must not be negative")
+    if int(nrows) < 1 or int(n_tx) < 1 or period < int(n_tx) or int(row_offset) < 0 or int(marker_bits) < 0:
+        raise ValueError("nrows and n_tx must be at least 1, period at least n_tx, row_offset and marker_bits not negative")
+    if state.dtype != torch.uint8 or state.numel() < 1 or not state.is_contiguous():
+        raise ValueError("state must hold ncw contiguous bytes")
+    ncw = int(state.numel())
+    if out is None:
+        out = _hip.empty(4 + 2 * ncw, "int64")
+    elif out.dtype != torch.int64 or out.numel() < 4 + 2 * ncw or not out.is_contiguous():
+        raise ValueError("out must hold 4 + 2 ncw contiguous int64")
+    _hip.check(_hip.lib().wf_idd_windows(ctx if ctx is not None else _hip.ctx(), _hip.ptr(state), ncw, int(nrows), int(n_tx), period,
+                                         int(row_offset), None if lock is None else _hip.ptr(_frame_lock(lock)), int(marker_bits), int(guard),
+                                         _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def viterbi_soft_apriori_windows(rows, apriori, windows, apriori_scale: float = 1.0, differential: bool = True, warmup: int = 0,
+                                 row_bytes: int = 48, ctx=None, out=None, max_windows: int | None = None):
+    """``viterbi_soft_apriori`` on the live windows of a burst only (``wf_viterbi4_soft_apriori_windows``; include/wfhip.h
+    states the definition) -> (ext f64[ncalls], bits u8[ncalls]) on device.  ``windows``: the device int64 table of
+    ``idd_windows`` (read on the device; ``max_windows`` default: what the table has room for).  Inside a window the result
+    is bitwise ``viterbi_soft_apriori`` of the slice; rows outside every window are NOT written: pass ``out`` = (ext, bits) of
+    an earlier pass to keep their values (fresh, uninitialised buffers otherwise)."""
+    torch = _hip.torch()
+    if row_bytes not in (32, 48):
+        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    nbytes = rows.numel() * rows.element_size()
+    if nbytes % row_bytes or nbytes == 0:
+        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
+    ncalls = nbytes // row_bytes
+    if apriori is None or apriori.dtype != torch.float32 or not apriori.is_contiguous() or apriori.numel() != ncalls:
+        raise ValueError(f"apriori must be {ncalls} contiguous float32 values (one per row)")
+    if windows.dtype != torch.int64 or not windows.is_contiguous() or windows.numel() < 6:
+        raise ValueError("windows must be the contiguous int64 table idd_windows writes (at least 6 words)")
+    room = (windows.numel() - 4) // 2
+    max_windows = room if max_windows is None else int(max_windows)
+    if not 1 <= max_windows <= room:
+        raise ValueError(f"max_windows = {max_windows} outside 1 .. {room} (the table's room)")
+    if out is None:
+        ext, bits = _hip.empty(ncalls, "float64"), _hip.empty(ncalls + 16, "uint8")
+    else:
+        ext, bits = out
+        if ext.dtype != torch.float64 or not ext.is_contiguous() or ext.numel() < ncalls:
+            raise ValueError("out[0] must hold ncalls contiguous float64")
+        if bits.dtype != torch.uint8 or not bits.is_contiguous() or bits.numel() < ncalls:
+            raise ValueError("out[1] must hold ncalls contiguous bytes")
+    _hip.check(_hip.lib().wf_viterbi4_soft_apriori_windows(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(row_bytes),
+                                                           int(bool(differential)), int(warmup), _hip.ptr(apriori), float(apriori_scale),
+                                                           _hip.ptr(windows), max_windows, _hip.ptr(ext), _hip.ptr(bits), _hip.stream()))
+    return ext[:ncalls], bits[:ncalls]
+
+
 def cpm_soft(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None):
     """Max-log-MAP soft output of the generic CPM trellis (``wf_cpm_soft``; include/wfhip.h states the definition) -> (llr
     f64[n lgM], bits u8[n lgM]) on device, one fresh burst.  ``spec``: a full-phase design (NC = p, at most 64 states:

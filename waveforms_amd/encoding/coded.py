@@ -22,6 +22,7 @@ import numpy as np
 
 from .. import _hip
 from .. import device as dev
+from .live import DEFAULT_GUARD
 from ..cpm.soqpsk import freq_pulse_soqpsk_tg
 from ..cpm.trellis.model import SOQPSKTrellis4x2DiffEncoded
 from ..filters.matched import pam_matched_filter_taps, pt_matched_filter_taps
@@ -215,13 +216,26 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
     sum sps + 1 unit-magnitude taps): the defaults are ext_sat = 6.25 sps (50 at sps 8, where mean |λ| is about 11 at
     4.5 dB) and no clip.  ``outer`` is fixed per block and nothing synchronises with the host inside one; every pass is
     queued even when every codeword is already frozen (the decoder's workgroups then retire at once, the detector
-    still runs).  ``per_pass=True`` also accumulates the four counts after every pass (``pass_results``)."""
+    still runs).  ``per_pass=True`` also accumulates the four counts after every pass (``pass_results``).
+
+    ``live_only=True`` is the answer to that last remark: pass 1 is unchanged, every later pass first turns the states the
+    previous decoder pass left into the burst's live windows (``idd_windows``: the rows of the open codewords and ``guard``
+    rows on either side, on the device) and runs the detector on those rows only (``viterbi_soft_apriori_windows``), into the
+    ONE ext / bits buffer the block keeps: rows outside the windows hold an earlier pass's values, and the decoder never
+    reads a frozen codeword's input.  Still no host synchronisation and a fixed ``outer``; a pass with nothing open costs
+    launches that find nothing.  A window's edges start from free metrics instead of the burst's history, so this is the
+    full loop exactly only when the metrics merge within the guard; the frozen neighbours' saturated priors pin the trellis
+    within a few rows, and INTEGRATION.md has the counts behind the default of 128 rows (``guard >= nrows`` makes any open
+    codeword's window the whole burst: the full loop bit for bit).  ``live_results`` returns what each pass worked on."""
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
-                 lead_bits: int = 0, marker_prior: float | None = None) -> None:
+                 lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD) -> None:
         if outer < 1 or inner < 1:
             raise ValueError("outer and inner must be at least 1")
+        if int(guard) < 0:
+            raise ValueError(f"guard = {guard} must not be negative")
+        self.live_only, self.guard = bool(live_only), int(guard)
         if not (math.isfinite(damping) and damping > 0.0):
             raise ValueError("damping must be finite and positive")
         self.outer, self.inner, self.damping = int(outer), int(inner), float(damping)
@@ -236,10 +250,14 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         self.per_pass = bool(per_pass)
         self.pass_counts = _hip.zeros((self.outer, 4), "int64")
         self.prior = self.state = self.iters = self.decided = self.ext = None
+        self.live_counts = _hip.zeros((self.outer, 3), "int64") if self.live_only else None
+        self.windows = _hip.zeros(4 + 2 * self.ncw, "int64") if self.live_only else None
+        self._live_out, self._live_first = None, 0          # the block's ext / bits buffers; first passes run
 
     # ---------------------------------------------------------------- stages
     def begin(self, nrows: int) -> None:
         """Fresh loop state of one block: prior 0 on every row, every codeword open, no iterations."""
+        self._live_out = None
         if self.prior is None or self.prior.numel() != nrows:
             self.prior = _hip.zeros(nrows, "float32")
             self.state = _hip.zeros(self.ncw, "uint8")
@@ -251,10 +269,30 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
                 if t is not None:
                     t.zero_()
 
-    def detect(self, rows, first: bool = False):
+    def live_windows(self, nrows: int):
+        """The live windows of the burst's ``nrows`` rows for the states as they are now -> the device table of ``idd_windows``
+        (kept in ``windows``).  Coded bit j is row j + 1; framed, codeword 0 starts behind the lock's p̂ and one marker."""
+        if self.framing is None:
+            return dev.idd_windows(self.state, nrows, self.code.n_tx, guard=self.guard, out=self.windows)
+        return dev.idd_windows(self.state, nrows, self.code.n_tx, self.framing.period, 1, self.lock, self.framing.L, self.guard, out=self.windows)
+
+    def detect(self, rows, first: bool = False, o: int | None = None):
         """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
-        of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
-        ext, bits = dev.viterbi_soft_apriori(rows, None if first else self.prior, self.damping)
+        of a block has prior 0 everywhere and takes the plain detector (bitwise the same result).  ``live_only``: every
+        later pass works on the live windows only and writes into the first pass's buffers; ``o`` is the pass whose entry
+        of ``live_results`` gets the table's counts (None: nobody's)."""
+        if self.live_only and not first:
+            if self._live_out is None:
+                raise RuntimeError("live_only: the block's first pass (first=True) has not run")
+            table = self.live_windows(int(self._live_out[0].numel()))
+            if o is not None:
+                self.live_counts[o] += table[:3]
+            ext, bits = dev.viterbi_soft_apriori_windows(rows, self.prior, table, self.damping, out=self._live_out)
+        else:
+            ext, bits = dev.viterbi_soft_apriori(rows, None if first else self.prior, self.damping)
+            if self.live_only:
+                self._live_out = (ext, bits)
+                self._live_first += o is not None
         if self.framing is not None:
             return self.deframe(ext[1:], search=first), bits[1:1 + self.nch]
         return ext[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
@@ -278,7 +316,7 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
         self.begin(int(rows.shape[0]))
         for o in range(self.outer):
-            ext, hard = self.detect(rows, first=o == 0)
+            ext, hard = self.detect(rows, first=o == 0, o=o)
             if o == 0:
                 dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
             self.decode(ext)
@@ -290,6 +328,9 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
     def reset_counts(self) -> None:
         super().reset_counts()
         self.pass_counts.zero_()
+        if self.live_only:
+            self.live_counts.zero_()
+            self._live_first = 0
 
     def pass_results(self) -> list[tuple[int, int, int, float]]:
         """Per outer pass (``per_pass=True``): (information bit errors, codeword errors, codewords still open, mean
@@ -297,6 +338,18 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
         ncw = self.blocks * self.ncw
         return [(int(be), int(fe), int(nc), (int(its) / ncw if ncw else 0.0)) for be, fe, nc, its in self.pass_counts.cpu().tolist()]
+
+    def live_results(self) -> list[tuple[int, int, int]]:
+        """Per outer pass (``live_only=True``): (windows, live rows, codewords open on entry), summed over the blocks
+        run since ``reset_counts`` - synchronises.  Pass 1 is the plain detector on the whole burst: one
+        window of every row, every codeword open.  The later entries are the words [0 .. 2] of the passes' window tables,
+        added up on the device."""
+        if not self.live_only:
+            raise RuntimeError("live_results needs live_only=True")
+        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
+        rest = [tuple(int(v) for v in row) for row in self.live_counts.cpu().tolist()[1:]]
+        nrows = 0 if self.prior is None else int(self.prior.numel())
+        return [(self._live_first, self._live_first * nrows, self._live_first * self.ncw)] + rest
 
 
 PAD_SYMS = 8                              # CPM chains: zero symbols after the burst's last codeword
