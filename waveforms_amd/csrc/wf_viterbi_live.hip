@@ -18,11 +18,9 @@
 //
 // Rows, priors and outputs are addressed by their index in the BURST: a window starts on an even row, so row k is trellis
 // column k % 2 in the burst and in the window alike, and a window's rows go through exactly the operations the burst
-// detector applies to the slice (wf_viterbi_soft_apriori.h has them).  The result is the definition for any chunk length
+// detector applies to the slice (wf_viterbi_soft.h has them: the walks over a soft_chunk whose limits are its window's).  The result is the definition for any chunk length
 // and warm-up, as the burst detector's is, because every chunk start that is not exact is proven or repaired.
-#include "wf_viterbi_soft_apriori.h"
-
-#include <cmath>
+#include "wf_viterbi_soft.h"
 
 // ---- the window table ---------------------------------------------------------------------------------------------------
 struct live_span {
@@ -199,12 +197,11 @@ __global__ __launch_bounds__(LIVE_WIN_THREADS) void live_plan_kernel(const int64
 }
 
 struct live_chunk {
-    int64_t a, e;           // the chunk's rows
-    int64_t ws, we;         // its window's
+    soft_chunk k;           // rows, its window's edges as the limits; records and ã lane by its own number, either direction
     bool first, last;       // of its window
 };
 
-__device__ __forceinline__ live_chunk live_find(const int64_t *__restrict__ plan, const int64_t *__restrict__ table, int64_t c, int ch)
+__device__ __forceinline__ live_chunk live_find(const int64_t *__restrict__ plan, const int64_t *__restrict__ table, int64_t c, int ch, int64_t tmax)
 {
     const int64_t *cum = plan + LIVE_PLAN_HDR;
     int64_t lo = 0, hi = plan[1];                              // cum[lo] <= c < cum[hi]
@@ -213,13 +210,8 @@ __device__ __forceinline__ live_chunk live_find(const int64_t *__restrict__ plan
         if (cum[mid] <= c) lo = mid;
         else hi = mid;
     }
-    live_chunk k;
-    k.ws = table[4 + 2 * lo], k.we = table[4 + 2 * lo + 1];
-    k.a = k.ws + (c - cum[lo]) * ch;
-    k.e = k.a + ch < k.we ? k.a + ch : k.we;
-    k.first = c == cum[lo];
-    k.last = c + 1 == cum[lo + 1];
-    return k;
+    const int64_t ws = table[4 + 2 * lo], we = table[4 + 2 * lo + 1], a = ws + (c - cum[lo]) * ch;
+    return live_chunk{soft_chunk{a, a + ch < we ? a + ch : we, ws, we, c, c, c, tmax}, c == cum[lo], c + 1 == cum[lo + 1]};
 }
 
 struct live_args {
@@ -237,19 +229,7 @@ __global__ __launch_bounds__(SOFT_THREADS) void live_bounds_kernel(live_args g)
 {
     const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
     if (c >= g.plan[0]) return;
-    const live_chunk k = live_find(g.plan, g.table, c, g.ch);
-    soft_prior_win w;
-    double m[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t r = k.a - g.warmup > k.ws ? k.a - g.warmup : k.ws; r < k.a; ++r) soft_ap_fwd_row<PACKED, DIFF>(m, g.rows, g.pr, w, r);
-    soft_put4(g.fedge + 8 * c, m);
-    soft_ap_fwd_chunk<PACKED, DIFF>(g.rows, g.pr, w, k.a, k.e, c, g.tmax, g.alpha, m);
-    soft_put4(g.fedge + 8 * c + 4, m);
-
-    double b[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t r = (k.e + g.warmup < k.we ? k.e + g.warmup : k.we) - 1; r >= k.e; --r) soft_ap_bwd_row<PACKED, DIFF>(b, g.rows, g.pr, w, r);
-    soft_put4(g.bedge + 8 * c, b);
-    for (int64_t r = k.e - 1; r >= k.a; --r) soft_ap_bwd_row<PACKED, DIFF>(b, g.rows, g.pr, w, r);
-    soft_put4(g.bedge + 8 * c + 4, b);
+    soft_bounds_body<PACKED, DIFF, true>(g.rows, g.pr, live_find(g.plan, g.table, c, g.ch, g.tmax).k, g.warmup, g.fedge, g.bedge, g.alpha);
 }
 
 // ---- proof and repair -------------------------------------------------------------------------------------------------------
@@ -267,7 +247,7 @@ __device__ __forceinline__ bool live_fixup_verify(const live_args &g, const doub
     const unsigned long long *rec = reinterpret_cast<const unsigned long long *>(edge);
     int listed = 0;
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < T; c += (int64_t)gridDim.x * blockDim.x) {
-        const live_chunk k = live_find(g.plan, g.table, c, g.ch);
+        const live_chunk k = live_find(g.plan, g.table, c, g.ch, g.tmax);
         if (BWD ? k.last : k.first) continue;                  // starts at its window's edge: exact
         const unsigned long long *st = rec + 8 * c, *en = rec + 8 * (BWD ? c + 1 : c - 1) + 4;
         if (st[0] != en[0] || st[1] != en[1] || st[2] != en[2] || st[3] != en[3]) {
@@ -293,26 +273,8 @@ __device__ __forceinline__ bool live_fixup_verify(const live_args &g, const doub
 template <bool PACKED, bool BWD, int DIFF>
 __device__ __forceinline__ int64_t live_rerun(const live_args &g, double *__restrict__ edge, int64_t c)
 {
-    const live_chunk k = live_find(g.plan, g.table, c, g.ch);
-    double *rec = edge + 8 * c;
-    const double *pred = edge + 8 * (BWD ? c + 1 : c - 1) + 4;
-    double m[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        m[q] = __hip_atomic_load(pred + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        rec[q] = m[q];
-    }
-    soft_prior_win w;
-    if (BWD)
-        for (int64_t r = k.e - 1; r >= k.a; --r) soft_ap_bwd_row<PACKED, DIFF>(m, g.rows, g.pr, w, r);
-    else
-        soft_ap_fwd_chunk<PACKED, DIFF>(g.rows, g.pr, w, k.a, k.e, c, g.tmax, g.alpha, m);
-    bool changed = false;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        changed |= __double_as_longlong(rec[4 + q]) != __double_as_longlong(m[q]);
-        rec[4 + q] = m[q];
-    }
+    const live_chunk k = live_find(g.plan, g.table, c, g.ch, g.tmax);
+    const bool changed = soft_rerun_body<PACKED, BWD, DIFF, true>(g.rows, g.pr, k.k, edge + 8 * c, edge + 8 * (BWD ? c + 1 : c - 1) + 4, g.alpha);
     if (!changed) return -2;
     if (BWD ? k.first : k.last) return -1;
     return BWD ? c - 1 : c + 1;
@@ -349,27 +311,7 @@ __global__ __launch_bounds__(SOFT_THREADS) void live_llr_kernel(live_args g, dou
 {
     const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
     if (c >= g.plan[0]) return;
-    const live_chunk k = live_find(g.plan, g.table, c, g.ch);
-    double b[4], m[4];
-    soft_prior_win w;
-    soft_get4(g.bedge + 8 * c, b);                             // b̃ at the chunk's end, proven
-    for (int64_t r = k.e - 1; r >= k.a; --r) {
-        soft_get4(g.alpha + 4 * ((r - k.a) * g.tmax + c), m);  // ã_r (of inc')
-        const double2 *z = soft_row<PACKED>(g.rows, r);
-        const double pi = soft_prior_at(g.pr, w, r);
-        double lam;
-        if (r & 1) {
-            const vit_comp q = vit_components<1, PACKED>(z);
-            lam = soft_llr<1, DIFF>(m, b, q);
-            soft_ap_bwd<1, DIFF>(b, q, pi);
-        } else {
-            const vit_comp q = vit_components<0, PACKED>(z);
-            lam = soft_llr<0, DIFF>(m, b, q);
-            soft_ap_bwd<0, DIFF>(b, q, pi);
-        }
-        ext[r] = lam;
-        bits[r] = lam + pi < 0.0 ? 1 : 0;
-    }
+    soft_llr_body<PACKED, DIFF, true>(g.rows, g.pr, live_find(g.plan, g.table, c, g.ch, g.tmax).k, g.bedge, g.alpha, ext, bits);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -401,16 +343,11 @@ static int live_run(wf_ctx *ctx, const live_args &a, unsigned long long *fhdr, u
     const unsigned grid = (unsigned)((a.tmax + SOFT_THREADS - 1) / SOFT_THREADS);
     hipLaunchKernelGGL((live_bounds_kernel<PACKED, DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, a);
     WF_LAUNCH_CHECK();
-    // repair, count only, or repair and count behind it: as wf_viterbi_soft.hip (soft_run)
     const unsigned fgrid = (unsigned)wf_grid_for(a.tmax, 256, 1024);
-    const int passes = ctx->opt[WF_OPT_DET_REPAIR] == 0 && ctx->opt[WF_OPT_DET_FINAL_VERIFY] ? 2 : 1;
-    for (int pass = 0; pass < passes; ++pass) {
-        const int mode = pass == 0 && ctx->opt[WF_OPT_DET_REPAIR] == 0 ? 1 : 0;
-        hipLaunchKernelGGL((live_fixup_kernel<PACKED, false, DIFF>), dim3(fgrid), dim3(256), 0, s, a, fhdr, ctx->d_vit_unmerged, mode);
-        WF_LAUNCH_CHECK();
-        hipLaunchKernelGGL((live_fixup_kernel<PACKED, true, DIFF>), dim3(fgrid), dim3(256), 0, s, a, bhdr, ctx->d_vit_unmerged, mode);
-        WF_LAUNCH_CHECK();
-    }
+    const int rc = soft_fixup_passes(ctx, [&](auto bwd, int mode) {
+        hipLaunchKernelGGL((live_fixup_kernel<PACKED, decltype(bwd)::value, DIFF>), dim3(fgrid), dim3(256), 0, s, a, bwd ? bhdr : fhdr, ctx->d_vit_unmerged, mode);
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL((live_llr_kernel<PACKED, DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, a, ext, bits);
     WF_LAUNCH_CHECK();
     return WF_OK;
@@ -420,20 +357,15 @@ extern "C" int wf_viterbi4_soft_apriori_windows(wf_ctx *ctx, const double *d_row
                                                 const float *d_apriori, double apriori_scale, const int64_t *d_windows, int64_t max_windows,
                                                 double *d_ext, uint8_t *d_bits, void *stream)
 {
-    WF_REQUIRE(ctx && d_rows && d_apriori && d_windows && d_ext && d_bits, "wf_viterbi4_soft_apriori_windows: NULL argument");
-    WF_REQUIRE(ncalls >= 1 && warmup >= 0, "wf_viterbi4_soft_apriori_windows: bad argument");
-    WF_REQUIRE(max_windows >= 1 && max_windows <= ((int64_t)1 << 31), "wf_viterbi4_soft_apriori_windows: max_windows = %lld outside 1 .. 2^31",
-               (long long)max_windows);
-    WF_REQUIRE(row_bytes == 32 || row_bytes == 48, "wf_viterbi4_soft_apriori_windows: row_bytes must be 32 (packed) or 48 (3 complex128)");
-    WF_REQUIRE(std::isfinite(apriori_scale), "wf_viterbi4_soft_apriori_windows: apriori_scale must be finite");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_ext) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_apriori) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_windows) & 7) == 0,
-               "wf_viterbi4_soft_apriori_windows: rows must be 16-byte, ext and the window table 8-byte and the prior 4-byte aligned");
+    static const char who[] = "wf_viterbi4_soft_apriori_windows";
+    WF_REQUIRE(d_apriori && d_windows, "%s: NULL argument", who);
+    int rc = soft_check_args(who, ctx, d_rows, ncalls, row_bytes, warmup, d_apriori, apriori_scale, d_windows, d_ext, d_bits,
+                             "rows must be 16-byte, ext and the window table 8-byte and the prior 4-byte aligned");
+    if (rc) return rc;
+    WF_REQUIRE(max_windows >= 1 && max_windows <= ((int64_t)1 << 31), "%s: max_windows = %lld outside 1 .. 2^31", who, (long long)max_windows);
     const soft_geom g = soft_geometry(ctx, ncalls, warmup);
     const live_geom l = live_geometry(g, max_windows);
-    WF_REQUIRE((l.tmax + SOFT_THREADS - 1) / SOFT_THREADS < (1ll << 31), "wf_viterbi4_soft_apriori_windows: burst too long for one launch");
-    WF_HIP(hipSetDevice(ctx->device));
-    const int rc = wf_ctx_reserve_vit(ctx, l.words);
+    rc = soft_reserve(who, ctx, l.tmax, l.words);
     if (rc) return rc;
     hipStream_t s = wf_stream(stream);
     double *base = ctx->d_vit_edge;
@@ -444,11 +376,11 @@ extern "C" int wf_viterbi4_soft_apriori_windows(wf_ctx *ctx, const double *d_row
     WF_LAUNCH_CHECK();
     live_args a;
     a.rows = d_rows;
-    a.pr = soft_prior{d_apriori, apriori_scale, ncalls, (reinterpret_cast<uintptr_t>(d_apriori) & 15) == 0 ? 1 : 0};
+    a.pr = soft_prior_of(d_apriori, apriori_scale, ncalls);
     a.table = d_windows, a.plan = plan;
     a.ch = g.ch, a.warmup = g.warmup, a.tmax = l.tmax;
     a.fedge = base + l.off_f, a.bedge = base + l.off_b, a.alpha = base + l.off_alpha;
-    if (row_bytes == 32)
-        return differential ? live_run<true, 1>(ctx, a, fhdr, bhdr, d_ext, d_bits, s) : live_run<true, 0>(ctx, a, fhdr, bhdr, d_ext, d_bits, s);
-    return differential ? live_run<false, 1>(ctx, a, fhdr, bhdr, d_ext, d_bits, s) : live_run<false, 0>(ctx, a, fhdr, bhdr, d_ext, d_bits, s);
+    return soft_dispatch(row_bytes, differential, [&](auto packed, auto diff) {
+        return live_run<decltype(packed)::value, decltype(diff)::value>(ctx, a, fhdr, bhdr, d_ext, d_bits, s);
+    });
 }

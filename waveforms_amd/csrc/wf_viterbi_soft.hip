@@ -22,59 +22,21 @@
 //   soft_llr_kernel      from the proven b̃ at the chunk end, back over the chunk: λ_k from the stored ã_k, then b̃_k.
 // The result is bitwise the definition whatever `warmup` and the chunking; the warm-up only sets how often the
 // repairs run.
+//
+// This file owns the definition above, the plain kernels and the entry points wf_viterbi4_soft and
+// wf_viterbi4_soft_geometry.  The trellis steps and the walks of the three launches live in wf_viterbi_soft.h, shared with
+// wf_viterbi_soft_apriori.hip and wf_viterbi_live.hip; the kernels here are its AP = false form.  Without a prior no
+// branch's input bit enters the recursions, so only the last launch carries DIFF.
 #include "wf_viterbi_soft.h"
 
 template <bool PACKED>
 __global__ __launch_bounds__(SOFT_THREADS) void soft_bounds_kernel(const double *__restrict__ rows, int64_t n, int ch, int warmup, int64_t nch,
                                                                  double *__restrict__ fedge, double *__restrict__ bedge, double *__restrict__ alpha)
 {
-    if (blockIdx.x == 0 && threadIdx.x < VIT_HDR) {        // lists empty, nobody arrived (both directions)
-        reinterpret_cast<uint64_t *>(fedge + 8 * nch)[threadIdx.x] = 0;
-        reinterpret_cast<uint64_t *>(bedge + 8 * nch)[threadIdx.x] = 0;
-    }
+    soft_burst_clear_lists(fedge, bedge, nch);
     const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
     if (c >= nch) return;
-    const int64_t a = c * ch, e = a + ch < n ? a + ch : n;
-    double m[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t k = a - warmup > 0 ? a - warmup : 0; k < a; ++k) soft_fwd_row<PACKED>(m, rows, k);
-    soft_put4(fedge + 8 * c, m);
-    soft_fwd_chunk<PACKED>(rows, a, e, c, nch, alpha, m);
-    soft_put4(fedge + 8 * c + 4, m);
-
-    double b[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t k = (e + warmup < n ? e + warmup : n) - 1; k >= e; --k) soft_bwd_row<PACKED>(b, rows, k);
-    const int64_t cm = nch - 1 - c;                        // mirrored record index
-    soft_put4(bedge + 8 * cm, b);
-    for (int64_t k = e - 1; k >= a; --k) soft_bwd_row<PACKED>(b, rows, k);
-    soft_put4(bedge + 8 * cm + 4, b);
-}
-
-// Repair of record r (forward: chunk r; backward: chunk nch - 1 - r) by one thread: start from the predecessor
-// record's end as it is now, run the chunk, rewrite the end; true when the end changed.
-template <bool PACKED, bool BWD>
-__device__ __forceinline__ bool soft_rerun(const double *__restrict__ rows, int64_t n, int ch, int64_t nch, double *__restrict__ edge,
-                                           double *__restrict__ alpha, int64_t r)
-{
-    double *rec = edge + 8 * r;
-    double m[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        m[q] = __hip_atomic_load(rec - 4 + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (r >= 1: record 0 is exact)
-        rec[q] = m[q];
-    }
-    const int64_t c = BWD ? nch - 1 - r : r;
-    const int64_t a = c * ch, e = a + ch < n ? a + ch : n;
-    if (BWD)
-        for (int64_t k = e - 1; k >= a; --k) soft_bwd_row<PACKED>(m, rows, k);
-    else
-        soft_fwd_chunk<PACKED>(rows, a, e, c, nch, alpha, m);
-    bool changed = false;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        changed |= __double_as_longlong(rec[4 + q]) != __double_as_longlong(m[q]);
-        rec[4 + q] = m[q];
-    }
-    return changed;
+    soft_bounds_body<PACKED, 0, false>(rows, soft_no_prior{}, soft_burst_chunk(c, ch, n, nch), warmup, fedge, bedge, alpha);
 }
 
 template <bool PACKED, bool BWD>
@@ -82,7 +44,7 @@ __global__ __launch_bounds__(256) void soft_fixup_kernel(const double *__restric
                                                          double *__restrict__ alpha, unsigned long long *__restrict__ unmerged, int mode)
 {
     if (!vit_fixup_verify(edge, nch, unmerged, mode)) return;
-    vit_fixup_rounds(edge, nch, unmerged, [&](int64_t r) { return soft_rerun<PACKED, BWD>(rows, n, ch, nch, edge, alpha, r); });
+    vit_fixup_rounds(edge, nch, unmerged, [&](int64_t r) { return soft_burst_rerun<PACKED, BWD, 0, false>(rows, soft_no_prior{}, n, ch, nch, edge, alpha, r); });
 }
 
 template <bool PACKED, int DIFF>
@@ -92,25 +54,7 @@ __global__ __launch_bounds__(SOFT_THREADS) void soft_llr_kernel(const double *__
 {
     const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
     if (c >= nch) return;
-    const int64_t a = c * ch, e = a + ch < n ? a + ch : n;
-    double b[4], m[4];
-    soft_get4(bedge + 8 * (nch - 1 - c), b);               // b̃_e, proven
-    for (int64_t k = e - 1; k >= a; --k) {
-        soft_get4(alpha + 4 * ((k - a) * nch + c), m);     // ã_k
-        const double2 *z = soft_row<PACKED>(rows, k);
-        double lam;
-        if (k & 1) {
-            const vit_comp q = vit_components<1, PACKED>(z);
-            lam = soft_llr<1, DIFF>(m, b, q);
-            soft_bwd<1>(b, q);
-        } else {
-            const vit_comp q = vit_components<0, PACKED>(z);
-            lam = soft_llr<0, DIFF>(m, b, q);
-            soft_bwd<0>(b, q);
-        }
-        llr[k] = lam;
-        bits[k] = lam < 0.0 ? 1 : 0;
-    }
+    soft_llr_body<PACKED, DIFF, false>(rows, soft_no_prior{}, soft_burst_chunk(c, ch, n, nch), bedge, alpha, llr, bits);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -126,39 +70,22 @@ extern "C" int wf_viterbi4_soft_geometry(wf_ctx *ctx, int64_t ncalls, int warmup
     return WF_OK;
 }
 
-template <bool PACKED>
-static void soft_launch_llr(int diff, unsigned grid, hipStream_t s, const double *rows, int64_t n, const soft_geom &g, const double *bedge,
-                            const double *alpha, double *llr, uint8_t *bits)
-{
-    if (diff)
-        hipLaunchKernelGGL((soft_llr_kernel<PACKED, 1>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, n, g.ch, g.nch, bedge, alpha, llr, bits);
-    else
-        hipLaunchKernelGGL((soft_llr_kernel<PACKED, 0>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, n, g.ch, g.nch, bedge, alpha, llr, bits);
-}
-
-template <bool PACKED>
-static int soft_run(wf_ctx *ctx, const double *rows, int64_t n, int diff, const soft_geom &g, double *llr, uint8_t *bits, hipStream_t s)
+template <bool PACKED, int DIFF>
+static int soft_run(wf_ctx *ctx, const double *rows, int64_t n, const soft_geom &g, double *llr, uint8_t *bits, hipStream_t s)
 {
     double *fedge = ctx->d_vit_edge, *bedge = fedge + g.off_b, *alpha = fedge + g.off_alpha;
     const unsigned grid = (unsigned)((g.nch + SOFT_THREADS - 1) / SOFT_THREADS);
     hipLaunchKernelGGL((soft_bounds_kernel<PACKED>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, n, g.ch, g.warmup, g.nch, fedge, bedge, alpha);
     WF_LAUNCH_CHECK();
     if (g.nch > 1) {
-        // as the hard detectors (wf_viterbi.hip: viterbi_launch): repair, or only count under WF_OPT_DET_REPAIR = 1;
-        // WF_OPT_DET_FINAL_VERIFY adds a counting pass behind the repairs
         const unsigned fgrid = (unsigned)wf_grid_for(g.nch - 1, 256, 1024);
-        const int passes = ctx->opt[WF_OPT_DET_REPAIR] == 0 && ctx->opt[WF_OPT_DET_FINAL_VERIFY] ? 2 : 1;
-        for (int pass = 0; pass < passes; ++pass) {
-            const int mode = pass == 0 && ctx->opt[WF_OPT_DET_REPAIR] == 0 ? 1 : 0;
-            hipLaunchKernelGGL((soft_fixup_kernel<PACKED, false>), dim3(fgrid), dim3(256), 0, s, rows, n, g.ch, fedge, g.nch, alpha,
+        const int rc = soft_fixup_passes(ctx, [&](auto bwd, int mode) {
+            hipLaunchKernelGGL((soft_fixup_kernel<PACKED, decltype(bwd)::value>), dim3(fgrid), dim3(256), 0, s, rows, n, g.ch, bwd ? bedge : fedge, g.nch, alpha,
                                ctx->d_vit_unmerged, mode);
-            WF_LAUNCH_CHECK();
-            hipLaunchKernelGGL((soft_fixup_kernel<PACKED, true>), dim3(fgrid), dim3(256), 0, s, rows, n, g.ch, bedge, g.nch, alpha,
-                               ctx->d_vit_unmerged, mode);
-            WF_LAUNCH_CHECK();
-        }
+        });
+        if (rc) return rc;
     }
-    soft_launch_llr<PACKED>(diff, grid, s, rows, n, g, bedge, alpha, llr, bits);
+    hipLaunchKernelGGL((soft_llr_kernel<PACKED, DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, n, g.ch, g.nch, bedge, alpha, llr, bits);
     WF_LAUNCH_CHECK();
     return WF_OK;
 }
@@ -166,17 +93,15 @@ static int soft_run(wf_ctx *ctx, const double *rows, int64_t n, int diff, const 
 extern "C" int wf_viterbi4_soft(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int row_bytes, int differential, int warmup,
                                 double *d_llr, uint8_t *d_bits, void *stream)
 {
-    WF_REQUIRE(ctx && d_rows && d_llr && d_bits, "wf_viterbi4_soft: NULL argument");
-    WF_REQUIRE(ncalls >= 1 && warmup >= 0, "wf_viterbi4_soft: bad argument");
-    WF_REQUIRE(row_bytes == 32 || row_bytes == 48, "wf_viterbi4_soft: row_bytes must be 32 (packed) or 48 (3 complex128)");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_rows) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_llr) & 7) == 0,
-               "wf_viterbi4_soft: rows must be 16-byte and llr 8-byte aligned");
+    static const char who[] = "wf_viterbi4_soft";
+    int rc = soft_check_args(who, ctx, d_rows, ncalls, row_bytes, warmup, nullptr, 0.0, nullptr, d_llr, d_bits,
+                             "rows must be 16-byte and llr 8-byte aligned");
+    if (rc) return rc;
     const soft_geom g = soft_geometry(ctx, ncalls, warmup);
-    WF_REQUIRE((g.nch + SOFT_THREADS - 1) / SOFT_THREADS < (1ll << 31), "wf_viterbi4_soft: burst too long for one launch");
-    WF_HIP(hipSetDevice(ctx->device));
-    const int rc = wf_ctx_reserve_vit(ctx, g.words);
+    rc = soft_reserve(who, ctx, g.nch, g.words);
     if (rc) return rc;
     hipStream_t s = wf_stream(stream);
-    return row_bytes == 32 ? soft_run<true>(ctx, d_rows, ncalls, differential ? 1 : 0, g, d_llr, d_bits, s)
-                           : soft_run<false>(ctx, d_rows, ncalls, differential ? 1 : 0, g, d_llr, d_bits, s);
+    return soft_dispatch(row_bytes, differential, [&](auto packed, auto diff) {
+        return soft_run<decltype(packed)::value, decltype(diff)::value>(ctx, d_rows, ncalls, g, d_llr, d_bits, s);
+    });
 }
