@@ -712,6 +712,55 @@ int wf_ldpc_decode_ext(wf_ctx *ctx, const wf_ldpc_code *code, const double *d_ll
 int wf_ldpc_count(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_t *d_info_bits, const uint8_t *d_ref_info,
                   const uint8_t *d_state, const int32_t *d_iters, int64_t ncw, int64_t *d_counts, void *stream);
 
+/* ---- Convolutional codes: terminated feed-forward encoder and exact max-log-MAP soft-in / soft-out decoder -----------------
+ * (The reference has no coding layer; these entry points are defined here.)
+ * Code: rate 1 / n_out, constraint length K = 3 .. 7, memory ν = K - 1, S = 2^ν <= 64 states, n_out = 2 .. 4.  The generators
+ * h_gen[j] are K-bit masks whose bit ν (the MSB) taps the current input bit, so octal 171 / 133 read in the usual way.  Every
+ * generator must have bit ν and bit 0 set: then every code bit takes both values on branches of the terminated trellis that lie
+ * on a path, no -inf - (-inf) arises and every output below is finite.  No output is inverted.
+ * Trellis: the message u_0 .. u_{k-1} is followed by ν zero tail bits, T = k + ν steps.  With s_0 = 0, step i has
+ *   reg = (u_i << ν) | s_i,   c_{i,j} = parity(reg & g_j),   s_{i+1} = reg >> 1,
+ * variable v = n_out i + j carries c_{i,j}, N = n_out T <= 32768.  Transmitted position t (0 .. n_tx-1) carries variable
+ * h_tx_var[t]: this one table is the bit interleaver and the puncturing map, exactly as for the LDPC codes (a variable it does
+ * not name is punctured).  Checked on the host before any device memory is touched (WF_ERR_VALUE): K, n_out, the generators'
+ * end taps, k >= 1, N, 1 <= n_tx <= N, tx_var distinct and in range.  The tables are uploaded into device memory the handle
+ * owns (synchronous); wf_conv_code_free releases it (synchronous). */
+typedef struct wf_conv_code wf_conv_code;
+int wf_conv_code_create(wf_ctx *ctx, int32_t K, int32_t n_out, const uint32_t *h_gen, int32_t k, int32_t n_tx, const int32_t *h_tx_var,
+                        wf_conv_code **out);
+int wf_conv_code_free(wf_conv_code *code);
+/* d_info: ncw x k bits (u8 0 / 1) -> d_tx: ncw x n_tx bits in transmit order (codeword b, position t = variable tx_var[t]). */
+int wf_conv_encode(wf_ctx *ctx, const wf_conv_code *code, const uint8_t *d_info, int64_t ncw, uint8_t *d_tx, void *stream);
+/* Max-log-MAP over the whole block (no window), per codeword, in float32 and in exactly this order.  Codeword b's channel value
+ * for transmitted position t is d_llr[b n_tx + t]; d_info_prior (ncw x k float32, or NULL) is the prior A_i of message bit i.
+ * λ, A and the outputs Λ, P, ext all follow one convention: positive favours bit 0.
+ *   L_v = (float)(scale * λ[src v]) (product in float64, then rounded); L_v = 0 for a punctured v; A_i = 0 when the pointer is NULL.
+ *   Branch (s, u) of step i: γ starts as (u ? -A_i : +0); then, for j = 0 .. n_out-1 in this order, γ = γ - L_{n_out i + j} where
+ *   c_{i,j} = 1 on the branch.  Only u = 0 exists for i >= k.
+ *   α_0(0) = 0, every other α_0 = -INFINITY;   α_{i+1}(s') = max over the branches into s' of (α_i(s) + γ)
+ *   β_T(0) = 0, every other β_T = -INFINITY;   β_i(s)     = max over u of (γ + β_{i+1}(s'))
+ *   No normalisation.  Per branch V = (α_i(s) + γ) + β_{i+1}(s').
+ *   Λ_i = max_{u = 0} V - max_{u = 1} V  (i < k);  the information bit is [Λ_i < 0]
+ *   P_v = max_{c_{i,j} = 0} V - max_{c_{i,j} = 1} V
+ *   d_ext[b ext_stride + t] = min(max(P_v - L_v, -ext_clip), +ext_clip), v = tx_var[t]   (a punctured variable has no entry)
+ * A max never meets -0 (α and β start from +0 or -INFINITY, and a sum is -0 only when both operands are), so equal operands are
+ * bitwise equal and the order in which a machine takes a max does not matter; the sums are taken as written.  An
+ * implementation may keep α at checkpoints and recompute it (the same operations on the same operands); it may not window.
+ * Inputs (λ, A) must be finite, with |L| and |A| small enough that no sum overflows: this is not checked on the device.
+ * Outputs (each may be NULL): d_info_bits ncw x k, d_info_post ncw x k (Λ), d_ext as above (ext_stride >= n_tx lets the call
+ * write straight into a burst's prior buffer; ext_clip > 0, INFINITY: no clip).  With d_ref_info (ncw x k bits), d_counts[0..1]
+ * are ADDED: information bit errors, codewords with any.  Asynchronous on `stream`; the checkpoints live in the context's
+ * detector scratch (wf_conv_siso_geometry).  A NULL code / ctx / d_llr, ncw < 1, scale not finite and positive, d_ext with
+ * ext_stride < n_tx or ext_clip not > 0, d_ref_info without d_counts, a misaligned pointer: WF_ERR_VALUE.
+ * Parallelism: a codeword is serial in its T steps (the order above is the definition), so a call has ncw S lanes of work:
+ * lane = state, 64 / S codewords per wave. */
+int wf_conv_siso(wf_ctx *ctx, const wf_conv_code *code, const double *d_llr, int64_t ncw, double scale, const float *d_info_prior,
+                 uint8_t *d_info_bits, float *d_info_post, float *d_ext, int64_t ext_stride, float ext_clip,
+                 const uint8_t *d_ref_info, int64_t *d_counts, void *stream);
+/* What wf_conv_siso launches for ncw codewords: h_geom[0] codewords per wave (64 / S), [1] waves, [2] checkpoint spacing C in
+ * steps, [3] LDS bytes per wave, [4] scratch bytes.  Host only. */
+int wf_conv_siso_geometry(wf_ctx *ctx, const wf_conv_code *code, int64_t ncw, int64_t *h_geom);
+
 /* ---- Framed coded links: attached sync marker, randomiser, soft frame search ------------------------------------------
  * (The reference has no coding or framing layer; these entry points are defined here.)
  * Frame: L marker bits (1 <= L <= 64) followed by the n_tx transmitted bits of one codeword, bit t exclusive-ored with

@@ -4,6 +4,7 @@ decoder's speed; prints ONE JSON line.
     python tools/coded_ber.py [--waveform soqpsk|multih|pcmfm] [--code demo|demo16k] [--ebn0 4 5 6 7 8] [--codewords N]
                               [--detector PT] [--steps 5] [--outer N --inner M --damping D]
                               [--framed [--lead-bits J] [--marker-prior X]] [--live-only [--guard G]]
+    python tools/coded_ber.py --code conv-k3|conv-k7 [--info-bits K] [--interleave] [--outer N --damping D] [--ebn0 ...]
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -32,6 +33,13 @@ codewords open on entry, summed over the blocks), the number of codewords whose 
 and the per-pass detector and decoder times of both loops from the same run: ``--steps`` timed blocks after one warm-up
 block, full and windowed alternating (device events; a windowed detector pass includes the window table, a framed one the
 gather, a framed decoder pass the scatter).
+
+``--code conv-k3`` / ``conv-k7`` (SOQPSK-TG only) is ConvSOQPSKLink (waveforms_amd/encoding/sccc.py) with the (7, 5) or the
+(171, 133) convolutional code of ``--info-bits`` information bits (default: n = 2048) and, with ``--interleave``, the QPP
+interleaver (31 t + 64 t^2) mod n: ``--outer`` passes (0 or 1: one pass with the plain detector) of soft detector and
+max-log-MAP decoder.  Per point: BER / FER (after every pass), the uncoded BER, and the time per block of the encoder, the
+front end and every detector and decoder pass (device events; the same device calls ``run_block`` makes, so with one pass
+the plain detector and a decoder that writes no extrinsic output), with the decoder's information bits per second of one pass.
 """
 import argparse
 import json
@@ -90,10 +98,80 @@ def live_point(full, lv, differ, code, ebn0, first_block, steps, ncw):
             "ms_per_block": ms(1), "full_loop_ms_per_block_same_run": ms(0)}
 
 
+def main_conv(args) -> None:
+    """The ``--code conv-*`` form: ConvSOQPSKLink."""
+    import torch
+
+    from waveforms_amd import device as dev
+    from waveforms_amd.encoding import conv
+    from waveforms_amd.encoding.sccc import ConvSOQPSKLink
+
+    torch.cuda.set_device(0)
+    K = 3 if args.code == "conv-k3" else 7
+    k = args.info_bits or 1024 - (K - 1)
+    n = 2 * (k + K - 1)
+    order = conv.qpp_order(n, 31, 64) if args.interleave else None
+    code = (conv.nasa_k3 if K == 3 else conv.ccsds_k7)(k, tx_order=order)
+    per = args.block_codewords or max(1, int(1e7) // code.n_tx)
+    per = min(per, args.codewords)
+    outer = max(args.outer, 1)
+    link = ConvSOQPSKLink(code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True)
+    out = {"tool": "coded_ber", "code": args.code, "generators": [oct(g) for g in code.generators], "K": code.K, "n": code.n, "k": code.k,
+           "n_tx": code.n_tx, "interleave": bool(args.interleave), "detector": args.detector, "block_codewords": per, "outer": outer,
+           "damping": link.damping, "ext_clip": link.ext_clip, "geometry": dev.conv_siso_geometry(code, per), "points": []}
+    for e in args.ebn0:
+        link.reset_counts()
+        b = 0
+        while b * per < args.codewords:
+            link.run_block(e, seed=1, stream_id=b)
+            b += 1
+        be, fe, m = link.result()
+        ue, um = link.uncoded_result()
+        passes = link.pass_results()
+        ncw = b * per
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3 + 2 * outer)]
+        ms = np.zeros(2 + 2 * outer)
+        for s in range(args.steps + 1):
+            ev[0].record()
+            tx = dev.conv_encode(code, link.info_bits(b + s))
+            ev[1].record()
+            rows, _ = link.front_end(tx, e, 1, b + s)
+            ev[2].record()
+            if outer == 1:                                                # the calls of run_block: plain detector, no ext output
+                llr, _ = link.soft(rows)
+                ev[3].record()
+                dev.conv_siso(code, llr, scale=link.llr_scale, want_post=False, want_ext=False)
+                ev[4].record()
+            else:
+                link.begin(int(rows.shape[0]))
+                for o in range(outer):
+                    ext, _ = link.detect(rows, first=o == 0)
+                    ev[3 + 2 * o].record()
+                    link.decode(ext)
+                    ev[4 + 2 * o].record()
+            torch.cuda.synchronize()
+            if s:                                                         # (the first round warms up)
+                ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(2 + 2 * outer)]
+        ms /= max(args.steps, 1)
+        det, dec = ms[2::2], ms[3::2]
+        out["points"].append({
+            "ebn0_info_db": e, "ebn0_channel_db": round(e + 10 * np.log10(code.k / code.n_tx), 3), "codewords": ncw,
+            "coded_ber": be / m, "fer": fe / ncw, "info_bit_errors": be, "codeword_errors": fe, "uncoded_ber": ue / um,
+            "per_pass": [{"info_bit_errors": p[0], "codeword_errors": p[1]} for p in passes],
+            "ms_per_block": {"encode": round(ms[0], 4), "front_end": round(ms[1], 4), "detector_passes": [round(v, 4) for v in det],
+                             "siso_passes": [round(v, 4) for v in dec], "detector_total": round(float(det.sum()), 4),
+                             "siso_total": round(float(dec.sum()), 4)},
+            "siso_info_gbps": round(per * code.k / (float(dec.mean()) * 1e-3) / 1e9, 4) if dec.mean() > 0 else None,
+        })
+    print(json.dumps(out))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--waveform", default="soqpsk", choices=["soqpsk", "multih", "pcmfm"])
-    ap.add_argument("--code", default="demo", choices=["demo", "demo16k"])
+    ap.add_argument("--code", default="demo", choices=["demo", "demo16k", "conv-k3", "conv-k7"])
+    ap.add_argument("--info-bits", type=int, default=0, help="--code conv-*: information bits per codeword (0: n = 2048)")
+    ap.add_argument("--interleave", action="store_true", help="--code conv-*: QPP interleaver (31 t + 64 t^2) mod n")
     ap.add_argument("--ebn0", type=float, nargs="+", default=[4.0, 5.0, 6.0, 7.0, 8.0])
     ap.add_argument("--codewords", type=int, default=20000)
     ap.add_argument("--block-codewords", type=int, default=0, help="codewords per burst (0: about 1e7 channel bits)")
@@ -112,6 +190,12 @@ def main() -> None:
     args = ap.parse_args()
     if args.live_only and (args.waveform != "soqpsk" or args.outer < 1):
         ap.error("--live-only is the SOQPSK-TG loop's: it needs --waveform soqpsk and --outer N")
+    if args.code.startswith("conv"):
+        if args.waveform != "soqpsk" or args.framed or args.live_only:
+            ap.error("--code conv-* is the SOQPSK-TG link's, unframed and without --live-only")
+        return main_conv(args)
+    if args.info_bits or args.interleave:
+        ap.error("--info-bits and --interleave go with --code conv-k3 / conv-k7")
 
     import torch
 

@@ -109,6 +109,11 @@ SIGNATURES = {
     "wf_ldpc_decode_ext": (c_int, [_P, _P, _P, c_int64, c_double, ctypes.c_float, c_int, _P, _P, _P, _P, _P, c_int64, ctypes.c_float,
                            ctypes.c_float, _P]),
     "wf_ldpc_count": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, _P, _P]),
+    "wf_conv_code_create": (c_int, [_P, ctypes.c_int32, ctypes.c_int32, _P, ctypes.c_int32, ctypes.c_int32, _P, POINTER(c_void_p)]),
+    "wf_conv_code_free": (c_int, [_P]),
+    "wf_conv_encode": (c_int, [_P, _P, _P, c_int64, _P, _P]),
+    "wf_conv_siso": (c_int, [_P, _P, _P, c_int64, c_double, _P, _P, _P, _P, c_int64, ctypes.c_float, _P, _P, _P]),
+    "wf_conv_siso_geometry": (c_int, [_P, _P, c_int64, POINTER(c_int64)]),
     "wf_frame_build": (c_int, [_P, _P, c_int64, ctypes.c_int32, c_uint64, ctypes.c_int32, _P, _P, _P]),
     "wf_frame_search": (c_int, [_P, _P, c_int64, c_uint64, ctypes.c_int32, c_int64, _P, _P, _P]),
     "wf_frame_gather": (c_int, [_P, _P, c_int64, _P, ctypes.c_int32, ctypes.c_int32, _P, c_int64, _P, _P]),
