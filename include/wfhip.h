@@ -761,6 +761,72 @@ int wf_conv_siso(wf_ctx *ctx, const wf_conv_code *code, const double *d_llr, int
  * steps, [3] LDS bytes per wave, [4] scratch bytes.  Host only. */
 int wf_conv_siso_geometry(wf_ctx *ctx, const wf_conv_code *code, int64_t ncw, int64_t *h_geom);
 
+/* ---- Turbo codes: two terminated RSC constituents, an interleaver, and a max-log-MAP decoder of all half-iterations ----------
+ * (The reference has no coding layer; these entry points are defined here.)
+ * Constituent: a recursive systematic convolutional code of constraint length K = 3 .. 5, memory ν = K - 1, S = 2^ν <= 16 states.
+ * The feedback mask fb and the n_par = 1 .. 3 parity generators h_gen[0 .. n_par-1] (g_1 .. g_npar below) are K-bit masks whose
+ * bit ν (the MSB) taps the current register input, so octal 13 / 15 read in the usual way.  Every mask must have bit ν and bit 0
+ * set, and g_j != fb.  With f(s) = parity(s & (fb & (S - 1))), s_0 = 0 and T = k + ν steps:
+ *   i < k:  a_i = u_i ^ f(s_i);      i >= k (the tail):  a_i = 0, so the tail bit sent is u_i = f(s_i) and the register empties;
+ *   reg = (a_i << ν) | s_i,   c_{i,0} = a_i ^ f(s_i) = u_i = parity(reg & fb),   c_{i,j} = parity(reg & g_j),   s_{i+1} = reg >> 1,
+ * m = 1 + n_par outputs per step.
+ * Turbo code: constituent 1 encodes u_0 .. u_{k-1}, constituent 2 encodes u_π(0) .. u_π(k-1), π = h_perm, any bijection of
+ * 0 .. k-1; both are terminated on their own.  Variable v = 2m i + j is output j of constituent 1 at step i, v = 2m i + m + j
+ * output j of constituent 2, N = 2m T <= 32768.  Transmitted position t (0 .. n_tx-1) carries variable h_tx_var[t]: this one
+ * table is the puncturing map and the channel interleaver, exactly as for the other codes.  (The usual choice sends every
+ * variable except constituent 2's systematic output at the steps i < k.)  Checked on the host before any device memory is
+ * touched (WF_ERR_VALUE): K, n_par, the masks' end taps, g_j != fb, k >= 1, N, π a bijection, 1 <= n_tx <= N, tx_var distinct
+ * and in range.  π, its inverse, var -> src and tx_var are uploaded into device memory the handle owns (synchronous);
+ * wf_turbo_code_free releases it (synchronous). */
+typedef struct wf_turbo_code wf_turbo_code;
+int wf_turbo_code_create(wf_ctx *ctx, int32_t K, int32_t n_par, uint32_t fb, const uint32_t *h_gen, int32_t k, const int32_t *h_perm,
+                         int32_t n_tx, const int32_t *h_tx_var, wf_turbo_code **out);
+int wf_turbo_code_free(wf_turbo_code *code);
+/* d_info: ncw x k bits (u8 0 / 1) -> d_tx: ncw x n_tx bits in transmit order (codeword b, position t = variable tx_var[t]). */
+int wf_turbo_encode(wf_ctx *ctx, const wf_turbo_code *code, const uint8_t *d_info, int64_t ncw, uint8_t *d_tx, void *stream);
+/* The turbo decoder: half_iters = H (1 .. 64) max-log-MAP half-iterations per codeword in ONE call, in float32 and in exactly
+ * this order.  Positive favours bit 0 everywhere.
+ * Channel values: L_v = (float)(scale * λ[src v]) (product in float64, then rounded), L_v = 0 for a punctured v.  Ls1_i is L of
+ * constituent 1's systematic variable at step i.  For i < k constituent 2's systematic value is Ls2_i = Ls1_π(i): it is COPIED,
+ * whether or not constituent 2's own systematic variable is transmitted, and if that variable is transmitted its own L is
+ * ignored by the decoding for i < k (it is only subtracted in that variable's own d_ext entry).  For i >= k each constituent
+ * uses its own tail values.
+ * SISO(c, A) of constituent c with the prior A_0 .. A_{k-1}: γ of branch (s, a) at step i starts as (u ? -A_i : +0) with
+ * u = a ^ f(s) for i < k, and as +0 for i >= k; then, for j = 0 .. m-1 in this order, γ = γ - L_{c,i,j} where the branch's code
+ * bit j is 1.  α, β, their boundary values and "no normalisation" are wf_conv_siso's, with only a = 0 for i >= k:
+ *   α_0(0) = 0, every other α_0 = -INFINITY;   α_{i+1}(s') = max over the branches into s' of (α_i(s) + γ)
+ *   β_T(0) = 0, every other β_T = -INFINITY;   β_i(s)     = max over a of (γ + β_{i+1}(s'))
+ *   V = (α_i(s) + γ) + β_{i+1}(s');   P_{i,j} = max_{c_j = 0} V - max_{c_j = 1} V;   Λ_i = max_{u = 0} V - max_{u = 1} V = P_{i,0}  (i < k)
+ * (Λ groups the branches by u, not by a.)  Every P is finite except that of a tail bit which is 0 in every codeword (k < ν
+ * only): that one is +INFINITY.
+ * Half-iterations h = 1 .. H.  Before the first, A1 = 0, or d_a1 (ncw x k float32, in and out) when given.
+ *   odd h:   Λ1 = SISO(1, A1);  E1_i = ext_scale * ((Λ1_i - A1_i) - Ls1_i), the two subtractions and the product each rounded to
+ *            float32;  A2_i = E1_π(i).
+ *   even h:  Λ2 = SISO(2, A2);  E2_i = ext_scale * ((Λ2_i - A2_i) - Ls2_i);  A1_π(i) = E2_i.
+ * Decision after an odd last half-iteration: x̂_i = [Λ1_i < 0] and post_i = Λ1_i; after an even one x̂_π(i) = [Λ2_i < 0] and
+ * post_π(i) = Λ2_i.
+ * Stop rule (early_stop != 0): after an even h, a codeword with [Λ2_i < 0] == [Λ1_π(i) < 0] for all i stops, iters = h / 2.  A
+ * stopped codeword is never updated again: its outputs (d_a1 included) are those of its stopping half-iteration.  Otherwise
+ * iters = ceil(H / 2).
+ * d_ext[b ext_stride + t] (H even only), at the codeword's last half-iteration, v = tx_var[t]: for constituent 1's systematic
+ * variable at i < k, X = (Λ2 deinterleaved)_i - Ls1_i; for every other variable X = P_{i,j} - L_v from the last SISO of its
+ * constituent; the entry is min(max(X, -ext_clip), +ext_clip).  A punctured variable has no entry; ext_stride >= n_tx lets the
+ * call write straight into a burst's prior buffer.
+ * Outputs (each may be NULL): d_info_bits ncw x k, d_info_post ncw x k, d_iters ncw (int32), d_ext, d_a1 (A1 as the last
+ * half-iteration left it).  With d_ref_info (ncw x k bits), d_counts[0..2] are ADDED: information bit errors, codewords with any,
+ * half-iterations run summed over the codewords.  Inputs must be finite and small enough that no sum overflows (not checked on
+ * the device).  A NULL code / ctx / d_llr, ncw < 1, scale or ext_scale not finite and positive, H outside 1 .. 64, d_ext with an
+ * odd H, ext_stride < n_tx or ext_clip not > 0, d_ref_info without d_counts, a misaligned pointer, a code of another device:
+ * WF_ERR_VALUE.  Asynchronous on `stream`, one launch for all half-iterations (several only for a batch whose scratch would
+ * pass the cap): lane = state, 64 / S codewords per wave in lockstep; A1, A2, constituent 1's decisions and the α checkpoints
+ * live in the context's detector scratch (wf_turbo_decode_geometry), nothing synchronises with the host. */
+int wf_turbo_decode(wf_ctx *ctx, const wf_turbo_code *code, const double *d_llr, int64_t ncw, double scale, float ext_scale,
+                    int32_t half_iters, int32_t early_stop, float *d_a1, uint8_t *d_info_bits, float *d_info_post, int32_t *d_iters,
+                    float *d_ext, int64_t ext_stride, float ext_clip, const uint8_t *d_ref_info, int64_t *d_counts, void *stream);
+/* What wf_turbo_decode launches for ncw codewords: h_geom[0] codewords per wave (64 / S), [1] waves, [2] checkpoint spacing C in
+ * steps, [3] LDS bytes per wave, [4] scratch bytes.  Host only. */
+int wf_turbo_decode_geometry(wf_ctx *ctx, const wf_turbo_code *code, int64_t ncw, int64_t *h_geom);
+
 /* ---- Framed coded links: attached sync marker, randomiser, soft frame search ------------------------------------------
  * (The reference has no coding or framing layer; these entry points are defined here.)
  * Frame: L marker bits (1 <= L <= 64) followed by the n_tx transmitted bits of one codeword, bit t exclusive-ored with

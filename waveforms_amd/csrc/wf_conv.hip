@@ -14,16 +14,13 @@
 //                   DPP butterfly (quad_perm, row_half_mirror, row_mirror inside a row of 16; ds_bpermute across rows).
 // The channel values of a segment, its priors, reference bits and var -> src entries are staged in LDS by all lanes before
 // the segment's serial loop, so that loop holds no load from global memory.
-#include "wf_common.h"
+#include "wf_conv_common.h"
 
 #include <algorithm>
 #include <cmath>
 
-#define CONV_MAX_N 32768
-#define CONV_C 32                   // checkpoint spacing = steps per segment
 #define CONV_ENC_RUN 8              // steps per encoder thread
 #define CONV_ENC_THREADS 256
-#define CONV_SCRATCH_CAP (128ll << 20)   // checkpoint bytes one launch may use
 
 struct wf_conv_code {
     int device = 0;
@@ -107,41 +104,6 @@ struct conv_siso_args {
     int32_t k, T, n_tx, nseg;
     uint32_t gen[4];
 };
-
-// gamma of one branch: start (u ? -A : +0), then minus L_j where the branch's code bit j is 1, j increasing.  (x - (+0) is x
-// for every x, -0 included, so +0 stands for "no subtraction".)  c[j]: all ones where the code bit is 1, else 0: L_j & c[j] is
-// L_j or +0 in one instruction, and the branch's bits live in vector registers instead of one lane mask each.
-template <int NOUT>
-__device__ __forceinline__ float conv_gamma(float start, const float (&L)[NOUT], const uint32_t (&c)[NOUT])
-{
-    float g = start;
-#pragma unroll
-    for (int j = 0; j < NOUT; ++j) g = __fsub_rn(g, __uint_as_float(__float_as_uint(L[j]) & c[j]));
-    return g;
-}
-
-// c ? -INFINITY : v and c ? v : -INFINITY for a mask c of all ones / all zeros (one v_bfi_b32 each)
-__device__ __forceinline__ float conv_drop_if(uint32_t c, float v) { return __uint_as_float((c & 0xFF800000u) | (~c & __float_as_uint(v))); }
-__device__ __forceinline__ float conv_keep_if(uint32_t c, float v) { return __uint_as_float((c & __float_as_uint(v)) | (~c & 0xFF800000u)); }
-
-template <int CTRL>
-__device__ __forceinline__ float conv_dpp(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
-}
-
-// max over the S lanes of a codeword, in every one of them (the operands are never -0 and never NaN: the order is free)
-template <int S>
-__device__ __forceinline__ float conv_group_max(float v)
-{
-    if constexpr (S >= 2) v = fmaxf(v, conv_dpp<0xB1>(v));         // quad_perm [1, 0, 3, 2]
-    if constexpr (S >= 4) v = fmaxf(v, conv_dpp<0x4E>(v));         // quad_perm [2, 3, 0, 1]
-    if constexpr (S >= 8) v = fmaxf(v, conv_dpp<0x141>(v));        // row_half_mirror: the other quad of the 8
-    if constexpr (S >= 16) v = fmaxf(v, conv_dpp<0x140>(v));       // row_mirror: the other 8 of the row
-    if constexpr (S >= 32) v = fmaxf(v, __shfl_xor(v, 16, WF_WAVE));
-    if constexpr (S >= 64) v = fmaxf(v, __shfl_xor(v, 32, WF_WAVE));
-    return v;
-}
 
 template <int NU, int NOUT>
 __global__ __launch_bounds__(WF_WAVE) void conv_siso_kernel(conv_siso_args a)

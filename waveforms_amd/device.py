@@ -579,6 +579,73 @@ def conv_siso_geometry(code, ncw: int) -> dict:
     return dict(zip(("codewords_per_wave", "waves", "checkpoint_steps", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
 
 
+def turbo_encode(code, d_info):
+    """Turbo encoder (``wf_turbo_encode``): device messages (ncw x k bits, u8) -> transmitted bits (ncw x n_tx, u8) in transmit
+    order.  ``code``: a :class:`waveforms_amd.encoding.turbo.TurboCode`."""
+    if not d_info.is_contiguous() or d_info.numel() % code.k or d_info.numel() == 0:
+        raise ValueError(f"messages must be a contiguous whole number of k = {code.k} bits")
+    ncw = d_info.numel() // code.k
+    out = _hip.empty((ncw, code.n_tx), "uint8")
+    _hip.check(_hip.lib().wf_turbo_encode(_hip.ctx(), code.handle(), _hip.ptr(d_info), ncw, _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def turbo_decode(code, d_llr, half_iters: int = 12, scale: float = 1.0, ext_scale: float = 0.75, early_stop: bool = True, a1=None,
+                 want_a1: bool = False, ext=None, ext_stride: int | None = None, ext_clip: float = float("inf"), ref_info=None, counts=None,
+                 want_bits: bool = True, want_post: bool = True, want_iters: bool = True, want_ext: bool = False) -> dict:
+    """Max-log-MAP turbo decoding (``wf_turbo_decode``; include/wfhip.h states the definition): ``half_iters`` half-iterations
+    of ncw codewords in ONE launch.  ``d_llr`` contiguous float64, codeword b's λ for transmitted position t at [b n_tx + t],
+    λ > 0 favouring bit 0.  ``a1``: device float32 ncw x k, constituent 1's prior, read AND left as the last half-iteration
+    made it (None: the prior starts as 0; ``want_a1`` then hands a fresh one back).  ``ext``: a device float32 tensor (or a
+    view into a prior buffer) that receives codeword b's extrinsic values at [b ext_stride + t] (``half_iters`` even only);
+    None: a fresh ncw x n_tx one when ``want_ext``.  Returns {"info_bits": u8 ncw x k, "info_post": float32 ncw x k, "iters":
+    int32 ncw, "a1", "ext", "counts"}, None for what was not asked for.  With ``ref_info`` (device ncw x k bits) the decoder
+    ADDS to ``counts`` (int64[3], fresh zeros if None): information bit errors, codewords with any, half-iterations run."""
+    torch = _hip.torch()
+    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
+        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
+    ncw = d_llr.numel() // code.n_tx
+    half_iters = int(half_iters)
+    if not 1 <= half_iters <= 64:
+        raise ValueError("half_iters must be 1 .. 64")
+    stride = code.n_tx if ext_stride is None else int(ext_stride)
+    if stride < code.n_tx:
+        raise ValueError(f"ext_stride {stride} is below n_tx = {code.n_tx}")
+    if not float(ext_clip) > 0.0:
+        raise ValueError("ext_clip must be positive")
+    if (ext is not None or want_ext) and half_iters % 2:
+        raise ValueError("the extrinsic output needs an even half_iters")
+    if a1 is not None and (a1.dtype != torch.float32 or not a1.is_contiguous() or a1.numel() != ncw * code.k):
+        raise ValueError("a1 must hold ncw x k contiguous float32 values")
+    if a1 is None and want_a1:
+        a1 = torch.zeros((ncw, code.k), dtype=torch.float32, device="cuda")
+    if ext is None:
+        if want_ext:
+            ext = torch.zeros((ncw, stride), dtype=torch.float32, device="cuda")
+    elif ext.dtype != torch.float32 or not ext.is_contiguous() or ext.numel() < (ncw - 1) * stride + code.n_tx:
+        raise ValueError("ext must be contiguous float32 with room for (ncw - 1) ext_stride + n_tx values")
+    if ref_info is not None:
+        if ref_info.numel() != ncw * code.k or not ref_info.is_contiguous():
+            raise ValueError("ref_info must hold ncw x k contiguous bits")
+        if counts is None:
+            counts = _hip.zeros(3, "int64")
+    bits = _hip.empty((ncw, code.k), "uint8") if want_bits else None
+    post = torch.empty((ncw, code.k), dtype=torch.float32, device="cuda") if want_post else None
+    iters = torch.empty(ncw, dtype=torch.int32, device="cuda") if want_iters else None
+    _hip.check(_hip.lib().wf_turbo_decode(_hip.ctx(), code.handle(), _hip.ptr(d_llr), ncw, float(scale), float(ext_scale), half_iters,
+                                          1 if early_stop else 0, _hip.ptr(a1), _hip.ptr(bits), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ext),
+                                          stride, float(ext_clip), _hip.ptr(ref_info), _hip.ptr(counts) if ref_info is not None else None,
+                                          _hip.stream()))
+    return {"info_bits": bits, "info_post": post, "iters": iters, "a1": a1, "ext": ext, "counts": counts if ref_info is not None else None}
+
+
+def turbo_decode_geometry(code, ncw: int) -> dict:
+    """What ``turbo_decode`` launches for ``ncw`` codewords (``wf_turbo_decode_geometry``)."""
+    g = (ctypes.c_int64 * 5)()
+    _hip.check(_hip.lib().wf_turbo_decode_geometry(_hip.ctx(), code.handle(), int(ncw), g))
+    return dict(zip(("codewords_per_wave", "waves", "checkpoint_steps", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
+
+
 def _frame_pn(pn, n_tx: int):
     torch = _hip.torch()
     if pn is not None and (pn.dtype != torch.uint8 or pn.numel() != n_tx or not pn.is_contiguous()):
