@@ -827,6 +827,49 @@ int wf_turbo_decode(wf_ctx *ctx, const wf_turbo_code *code, const double *d_llr,
  * steps, [3] LDS bytes per wave, [4] scratch bytes.  Host only. */
 int wf_turbo_decode_geometry(wf_ctx *ctx, const wf_turbo_code *code, int64_t ncw, int64_t *h_geom);
 
+/* ---- Reed-Solomon codes over GF(2^8): systematic encoder and bounded-distance errors-only decoder, symbol-interleaved ----------
+ * (The reference has no coding layer; these entry points are defined here.)
+ * Field: GF(2^8) = GF(2)[x] / prim(x), prim a 9-bit mask (bit 8 set; CCSDS: 0x187); a symbol is a byte whose bit i is the
+ * coefficient of x^i, α is the class of x.  prim must be primitive: α has period 255.
+ * Code: RS(n, k), 2t = n - k, t = 1 .. 16, n <= 255, k >= 1.  With β = α^step, gcd(step, 255) = 1, 1 <= step <= 254, and
+ * 0 <= fcr <= 254, the generator is g(x) = Π_{i=0}^{2t-1} (x - β^(fcr+i)).  CCSDS (255, 223): step 11, fcr 112; CCSDS (255, 239):
+ * step 11, fcr 120 (both generators are palindromic; their x^1 coefficients are 91 and 165).  The conventional code: prim 0x11d,
+ * fcr 0, step 1.  n < 255 is the shortened code: 255 - n leading message symbols are zero and are never sent.
+ * Codeword: c_0 .. c_{n-1}, c_0 sent first; as a polynomial c(x) = Σ c_i x^(n-1-i), so c_0 is the highest coefficient.  Encoding
+ * is systematic: c_0 .. c_{k-1} are the message, c_k .. c_{n-1} the remainder of m(x) x^(2t) by g(x), highest coefficient first.
+ * A word is a codeword exactly when its syndromes S_j = r(β^(fcr+j)), j = 0 .. 2t-1, are all zero.
+ * Interleaving to depth I = 1 .. 8: a frame is n I transmitted symbols; the symbol at position p belongs to codeword p mod I
+ * at index p div I.  A message frame is k I symbols laid out the same way.  Codeword b I + c is codeword c of frame b.
+ * Bit form: bits = 0: one symbol per byte; bits = 1: one bit per byte (u8 0 / 1, only bit 0 is read), eight per symbol, most
+ * significant bit first (the form wf_conv_encode reads and wf_conv_siso writes).
+ * Checked on the host before the context or any device memory is touched (WF_ERR_VALUE): prim of degree 8 and primitive,
+ * gcd(step, 255) = 1, and every range above.  The field tables are uploaded into device memory the handle owns (synchronous);
+ * wf_rs_code_free releases it (synchronous). */
+typedef struct wf_rs_code wf_rs_code;
+int wf_rs_code_create(wf_ctx *ctx, int32_t prim, int32_t fcr, int32_t step, int32_t n, int32_t k, int32_t depth, wf_rs_code **out);
+int wf_rs_code_free(wf_rs_code *code);
+/* d_msg: nframes message frames (k I symbols each) -> d_tx: nframes frames (n I symbols each), both in the bit form `bits`.
+ * The buffers must not overlap.  NULL pointer, nframes < 1, bits outside {0, 1}: WF_ERR_VALUE.  Asynchronous on `stream`. */
+int wf_rs_encode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_msg, int64_t nframes, int32_t bits, uint8_t *d_tx, void *stream);
+/* The decoder's result is defined by its outcome, not by an algorithm.  For each received word r of the (possibly shortened)
+ * code, errors only:
+ *   if a codeword c of that code lies within Hamming distance t of r, counted in symbols, it is unique: the output is c's
+ *   message and status = d(r, c) = 0 .. t;  otherwise the output is r's own message symbols unchanged and status = -1.
+ * (So a locator with a root at one of the 255 - n virtual positions is a failure, as is a locator of degree above t or one whose
+ * number of roots among the n positions differs from its degree.)  Erasures are not supported.
+ * d_rx: nframes frames -> d_msg_out: nframes message frames, d_status (int32 per codeword, b I + c; may be NULL).  With d_ref_msg
+ * (nframes message frames) these are ADDED to d_counts[0..4] (int64): [0] message bit errors after decoding, [1] codewords
+ * wrong after decoding, [2] codewords with status -1, [3] symbols corrected summed over the successful codewords, [4] frames
+ * with any wrong codeword.  Miscorrections are [1] - [2].  d_msg_out must not overlap d_rx (a frame's message lies where other
+ * workgroups may still be reading their input) or d_ref_msg.  NULL ctx / code / d_rx / d_msg_out, nframes < 1, d_ref_msg without
+ * d_counts, bits outside {0, 1}, a misaligned d_status or d_counts: WF_ERR_VALUE.  Asynchronous on `stream`; nothing
+ * synchronises with the host.  One workgroup per frame, one wave per codeword (wf_rs_decode_geometry). */
+int wf_rs_decode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, int64_t nframes, int32_t bits, uint8_t *d_msg_out,
+                 int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream);
+/* What wf_rs_decode launches for nframes frames: h_geom[0] waves (codewords) per workgroup = I, [1] workgroups, [2] launches,
+ * [3] LDS bytes per workgroup, [4] threads per workgroup (64 I).  Host only. */
+int wf_rs_decode_geometry(wf_ctx *ctx, const wf_rs_code *code, int64_t nframes, int64_t *h_geom);
+
 /* ---- Framed coded links: attached sync marker, randomiser, soft frame search ------------------------------------------
  * (The reference has no coding or framing layer; these entry points are defined here.)
  * Frame: L marker bits (1 <= L <= 64) followed by the n_tx transmitted bits of one codeword, bit t exclusive-ored with

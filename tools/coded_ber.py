@@ -5,6 +5,7 @@ decoder's speed; prints ONE JSON line.
                               [--detector PT] [--steps 5] [--outer N --inner M --damping D]
                               [--framed [--lead-bits J] [--marker-prior X]] [--live-only [--guard G]]
     python tools/coded_ber.py --code conv-k3|conv-k7 [--info-bits K] [--interleave] [--outer N --damping D] [--ebn0 ...]
+    python tools/coded_ber.py --code conv-k3|conv-k7 --rs 16|8 [--rs-depth I] [--rs-n N] ...
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -40,6 +41,13 @@ interleaver (31 t + 64 t^2) mod n: ``--outer`` passes (0 or 1: one pass with the
 max-log-MAP decoder.  Per point: BER / FER (after every pass), the uncoded BER, and the time per block of the encoder, the
 front end and every detector and decoder pass (device events; the same device calls ``run_block`` makes, so with one pass
 the plain detector and a decoder that writes no extrinsic output), with the decoder's information bits per second of one pass.
+
+With ``--rs E`` the link is RSConvSOQPSKLink (waveforms_amd/encoding/rsconv.py): the CCSDS Reed-Solomon code correcting E = 16 or 8
+symbols (``--rs-n``: shortened), interleaved to ``--rs-depth``, in front of the convolutional code, whose ``--info-bits`` are then
+fixed at one RS frame (8 n I).  Eb/N0 is per USER bit.  Every point gains an ``"rs"`` entry: BER and FER after the RS decoder
+next to the inner code's, flagged failures, miscorrections, symbols corrected, and the time per block of ``rs_encode`` and of
+``rs_decode`` (device events around those two calls alone, the same ``--steps`` blocks) with its ratio to the ``conv_siso`` passes
+of the block.  Without ``--rs`` the output is unchanged.
 """
 import argparse
 import json
@@ -108,6 +116,15 @@ def main_conv(args) -> None:
 
     torch.cuda.set_device(0)
     K = 3 if args.code == "conv-k3" else 7
+    rs = None
+    if args.rs:
+        from waveforms_amd.encoding.rs import RSCode
+        from waveforms_amd.encoding.rsconv import RSConvSOQPSKLink
+
+        rs = RSCode.ccsds(args.rs, args.rs_depth, args.rs_n)
+        if args.info_bits and args.info_bits != 8 * rs.n * rs.depth:
+            raise SystemExit(f"--rs fixes --info-bits at one RS frame: {8 * rs.n * rs.depth}")
+        args.info_bits = 8 * rs.n * rs.depth
     k = args.info_bits or 1024 - (K - 1)
     n = 2 * (k + K - 1)
     order = conv.qpp_order(n, 31, 64) if args.interleave else None
@@ -115,10 +132,17 @@ def main_conv(args) -> None:
     per = args.block_codewords or max(1, int(1e7) // code.n_tx)
     per = min(per, args.codewords)
     outer = max(args.outer, 1)
-    link = ConvSOQPSKLink(code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True)
+    if rs is None:
+        link = ConvSOQPSKLink(code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True)
+    else:
+        link = RSConvSOQPSKLink(rs, code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True)
     out = {"tool": "coded_ber", "code": args.code, "generators": [oct(g) for g in code.generators], "K": code.K, "n": code.n, "k": code.k,
            "n_tx": code.n_tx, "interleave": bool(args.interleave), "detector": args.detector, "block_codewords": per, "outer": outer,
            "damping": link.damping, "ext_clip": link.ext_clip, "geometry": dev.conv_siso_geometry(code, per), "points": []}
+    if rs is not None:
+        out["rs"] = {"n": rs.n, "k": rs.k, "t": rs.t, "depth": rs.depth, "prim": hex(rs.prim), "fcr": rs.fcr, "step": rs.step,
+                     "user_bits_per_block": link.user_bits_per_block, "geometry": dev.rs_decode_geometry(rs, per)}
+    rs_scratch = torch.zeros(5, dtype=torch.int64, device="cuda") if rs is not None else None
     for e in args.ebn0:
         link.reset_counts()
         b = 0
@@ -129,11 +153,18 @@ def main_conv(args) -> None:
         ue, um = link.uncoded_result()
         passes = link.pass_results()
         ncw = b * per
+        rs_counts = link.rs_result() if rs is not None else None
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3 + 2 * outer)]
-        ms = np.zeros(2 + 2 * outer)
+        rev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        ms, rs_ms = np.zeros(2 + 2 * outer), np.zeros(2)
         for s in range(args.steps + 1):
+            if rs is not None:                                            # (the RS encoder alone, in front of the block: what info_bits does)
+                link.user = link.user_bits(b + s)
+                rev[0].record()
+                info = dev.rs_encode(rs, link.user, bits=True).view(-1)
+                rev[1].record()
             ev[0].record()
-            tx = dev.conv_encode(code, link.info_bits(b + s))
+            tx = dev.conv_encode(code, info if rs is not None else link.info_bits(b + s))
             ev[1].record()
             rows, _ = link.front_end(tx, e, 1, b + s)
             ev[2].record()
@@ -149,10 +180,18 @@ def main_conv(args) -> None:
                     ev[3 + 2 * o].record()
                     link.decode(ext)
                     ev[4 + 2 * o].record()
+            if rs is not None:                                            # the call run_block makes on the block's decisions
+                decided = link.decided if outer > 1 else dev.conv_siso(code, llr, scale=link.llr_scale, want_post=False, want_ext=False)["info_bits"]
+                rev[2].record()
+                dev.rs_decode(rs, decided, bits=True, ref_msg=link.user, counts=rs_scratch)
+                rev[3].record()
             torch.cuda.synchronize()
             if s:                                                         # (the first round warms up)
                 ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(2 + 2 * outer)]
+                if rs is not None:
+                    rs_ms += [rev[0].elapsed_time(rev[1]), rev[2].elapsed_time(rev[3])]
         ms /= max(args.steps, 1)
+        rs_ms /= max(args.steps, 1)
         det, dec = ms[2::2], ms[3::2]
         out["points"].append({
             "ebn0_info_db": e, "ebn0_channel_db": round(e + 10 * np.log10(code.k / code.n_tx), 3), "codewords": ncw,
@@ -163,6 +202,14 @@ def main_conv(args) -> None:
                              "siso_total": round(float(dec.sum()), 4)},
             "siso_info_gbps": round(per * code.k / (float(dec.mean()) * 1e-3) / 1e9, 4) if dec.mean() > 0 else None,
         })
+        if rs is not None:
+            rbe, rce, rfl, rcor, rfe, rm = rs_counts
+            out["points"][-1]["ebn0_channel_db"] = round(e + link._rate_db(), 3)
+            out["points"][-1]["rs"] = {
+                "user_ber": rbe / rm, "fer": rfe / ncw, "user_bit_errors": rbe, "user_bits": rm, "codeword_errors": rce, "codewords": ncw * rs.depth,
+                "frame_errors": rfe, "flagged_failures": rfl, "miscorrections": rce - rfl, "symbols_corrected": rcor,
+                "ms_per_block": {"rs_encode": round(rs_ms[0], 4), "rs_decode": round(rs_ms[1], 4)},
+                "rs_decode_over_siso": round(float(rs_ms[1] / dec.sum()), 5) if dec.sum() > 0 else None}
     print(json.dumps(out))
 
 
@@ -172,6 +219,9 @@ def main() -> None:
     ap.add_argument("--code", default="demo", choices=["demo", "demo16k", "conv-k3", "conv-k7"])
     ap.add_argument("--info-bits", type=int, default=0, help="--code conv-*: information bits per codeword (0: n = 2048)")
     ap.add_argument("--interleave", action="store_true", help="--code conv-*: QPP interleaver (31 t + 64 t^2) mod n")
+    ap.add_argument("--rs", type=int, default=0, choices=[0, 8, 16], help="--code conv-*: CCSDS Reed-Solomon outer code correcting E symbols")
+    ap.add_argument("--rs-depth", type=int, default=1, help="--rs: symbol interleaving depth 1 .. 8")
+    ap.add_argument("--rs-n", type=int, default=255, help="--rs: shortened code length")
     ap.add_argument("--ebn0", type=float, nargs="+", default=[4.0, 5.0, 6.0, 7.0, 8.0])
     ap.add_argument("--codewords", type=int, default=20000)
     ap.add_argument("--block-codewords", type=int, default=0, help="codewords per burst (0: about 1e7 channel bits)")
@@ -194,8 +244,8 @@ def main() -> None:
         if args.waveform != "soqpsk" or args.framed or args.live_only:
             ap.error("--code conv-* is the SOQPSK-TG link's, unframed and without --live-only")
         return main_conv(args)
-    if args.info_bits or args.interleave:
-        ap.error("--info-bits and --interleave go with --code conv-k3 / conv-k7")
+    if args.info_bits or args.interleave or args.rs:
+        ap.error("--info-bits, --interleave and --rs go with --code conv-k3 / conv-k7")
 
     import torch
 

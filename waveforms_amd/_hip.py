@@ -119,6 +119,11 @@ SIGNATURES = {
     "wf_turbo_encode": (c_int, [_P, _P, _P, c_int64, _P, _P]),
     "wf_turbo_decode": (c_int, [_P, _P, _P, c_int64, c_double, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _P, _P, _P, _P, _P, c_int64, ctypes.c_float, _P, _P, _P]),
     "wf_turbo_decode_geometry": (c_int, [_P, _P, c_int64, POINTER(c_int64)]),
+    "wf_rs_code_create": (c_int, [_P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, POINTER(c_void_p)]),
+    "wf_rs_code_free": (c_int, [_P]),
+    "wf_rs_encode": (c_int, [_P, _P, _P, c_int64, ctypes.c_int32, _P, _P]),
+    "wf_rs_decode": (c_int, [_P, _P, _P, c_int64, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    "wf_rs_decode_geometry": (c_int, [_P, _P, c_int64, POINTER(c_int64)]),
     "wf_frame_build": (c_int, [_P, _P, c_int64, ctypes.c_int32, c_uint64, ctypes.c_int32, _P, _P, _P]),
     "wf_frame_search": (c_int, [_P, _P, c_int64, c_uint64, ctypes.c_int32, c_int64, _P, _P, _P]),
     "wf_frame_gather": (c_int, [_P, _P, c_int64, _P, ctypes.c_int32, ctypes.c_int32, _P, c_int64, _P, _P]),

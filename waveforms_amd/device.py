@@ -646,6 +646,47 @@ def turbo_decode_geometry(code, ncw: int) -> dict:
     return dict(zip(("codewords_per_wave", "waves", "checkpoint_steps", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
 
 
+def _rs_frames(code, x, per: int, bits: bool, what: str) -> int:
+    unit = (8 if bits else 1) * per * code.depth
+    if x.dtype != _hip.torch().uint8 or not x.is_contiguous() or x.numel() % unit or x.numel() == 0:
+        raise ValueError(f"{what} must be contiguous uint8, a whole number of frames of {unit} bytes")
+    return x.numel() // unit
+
+
+def rs_encode(code, d_msg, bits: bool = False):
+    """Reed-Solomon encoder (``wf_rs_encode``): device message frames (F x k I symbols; with ``bits`` one bit per byte, MSB
+    first) -> frames (F x n I) in the same form.  ``code``: a :class:`waveforms_amd.encoding.rs.RSCode`."""
+    nf = _rs_frames(code, d_msg, code.k, bits, "messages")
+    out = _hip.empty((nf, (8 if bits else 1) * code.n * code.depth), "uint8")
+    _hip.check(_hip.lib().wf_rs_encode(_hip.ctx(), code.handle(), _hip.ptr(d_msg), nf, int(bool(bits)), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def rs_decode(code, d_rx, bits: bool = False, ref_msg=None, counts=None, want_status: bool = True) -> dict:
+    """Bounded-distance Reed-Solomon decoding (``wf_rs_decode``; include/wfhip.h states the result) of F frames (F x n I
+    symbols, or bits) -> {"msg": F x k I in the same form, "status": int32 F I (symbols corrected, -1 = failure), "counts"}.
+    With ``ref_msg`` (device message frames) the decoder ADDS to ``counts`` (int64[5], fresh zeros if None): message bit errors,
+    codewords wrong, codewords flagged, symbols corrected, frames with a wrong codeword."""
+    nf = _rs_frames(code, d_rx, code.n, bits, "frames")
+    if ref_msg is not None:
+        if _rs_frames(code, ref_msg, code.k, bits, "ref_msg") != nf:
+            raise ValueError("ref_msg must hold as many message frames as there are frames")
+        if counts is None:
+            counts = _hip.zeros(5, "int64")
+    out = _hip.empty((nf, (8 if bits else 1) * code.k * code.depth), "uint8")
+    status = _hip.empty(nf * code.depth, "int32") if want_status else None
+    _hip.check(_hip.lib().wf_rs_decode(_hip.ctx(), code.handle(), _hip.ptr(d_rx), nf, int(bool(bits)), _hip.ptr(out), _hip.ptr(status),
+                                       _hip.ptr(ref_msg), _hip.ptr(counts) if ref_msg is not None else None, _hip.stream()))
+    return {"msg": out, "status": status, "counts": counts if ref_msg is not None else None}
+
+
+def rs_decode_geometry(code, nframes: int) -> dict:
+    """What ``rs_decode`` launches for ``nframes`` frames (``wf_rs_decode_geometry``)."""
+    g = (ctypes.c_int64 * 5)()
+    _hip.check(_hip.lib().wf_rs_decode_geometry(_hip.ctx(), code.handle(), int(nframes), g))
+    return dict(zip(("waves_per_workgroup", "workgroups", "launches", "lds_bytes", "threads_per_workgroup"), (int(v) for v in g)))
+
+
 def _frame_pn(pn, n_tx: int):
     torch = _hip.torch()
     if pn is not None and (pn.dtype != torch.uint8 or pn.numel() != n_tx or not pn.is_contiguous()):
