@@ -827,7 +827,7 @@ int wf_turbo_decode(wf_ctx *ctx, const wf_turbo_code *code, const double *d_llr,
  * steps, [3] LDS bytes per wave, [4] scratch bytes.  Host only. */
 int wf_turbo_decode_geometry(wf_ctx *ctx, const wf_turbo_code *code, int64_t ncw, int64_t *h_geom);
 
-/* ---- Reed-Solomon codes over GF(2^8): systematic encoder and bounded-distance errors-only decoder, symbol-interleaved ----------
+/* ---- Reed-Solomon codes over GF(2^8): systematic encoder and bounded-distance decoders, symbol-interleaved -------------------
  * (The reference has no coding layer; these entry points are defined here.)
  * Field: GF(2^8) = GF(2)[x] / prim(x), prim a 9-bit mask (bit 8 set; CCSDS: 0x187); a symbol is a byte whose bit i is the
  * coefficient of x^i, α is the class of x.  prim must be primitive: α has period 255.
@@ -856,7 +856,7 @@ int wf_rs_encode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_msg, int6
  *   if a codeword c of that code lies within Hamming distance t of r, counted in symbols, it is unique: the output is c's
  *   message and status = d(r, c) = 0 .. t;  otherwise the output is r's own message symbols unchanged and status = -1.
  * (So a locator with a root at one of the 255 - n virtual positions is a failure, as is a locator of degree above t or one whose
- * number of roots among the n positions differs from its degree.)  Erasures are not supported.
+ * number of roots among the n positions differs from its degree.)  Erasures: wf_rs_decode_erasures below.
  * d_rx: nframes frames -> d_msg_out: nframes message frames, d_status (int32 per codeword, b I + c; may be NULL).  With d_ref_msg
  * (nframes message frames) these are ADDED to d_counts[0..4] (int64): [0] message bit errors after decoding, [1] codewords
  * wrong after decoding, [2] codewords with status -1, [3] symbols corrected summed over the successful codewords, [4] frames
@@ -869,6 +869,34 @@ int wf_rs_decode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, int64
 /* What wf_rs_decode launches for nframes frames: h_geom[0] waves (codewords) per workgroup = I, [1] workgroups, [2] launches,
  * [3] LDS bytes per workgroup, [4] threads per workgroup (64 I).  Host only. */
 int wf_rs_decode_geometry(wf_ctx *ctx, const wf_rs_code *code, int64_t nframes, int64_t *h_geom);
+/* Errors and erasures, again defined by the outcome.  d_erase: nframes x n I bytes in SYMBOL form whatever `bits` is, laid out
+ * like the frame, nonzero = erased.  For a received word r of the (possibly shortened) code, let E be the set of its f erased
+ * positions among its n real positions.
+ *   If f > 2t: the output is r's own message symbols unchanged and status = -1.
+ *   Otherwise, if a codeword c of that code exists with 2 |{i not in E : c_i != r_i}| + f <= 2t, it is unique (two such
+ *   codewords would differ outside E in at most (2t - f) / 2 + (2t - f) / 2 = 2t - f places, while the code punctured at E has
+ *   minimum distance 2t + 1 - f): the output is c's message and status = e = |{i not in E : c_i != r_i}|, the number of
+ *   positions OUTSIDE E that changed (an erased symbol that was received right or wrong counts in f only).
+ *   Otherwise the output is r's own message symbols unchanged and status = -1.
+ * The bytes received at erased positions decide nothing: the status, and on success the whole output, are the same for any two
+ * inputs that differ only there.  (On a failure the output is the received message as it came, erased positions included:
+ * that copy is the only use of those bytes.)  A candidate with a root at one of the 255 - n virtual positions is a failure, as
+ * before.  With no position erased the outputs are exactly those of wf_rs_decode.
+ * Buffers, d_status, alignment and the refusals are those of wf_rs_decode, and a NULL d_erase is refused too (WF_ERR_VALUE before
+ * any launch).  d_counts has SIX entries: [0..4] as in wf_rs_decode ([3] adds the status, the errors outside E), [5] erasures
+ * filled: f summed over the successful codewords.  Asynchronous on `stream`, nothing synchronises with the host; the geometry
+ * is wf_rs_decode's: one workgroup per frame, one wave per codeword, one launch. */
+int wf_rs_decode_erasures(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, const uint8_t *d_erase, int64_t nframes, int32_t bits,
+                          uint8_t *d_msg_out, int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream);
+/* The rule that turns the inner decoder's soft output into erasures.  d_post: nframes x 8 n I float32 (4-byte aligned), the Λ
+ * of wf_conv_siso (d_info_post) for frames in bit form, finite.  A symbol's reliability is ρ = min over its eight bits of |Λ|.
+ * Per codeword the erased symbols are the at most f_max symbols of smallest ρ among those with ρ < below; of two symbols with
+ * equal ρ the one with the smaller index in its codeword goes first.  d_erase (nframes x n I bytes, the form
+ * wf_rs_decode_erasures reads) is written whole: 1 = erased, 0 = not.  f_max = 0 marks nothing.  NULL ctx / code / d_post /
+ * d_erase, nframes < 1, f_max outside 0 .. 2t, below not finite, a misaligned d_post: WF_ERR_VALUE before any launch.
+ * Asynchronous on `stream`; one workgroup per frame, one wave per codeword. */
+int wf_rs_mark_erasures(wf_ctx *ctx, const wf_rs_code *code, const float *d_post, int64_t nframes, int32_t f_max, float below,
+                        uint8_t *d_erase, void *stream);
 
 /* ---- Framed coded links: attached sync marker, randomiser, soft frame search ------------------------------------------
  * (The reference has no coding or framing layer; these entry points are defined here.)

@@ -5,7 +5,7 @@ decoder's speed; prints ONE JSON line.
                               [--detector PT] [--steps 5] [--outer N --inner M --damping D]
                               [--framed [--lead-bits J] [--marker-prior X]] [--live-only [--guard G]]
     python tools/coded_ber.py --code conv-k3|conv-k7 [--info-bits K] [--interleave] [--outer N --damping D] [--ebn0 ...]
-    python tools/coded_ber.py --code conv-k3|conv-k7 --rs 16|8 [--rs-depth I] [--rs-n N] ...
+    python tools/coded_ber.py --code conv-k3|conv-k7 --rs 16|8 [--rs-depth I] [--rs-n N] [--rs-erasures F [--rs-erase-below X]] ...
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -48,6 +48,12 @@ fixed at one RS frame (8 n I).  Eb/N0 is per USER bit.  Every point gains an ``"
 next to the inner code's, flagged failures, miscorrections, symbols corrected, and the time per block of ``rs_encode`` and of
 ``rs_decode`` (device events around those two calls alone, the same ``--steps`` blocks) with its ratio to the ``conv_siso`` passes
 of the block.  Without ``--rs`` the output is unchanged.
+
+With ``--rs-erasures F`` the link also declares erasures (``rs_mark_erasures``: per RS codeword the at most F symbols of smallest
+reliability below ``--rs-erase-below``, from the last inner pass's Λ) and decodes errors and erasures; the errors-only decoder
+runs on the SAME decisions of the same blocks, and stays the ``"rs"`` entry.  Every point gains ``"rs_erasures"``: BER and FER,
+flagged failures, miscorrections, symbols corrected, erasures declared / filled, and from the same timed blocks the device-event
+times of ``rs_mark_erasures``, of ``rs_decode`` with erasures and of ``rs_decode`` without, with their ratio.
 """
 import argparse
 import json
@@ -135,28 +141,39 @@ def main_conv(args) -> None:
     if rs is None:
         link = ConvSOQPSKLink(code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True)
     else:
-        link = RSConvSOQPSKLink(rs, code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True)
+        link = RSConvSOQPSKLink(rs, code, per, detector=args.detector, outer=outer, damping=args.damping, per_pass=True,
+                                erasures=args.rs_erasures, erase_below=args.rs_erase_below)
     out = {"tool": "coded_ber", "code": args.code, "generators": [oct(g) for g in code.generators], "K": code.K, "n": code.n, "k": code.k,
            "n_tx": code.n_tx, "interleave": bool(args.interleave), "detector": args.detector, "block_codewords": per, "outer": outer,
            "damping": link.damping, "ext_clip": link.ext_clip, "geometry": dev.conv_siso_geometry(code, per), "points": []}
     if rs is not None:
         out["rs"] = {"n": rs.n, "k": rs.k, "t": rs.t, "depth": rs.depth, "prim": hex(rs.prim), "fcr": rs.fcr, "step": rs.step,
                      "user_bits_per_block": link.user_bits_per_block, "geometry": dev.rs_decode_geometry(rs, per)}
-    rs_scratch = torch.zeros(5, dtype=torch.int64, device="cuda") if rs is not None else None
+    rs_scratch = torch.zeros(6, dtype=torch.int64, device="cuda") if rs is not None else None
+    era = bool(rs is not None and args.rs_erasures)
+    plain_counts = torch.zeros(5, dtype=torch.int64, device="cuda") if era else None      # the errors-only decoder on the same decisions
+    if era:
+        out["rs"]["erasures"] = {"f_max": link.erasures, "below": link.erase_below}
     for e in args.ebn0:
         link.reset_counts()
         b = 0
         while b * per < args.codewords:
             link.run_block(e, seed=1, stream_id=b)
+            if era:
+                dev.rs_decode(rs, link.decided, bits=True, ref_msg=link.user, counts=plain_counts)
             b += 1
         be, fe, m = link.result()
         ue, um = link.uncoded_result()
         passes = link.pass_results()
         ncw = b * per
         rs_counts = link.rs_result() if rs is not None else None
+        if era:
+            era_counts, era_marks = rs_counts, link.rs_erasure_result()
+            rs_counts = tuple(int(v) for v in plain_counts.cpu().tolist()) + (rs_counts[5],)
+            plain_counts.zero_()
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3 + 2 * outer)]
-        rev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-        ms, rs_ms = np.zeros(2 + 2 * outer), np.zeros(2)
+        rev = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
+        ms, rs_ms = np.zeros(2 + 2 * outer), np.zeros(4)
         for s in range(args.steps + 1):
             if rs is not None:                                            # (the RS encoder alone, in front of the block: what info_bits does)
                 link.user = link.user_bits(b + s)
@@ -178,18 +195,31 @@ def main_conv(args) -> None:
                 for o in range(outer):
                     ext, _ = link.detect(rows, first=o == 0)
                     ev[3 + 2 * o].record()
-                    link.decode(ext)
+                    link.decode(ext, want_post=era and o == outer - 1)
                     ev[4 + 2 * o].record()
             if rs is not None:                                            # the call run_block makes on the block's decisions
-                decided = link.decided if outer > 1 else dev.conv_siso(code, llr, scale=link.llr_scale, want_post=False, want_ext=False)["info_bits"]
+                if outer > 1:
+                    decided, post = link.decided, link.post
+                else:
+                    siso = dev.conv_siso(code, llr, scale=link.llr_scale, want_post=era, want_ext=False)
+                    decided, post = siso["info_bits"], siso["info_post"]
                 rev[2].record()
                 dev.rs_decode(rs, decided, bits=True, ref_msg=link.user, counts=rs_scratch)
                 rev[3].record()
+                if era:                                                   # ... and the two calls the link makes with erasures, on the same decisions
+                    rev[4].record()
+                    marks = dev.rs_mark_erasures(rs, post, link.erasures, link.erase_below)
+                    rev[5].record()
+                    rev[6].record()
+                    dev.rs_decode(rs, decided, bits=True, ref_msg=link.user, counts=rs_scratch, erasures=marks)
+                    rev[7].record()
             torch.cuda.synchronize()
             if s:                                                         # (the first round warms up)
                 ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(2 + 2 * outer)]
                 if rs is not None:
-                    rs_ms += [rev[0].elapsed_time(rev[1]), rev[2].elapsed_time(rev[3])]
+                    rs_ms[:2] += [rev[0].elapsed_time(rev[1]), rev[2].elapsed_time(rev[3])]
+                if era:
+                    rs_ms[2:] += [rev[4].elapsed_time(rev[5]), rev[6].elapsed_time(rev[7])]
         ms /= max(args.steps, 1)
         rs_ms /= max(args.steps, 1)
         det, dec = ms[2::2], ms[3::2]
@@ -210,6 +240,15 @@ def main_conv(args) -> None:
                 "frame_errors": rfe, "flagged_failures": rfl, "miscorrections": rce - rfl, "symbols_corrected": rcor,
                 "ms_per_block": {"rs_encode": round(rs_ms[0], 4), "rs_decode": round(rs_ms[1], 4)},
                 "rs_decode_over_siso": round(float(rs_ms[1] / dec.sum()), 5) if dec.sum() > 0 else None}
+        if era:
+            ebe, ece, efl, ecor, efe, em = era_counts
+            out["points"][-1]["rs_erasures"] = {
+                "user_ber": ebe / em, "fer": efe / ncw, "user_bit_errors": ebe, "user_bits": em, "codeword_errors": ece, "codewords": ncw * rs.depth,
+                "frame_errors": efe, "flagged_failures": efl, "miscorrections": ece - efl, "symbols_corrected": ecor,
+                "erasures_declared": era_marks[0], "erasures_filled": era_marks[1],
+                "ms_per_block": {"rs_mark_erasures": round(rs_ms[2], 4), "rs_decode_erasures": round(rs_ms[3], 4), "rs_decode": round(rs_ms[1], 4)},
+                "erasures_over_errors_only": round(float((rs_ms[2] + rs_ms[3]) / rs_ms[1]), 4) if rs_ms[1] > 0 else None,
+                "rs_decode_erasures_over_rs_decode": round(float(rs_ms[3] / rs_ms[1]), 4) if rs_ms[1] > 0 else None}
     print(json.dumps(out))
 
 
@@ -222,6 +261,8 @@ def main() -> None:
     ap.add_argument("--rs", type=int, default=0, choices=[0, 8, 16], help="--code conv-*: CCSDS Reed-Solomon outer code correcting E symbols")
     ap.add_argument("--rs-depth", type=int, default=1, help="--rs: symbol interleaving depth 1 .. 8")
     ap.add_argument("--rs-n", type=int, default=255, help="--rs: shortened code length")
+    ap.add_argument("--rs-erasures", type=int, default=0, help="--rs: also decode errors and erasures, at most F erasures per RS codeword (0: off)")
+    ap.add_argument("--rs-erase-below", type=float, default=float("inf"), help="--rs-erasures: only symbols whose reliability is below X are erased")
     ap.add_argument("--ebn0", type=float, nargs="+", default=[4.0, 5.0, 6.0, 7.0, 8.0])
     ap.add_argument("--codewords", type=int, default=20000)
     ap.add_argument("--block-codewords", type=int, default=0, help="codewords per burst (0: about 1e7 channel bits)")
@@ -243,9 +284,11 @@ def main() -> None:
     if args.code.startswith("conv"):
         if args.waveform != "soqpsk" or args.framed or args.live_only:
             ap.error("--code conv-* is the SOQPSK-TG link's, unframed and without --live-only")
+        if args.rs_erasures and not args.rs:
+            ap.error("--rs-erasures goes with --rs")
         return main_conv(args)
-    if args.info_bits or args.interleave or args.rs:
-        ap.error("--info-bits, --interleave and --rs go with --code conv-k3 / conv-k7")
+    if args.info_bits or args.interleave or args.rs or args.rs_erasures:
+        ap.error("--info-bits, --interleave, --rs and --rs-erasures go with --code conv-k3 / conv-k7")
 
     import torch
 

@@ -124,6 +124,8 @@ SIGNATURES = {
     "wf_rs_encode": (c_int, [_P, _P, _P, c_int64, ctypes.c_int32, _P, _P]),
     "wf_rs_decode": (c_int, [_P, _P, _P, c_int64, ctypes.c_int32, _P, _P, _P, _P, _P]),
     "wf_rs_decode_geometry": (c_int, [_P, _P, c_int64, POINTER(c_int64)]),
+    "wf_rs_decode_erasures": (c_int, [_P, _P, _P, _P, c_int64, ctypes.c_int32, _P, _P, _P, _P, _P]),
+    "wf_rs_mark_erasures": (c_int, [_P, _P, _P, c_int64, ctypes.c_int32, ctypes.c_float, _P, _P]),
     "wf_frame_build": (c_int, [_P, _P, c_int64, ctypes.c_int32, c_uint64, ctypes.c_int32, _P, _P, _P]),
     "wf_frame_search": (c_int, [_P, _P, c_int64, c_uint64, ctypes.c_int32, c_int64, _P, _P, _P]),
     "wf_frame_gather": (c_int, [_P, _P, c_int64, _P, ctypes.c_int32, ctypes.c_int32, _P, c_int64, _P, _P]),

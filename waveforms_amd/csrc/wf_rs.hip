@@ -1,5 +1,6 @@
-// wf_rs.hip — Reed-Solomon codes over GF(2^8): the systematic encoder and the bounded-distance errors-only decoder, symbol-
-// interleaved to depth I (include/wfhip.h states the field, the code, the frame layout and the decoder's result).  A code is an
+// wf_rs.hip — Reed-Solomon codes over GF(2^8): the systematic encoder, the bounded-distance decoder (errors only, or errors and
+// erasures) and the rule that declares erasures from the inner decoder's soft output, symbol-interleaved to depth I
+// (include/wfhip.h states the field, the code, the frame layout and the decoders' results).  A code is an
 // opaque handle whose parameters are validated once on the host; its field tables live in device memory the handle owns.
 //
 // Both kernels: one workgroup per frame, one wave of 64 lanes per codeword (I waves).  A lane owns the up to four symbols whose
@@ -15,6 +16,13 @@
 //   roots       Lambda(beta^(-d)) by Horner at the lane's four degrees, coefficients broadcast from their lanes; a root at a
 //               virtual degree, or a root count other than L: failure.
 //   values      Omega = S Lambda mod x^L (lane i = Omega_i); e_d = Omega(x) / Lambda'(x) F[d] at x = beta^(-d).
+// Errors and erasures (rse_decode_kernel, the same body with ERAS = true): the lane's erased degrees enter the syndromes as 0;
+//   the wave collects them by ballot (f of them; f > 2t: failure) and builds Gamma(x) = prod (1 - beta^d x) in lanes, one lane
+//   shift and one product per erasure; Berlekamp-Massey then starts from Lambda = B = Gamma, L = f at syndrome f, its length
+//   change taken when 2 L <= it + f; the result is the errata locator of degree L <= t + f / 2 <= 2t, still lane = coefficient.
+//   Roots and values run on it unchanged; the value at an erased degree IS the symbol.  2 L - f > 2t: failure; status = L - f.
+// Marking (rse_mark_kernel): one wave per codeword; rho of a symbol = min |post| over its eight bits, compared as the bit
+//   patterns of non-negative floats; f_max rounds of a wave arg-min over the 64-bit key (rho, index).
 // Encoder, per wave: the 2t-stage LFSR division, lane j = stage j, one step per message symbol.
 // GF(256) products: log / antilog tables in LDS (MUL_TABLES = true: three byte reads and an add) or shift-and-xor in registers
 // (false: 8 doublings, about 40 vector instructions).  The library is built with the form RS_MUL_TABLES names, the tables:
@@ -24,6 +32,8 @@
 #include "wf_common.h"
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 
 #define RS_MAX_DEPTH 8
 #define RS_MAX_T 16
@@ -47,7 +57,7 @@ struct wf_rs_code {
 };
 
 struct rs_args {
-    const uint8_t *tab, *in, *ref;
+    const uint8_t *tab, *in, *ref, *erase;
     uint8_t *out;
     int32_t *status;
     unsigned long long *counts;
@@ -88,6 +98,16 @@ struct rs_field {
         return r;                                                   // a^(2 + 4 + .. + 128)
     }
 };
+
+__device__ __forceinline__ unsigned long long rs_wave_min(unsigned long long v)
+{
+#pragma unroll
+    for (int d = WF_WAVE / 2; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, WF_WAVE);
+        v = o < v ? o : v;
+    }
+    return v;
+}
 
 __device__ __forceinline__ uint32_t rs_wave_xor(uint32_t v)
 {
@@ -167,8 +187,8 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_encode_kernel(rs_arg
 }
 
 // ---------------------------------------------------------------- decoder
-template <bool MUL_TABLES>
-__global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_args a)
+template <bool MUL_TABLES, bool ERAS>
+__device__ __forceinline__ void rs_decode_body(const rs_args &a)
 {
     __shared__ __attribute__((aligned(4))) uint8_t sTab[MUL_TABLES ? 768 : 16];      // (not allocated when unused)
     __shared__ int sFrameWrong;
@@ -180,12 +200,23 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_arg
 
     // the lane's symbols by degree d = lane + 64 q (0 at the virtual degrees and at d = 255)
     uint32_t r[4], term[4], dk[4];
+    uint32_t er = 0;                                                 // ERAS: bit q = the lane's degree lane + 64 q is erased
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int d = lane + 64 * q;
         r[q] = d < n ? rs_load(a.in, in0 + (int64_t)(n - 1 - d) * I, a.bits, a.wide) : 0u;
+        if constexpr (ERAS) er |= (d < n && a.erase[in0 + (int64_t)(n - 1 - d) * I] ? 1u : 0u) << q;
         dk[q] = a.tab[RS_TAB_D + (d & 255)];
-        term[q] = gf.mul(a.tab[RS_TAB_W + (d & 255)], r[q]);
+        term[q] = gf.mul(a.tab[RS_TAB_W + (d & 255)], (er >> q) & 1u ? 0u : r[q]);
+    }
+    unsigned long long em[4] = {0, 0, 0, 0};                         // ERAS: the wave's erased degrees, f of them
+    int f = 0;
+    if constexpr (ERAS) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            em[q] = __ballot((er >> q) & 1u);
+            f += __popcll(em[q]);
+        }
     }
 
     // syndromes, four to a dword; lane j keeps S_j
@@ -205,12 +236,28 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_arg
     if (lane >= t2) S = 0;
 
     int status = 0;
-    if (__ballot(S != 0) != 0) {
+    if (ERAS && f > t2) {
+        status = -1;
+    } else if (__ballot(S != 0) != 0) {
         // inversionless Berlekamp-Massey: Lambda <- b Lambda - delta x^m B; lane i holds coefficient i
-        uint32_t lam = lane == 0 ? 1u : 0u, B = lam, win = 0, b = 1;
-        int L = 0;
+        uint32_t lam = lane == 0 ? 1u : 0u, win = 0, b = 1;
+        if constexpr (ERAS) {
+            // Lambda = Gamma = prod over the erased degrees of (1 - beta^d x); the window as f iterations would have left it
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
 #pragma unroll 1
-        for (int it = 0; it < t2; ++it) {
+                for (unsigned long long m = em[q]; m; m &= m - 1) {
+                    const uint32_t X = (uint32_t)__shfl((int)dk[q], __builtin_ctzll(m), WF_WAVE), up = (uint32_t)__shfl_up((int)lam, 1, WF_WAVE);
+                    lam ^= gf.mul(X, lane ? up : 0u);
+                }
+            }
+            const uint32_t sw = (uint32_t)__shfl((int)S, (f - 1 - lane) & (WF_WAVE - 1), WF_WAVE);
+            win = lane < f ? sw : 0u;                                // lane i: S_{f - 1 - i}
+        }
+        uint32_t B = lam;
+        int L = f;
+#pragma unroll 1
+        for (int it = f; it < t2; ++it) {
             const uint32_t Bu = (uint32_t)__shfl_up((int)B, 1, WF_WAVE), wu = (uint32_t)__shfl_up((int)win, 1, WF_WAVE);
             const uint32_t sr = (uint32_t)__shfl((int)S, it, WF_WAVE);
             B = lane ? Bu : 0u;
@@ -218,16 +265,16 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_arg
             const uint32_t delta = rs_wave_xor(gf.mul(lam, win));
             if (delta) {
                 const uint32_t nl = gf.mul(b, lam) ^ gf.mul(delta, B);
-                if (2 * L <= it) {
+                if (2 * L <= it + f) {
                     B = lam;
-                    L = it + 1 - L;
+                    L = it + 1 + f - L;
                     b = delta;
                 }
                 lam = nl;
             }
         }
-        status = L <= t ? L : -1;
-        if (status > 0) {
+        status = ERAS ? (2 * L - f <= t2 ? L - f : -1) : (L <= t ? L : -1);      // (L = errors + erasures)
+        if (ERAS ? status >= 0 : status > 0) {
             // Omega_i = sum_{j <= i} Lambda_j S_{i - j}, i < L
             uint32_t om = 0;
 #pragma unroll 1
@@ -244,7 +291,7 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_arg
                 x2[q] = gf.mul(x[q], x[q]);
             }
 #pragma unroll 1
-            for (int i = t; i >= 0; --i) {
+            for (int i = ERAS ? L : t; i >= 0; --i) {
                 const uint32_t li = (uint32_t)__shfl((int)lam, i, WF_WAVE), oi = (uint32_t)__shfl((int)om, i, WF_WAVE);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -268,9 +315,12 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_arg
                 status = -1;
             } else {
 #pragma unroll
-                for (int q = 0; q < 4; ++q) r[q] ^= e[q];
+                for (int q = 0; q < 4; ++q) r[q] = ((er >> q) & 1u ? 0u : r[q]) ^ e[q];
             }
         }
+    } else if constexpr (ERAS) {                                     // zero syndromes: r with 0 at the erased degrees is the codeword
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r[q] = (er >> q) & 1u ? 0u : r[q];
     }
 
     // the message (the received one on a failure), the status and the counts
@@ -295,7 +345,72 @@ __global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_arg
             }
             if (status < 0) atomicAdd(a.counts + 2, 1ull);
             if (status > 0) atomicAdd(a.counts + 3, (unsigned long long)status);
+            if (ERAS && status >= 0 && f > 0) atomicAdd(a.counts + 5, (unsigned long long)f);
         }
+    }
+}
+
+template <bool MUL_TABLES>
+__global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rs_decode_kernel(rs_args a)
+{
+    rs_decode_body<MUL_TABLES, false>(a);
+}
+
+template <bool MUL_TABLES>
+__global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rse_decode_kernel(rs_args a)
+{
+    rs_decode_body<MUL_TABLES, true>(a);
+}
+
+// ---------------------------------------------------------------- erasure marking
+struct rs_mark_args {
+    const uint32_t *post;      // float32 bit patterns, bit form: eight per symbol
+    uint8_t *erase;
+    int32_t n, depth, f_max;
+    uint32_t below;            // the bit pattern of `below` (0 when below <= 0: nothing is under it)
+};
+
+__global__ __launch_bounds__(WF_WAVE *RS_MAX_DEPTH) void rse_mark_kernel(rs_mark_args a)
+{
+    const int lane = threadIdx.x & (WF_WAVE - 1), c = threadIdx.x >> 6, I = a.depth, n = a.n;
+    const int64_t sym0 = (int64_t)blockIdx.x * n * I + c;
+    // rho of the lane's symbols i = lane + 64 q, as the bit pattern of a non-negative float (ordered like the value); ~0: no candidate
+    uint32_t rho[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        rho[q] = ~0u;
+        if (i < n) {
+            const uint32_t *p = a.post + 8 * (sym0 + (int64_t)i * I);
+            uint32_t m = p[0] & 0x7fffffffu;
+#pragma unroll
+            for (int b = 1; b < 8; ++b) m = min(m, p[b] & 0x7fffffffu);
+            rho[q] = m < a.below ? m : ~0u;
+        }
+    }
+    uint32_t marked = 0;
+#pragma unroll 1
+    for (int round = 0; round < a.f_max; ++round) {
+        unsigned long long key = ~0ull;                              // (rho, index): the smaller index wins a tie
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const unsigned long long kq = ((unsigned long long)rho[q] << 32) | (uint32_t)(lane + 64 * q);
+            key = rho[q] != ~0u && kq < key ? kq : key;
+        }
+        const unsigned long long best = rs_wave_min(key);
+        if (best == ~0ull) break;                                    // (wave-uniform)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if ((uint32_t)best == (uint32_t)(lane + 64 * q)) {
+                marked |= 1u << q;
+                rho[q] = ~0u;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int i = lane + 64 * q;
+        if (i < n) a.erase[sym0 + (int64_t)i * I] = (uint8_t)((marked >> q) & 1u);
     }
 }
 
@@ -379,7 +494,7 @@ static rs_args rs_make_args(const wf_rs_code *code, int bits, const void *in, co
 {
     rs_args a;
     a.tab = code->d_tab;
-    a.in = a.ref = nullptr, a.out = nullptr, a.status = nullptr, a.counts = nullptr;
+    a.in = a.ref = a.erase = nullptr, a.out = nullptr, a.status = nullptr, a.counts = nullptr;
     a.n = code->n, a.k = code->k, a.t2 = 2 * code->t, a.depth = code->depth, a.bits = bits, a.prim = (uint32_t)code->prim;
     a.wide = bits && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ref)) & 7) == 0;
     return a;
@@ -436,6 +551,58 @@ extern "C" int wf_rs_decode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *
         a.ref = d_ref_msg ? d_ref_msg + f0 * msg_frame : nullptr;
         a.status = d_status ? d_status + f0 * code->depth : nullptr;
         hipLaunchKernelGGL(rs_decode_kernel<RS_MUL_TABLES != 0>, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
+        WF_LAUNCH_CHECK();
+    }
+    return WF_OK;
+}
+
+extern "C" int wf_rs_decode_erasures(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, const uint8_t *d_erase, int64_t nframes, int32_t bits,
+                                     uint8_t *d_msg_out, int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream)
+{
+    WF_REQUIRE(ctx && code && d_rx && d_erase && d_msg_out, "wf_rs_decode_erasures: NULL argument");
+    WF_REQUIRE(nframes >= 1, "wf_rs_decode_erasures: nframes must be at least 1");
+    WF_REQUIRE(bits == 0 || bits == 1, "wf_rs_decode_erasures: bits = %d outside {0, 1}", bits);
+    WF_REQUIRE(!d_ref_msg || d_counts, "wf_rs_decode_erasures: d_ref_msg needs d_counts");
+    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3) == 0,
+               "wf_rs_decode_erasures: counts must be 8-byte, status 4-byte aligned");
+    WF_REQUIRE(code->device == ctx->device, "wf_rs_decode_erasures: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_HIP(hipSetDevice(ctx->device));
+    rs_args a = rs_make_args(code, bits, d_rx, d_msg_out, d_ref_msg);
+    a.counts = reinterpret_cast<unsigned long long *>(d_counts);
+    const int64_t sym = bits ? 8 : 1, in_frame = sym * code->n * code->depth, msg_frame = sym * code->k * code->depth;
+    for (int64_t f0 = 0; f0 < nframes; f0 += RS_MAX_GRID) {
+        const unsigned grid = (unsigned)std::min<int64_t>(RS_MAX_GRID, nframes - f0);
+        a.in = d_rx + f0 * in_frame;
+        a.erase = d_erase + f0 * code->n * code->depth;
+        a.out = d_msg_out + f0 * msg_frame;
+        a.ref = d_ref_msg ? d_ref_msg + f0 * msg_frame : nullptr;
+        a.status = d_status ? d_status + f0 * code->depth : nullptr;
+        hipLaunchKernelGGL(rse_decode_kernel<RS_MUL_TABLES != 0>, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
+        WF_LAUNCH_CHECK();
+    }
+    return WF_OK;
+}
+
+extern "C" int wf_rs_mark_erasures(wf_ctx *ctx, const wf_rs_code *code, const float *d_post, int64_t nframes, int32_t f_max, float below,
+                                   uint8_t *d_erase, void *stream)
+{
+    WF_REQUIRE(ctx && code && d_post && d_erase, "wf_rs_mark_erasures: NULL argument");
+    WF_REQUIRE(nframes >= 1, "wf_rs_mark_erasures: nframes must be at least 1");
+    WF_REQUIRE(f_max >= 0 && f_max <= 2 * code->t, "wf_rs_mark_erasures: f_max = %d outside 0 .. 2t = %d", f_max, 2 * code->t);
+    WF_REQUIRE(std::isfinite(below), "wf_rs_mark_erasures: below must be finite");
+    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_post) & 3) == 0, "wf_rs_mark_erasures: d_post must be 4-byte aligned");
+    WF_REQUIRE(code->device == ctx->device, "wf_rs_mark_erasures: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_HIP(hipSetDevice(ctx->device));
+    rs_mark_args a;
+    a.n = code->n, a.depth = code->depth, a.f_max = f_max;
+    a.below = 0;
+    if (below > 0.0f) std::memcpy(&a.below, &below, 4);
+    const int64_t frame = (int64_t)code->n * code->depth;
+    for (int64_t f0 = 0; f0 < nframes; f0 += RS_MAX_GRID) {
+        const unsigned grid = (unsigned)std::min<int64_t>(RS_MAX_GRID, nframes - f0);
+        a.post = reinterpret_cast<const uint32_t *>(d_post) + 8 * f0 * frame;
+        a.erase = d_erase + f0 * frame;
+        hipLaunchKernelGGL(rse_mark_kernel, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
         WF_LAUNCH_CHECK();
     }
     return WF_OK;

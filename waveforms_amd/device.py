@@ -662,22 +662,50 @@ def rs_encode(code, d_msg, bits: bool = False):
     return out
 
 
-def rs_decode(code, d_rx, bits: bool = False, ref_msg=None, counts=None, want_status: bool = True) -> dict:
+def rs_decode(code, d_rx, bits: bool = False, ref_msg=None, counts=None, want_status: bool = True, erasures=None) -> dict:
     """Bounded-distance Reed-Solomon decoding (``wf_rs_decode``; include/wfhip.h states the result) of F frames (F x n I
     symbols, or bits) -> {"msg": F x k I in the same form, "status": int32 F I (symbols corrected, -1 = failure), "counts"}.
     With ``ref_msg`` (device message frames) the decoder ADDS to ``counts`` (int64[5], fresh zeros if None): message bit errors,
-    codewords wrong, codewords flagged, symbols corrected, frames with a wrong codeword."""
+    codewords wrong, codewords flagged, symbols corrected, frames with a wrong codeword.
+    ``erasures``: device uint8 F x n I in SYMBOL form whatever ``bits`` is, nonzero = erased: errors-and-erasures decoding
+    (``wf_rs_decode_erasures``); ``counts`` is then int64[6], [5] = erasures filled over the successful codewords."""
     nf = _rs_frames(code, d_rx, code.n, bits, "frames")
+    ncount = 5 if erasures is None else 6
+    if erasures is not None and _rs_frames(code, erasures, code.n, False, "erasures") != nf:
+        raise ValueError("erasures must hold n x depth bytes for every frame")
     if ref_msg is not None:
         if _rs_frames(code, ref_msg, code.k, bits, "ref_msg") != nf:
             raise ValueError("ref_msg must hold as many message frames as there are frames")
         if counts is None:
-            counts = _hip.zeros(5, "int64")
+            counts = _hip.zeros(ncount, "int64")
+        elif counts.numel() < ncount:
+            raise ValueError(f"counts must hold {ncount} int64 values")
     out = _hip.empty((nf, (8 if bits else 1) * code.k * code.depth), "uint8")
     status = _hip.empty(nf * code.depth, "int32") if want_status else None
-    _hip.check(_hip.lib().wf_rs_decode(_hip.ctx(), code.handle(), _hip.ptr(d_rx), nf, int(bool(bits)), _hip.ptr(out), _hip.ptr(status),
-                                       _hip.ptr(ref_msg), _hip.ptr(counts) if ref_msg is not None else None, _hip.stream()))
+    tail = (_hip.ptr(out), _hip.ptr(status), _hip.ptr(ref_msg), _hip.ptr(counts) if ref_msg is not None else None, _hip.stream())
+    if erasures is None:
+        _hip.check(_hip.lib().wf_rs_decode(_hip.ctx(), code.handle(), _hip.ptr(d_rx), nf, int(bool(bits)), *tail))
+    else:
+        _hip.check(_hip.lib().wf_rs_decode_erasures(_hip.ctx(), code.handle(), _hip.ptr(d_rx), _hip.ptr(erasures), nf, int(bool(bits)), *tail))
     return {"msg": out, "status": status, "counts": counts if ref_msg is not None else None}
+
+
+def rs_mark_erasures(code, post, f_max: int, below: float = float("inf")):
+    """Erasures from the inner decoder's soft output (``wf_rs_mark_erasures``): ``post`` device float32, F x 8 n I (the Λ of
+    ``conv_siso`` for frames in bit form) -> uint8 F x n I, 1 = erased: per codeword the at most ``f_max`` symbols of smallest
+    ρ = min |Λ| over the symbol's bits among those with ρ < ``below``, ties to the smaller index.  ``below`` is rounded to float32
+    and an infinite one becomes the largest finite float32 (``RSCode.mark_erasures_host`` does the same)."""
+    from .encoding.rs import below_f32
+
+    torch = _hip.torch()
+    unit = 8 * code.n * code.depth
+    if post.dtype != torch.float32 or not post.is_contiguous() or post.numel() % unit or post.numel() == 0:
+        raise ValueError(f"post must be contiguous float32, a whole number of frames of {unit} values")
+    nf = post.numel() // unit
+    out = _hip.empty((nf, code.n * code.depth), "uint8")
+    _hip.check(_hip.lib().wf_rs_mark_erasures(_hip.ctx(), code.handle(), _hip.ptr(post), nf, int(f_max), below_f32(below), _hip.ptr(out),
+                                              _hip.stream()))
+    return out
 
 
 def rs_decode_geometry(code, nframes: int) -> dict:

@@ -9,10 +9,13 @@ belonging to codeword p mod I at index p div I; a message frame is k I symbols l
 Every array here is in SYMBOLS (uint8, one per byte) unless ``bits=True`` is passed: then it is one bit per byte, eight per
 symbol, MSB first (``to_bits`` / ``from_bits``), the form the convolutional encoder reads and its decoder writes.
 
-The decoder is errors-only and bounded-distance: the unique codeword within t symbols of the received word if there is one
-(status = the distance), else the received message unchanged and status -1.  ``decode_host`` finds its candidate with the
-Euclidean algorithm and then CHECKS it against that definition (zero syndromes, at most t changes, none at a virtual position);
-the GPU decoder (Berlekamp-Massey) must agree with it bitwise.
+The decoder is bounded-distance: the unique codeword within t symbols of the received word if there is one (status = the
+distance), else the received message unchanged and status -1.  With ``erasures`` (f erased positions of a word, f <= 2t) it is
+the unique codeword that differs from the word in e positions OUTSIDE the erased set with 2e + f <= 2t (status = e); the bytes
+at erased positions decide nothing.  ``decode_host`` finds its candidate with the Euclidean algorithm (on the syndromes times
+the erasure locator) and then CHECKS it against that definition (zero syndromes, the inequality, none at a virtual position);
+the GPU decoder (Berlekamp-Massey) must agree with it bitwise.  ``mark_erasures_host`` is the rule that declares erasures from
+the inner decoder's soft output.
 """
 from __future__ import annotations
 
@@ -28,6 +31,17 @@ def to_bits(sym: np.ndarray) -> np.ndarray:
     """Symbols (.. x m) -> bits (.. x 8 m), MSB first."""
     s = np.ascontiguousarray(sym, dtype=np.uint8)
     return np.unpackbits(s[..., None], axis=-1).reshape(s.shape[:-1] + (8 * s.shape[-1],))
+
+
+def below_f32(below: float) -> float:
+    """The threshold of the erasure rule as the device takes it: rounded to float32, ±infinity replaced by the largest finite
+    float32 of that sign."""
+    with np.errstate(over="ignore"):
+        b = np.float32(below)
+    if np.isnan(b):
+        raise ValueError("below must not be NaN")
+    big = np.finfo(np.float32).max
+    return float(min(max(b, -big), big))
 
 
 def from_bits(bits: np.ndarray) -> np.ndarray:
@@ -151,20 +165,28 @@ class RSCode:
         out = self._join(self.encode_words_host(self._split(m, self.k)))
         return to_bits(out) if bits else out
 
-    def _candidate(self, S: np.ndarray):
-        """A candidate error vector by degree (255 entries) from the syndromes of one word, by the Euclidean algorithm, or None."""
-        t, t2 = self.t, 2 * self.t
+    def _candidate(self, S: np.ndarray, erased=()):
+        """A candidate error vector by degree (255 entries) from the syndromes of one word whose symbols at the degrees
+        ``erased`` were taken as 0, by the Euclidean algorithm on S Γ mod x^2t, Γ = Π (1 - β^d x) over the erased degrees, or
+        None.  Its values at the erased degrees are the symbols there."""
+        t2 = 2 * self.t
+        f = len(erased)
 
         def deg(p):
             nz = np.flatnonzero(p)
             return int(nz[-1]) if nz.size else -1
 
+        gam = np.zeros(t2 + 1, dtype=np.int64)
+        gam[0] = 1
+        for d in erased:                                               # Γ <- Γ (1 - β^d x)
+            gam[1:] ^= self.mul(gam[:-1], self.beta_pow(d))
         r0, r1 = np.zeros(t2 + 1, dtype=np.int64), np.zeros(t2 + 1, dtype=np.int64)
         r0[t2] = 1
-        r1[:t2] = S
+        for i in range(f + 1):                                         # the modified syndromes S Γ mod x^2t
+            r1[i:t2] ^= self.mul(gam[i], np.asarray(S[:t2 - i], dtype=np.int64))
         u0, u1 = np.zeros(t2 + 2, dtype=np.int64), np.zeros(t2 + 2, dtype=np.int64)
         u1[0] = 1
-        while deg(r1) >= t:
+        while 2 * deg(r1) >= t2 + f:
             d1, lead = deg(r1), self.inv(r1[deg(r1)])
             while deg(r0) >= d1:                                       # r0 <- r0 mod r1, u0 <- u0 - q u1
                 d0 = deg(r0)
@@ -172,16 +194,20 @@ class RSCode:
                 r0[s:s + d1 + 1] ^= self.mul(q, r1[:d1 + 1])
                 u0[s:] ^= self.mul(q, u1[:u1.size - s])
             r0, r1, u0, u1 = r1, r0, u1, u0
-        lam, om = u1, r1
-        L = deg(lam)
-        if L < 1 or L > t or lam[0] == 0:
+        sig, om = u1, r1                                               # the error locator; Ω = S Γ σ mod x^2t
+        Ls = deg(sig)
+        if Ls < (0 if f else 1) or 2 * Ls + f > t2 or sig[0] == 0:
             return None
+        lam = np.zeros(2 * t2 + 3, dtype=np.int64)                     # the errata locator σ Γ, of degree L
+        for i in range(Ls + 1):
+            lam[i:i + t2 + 1] ^= self.mul(sig[i], gam)
+        L = Ls + f
         d = np.arange(255)
-        x = self.beta_pow(-d)                                          # β^(-d): a root there is an error at degree d
-        roots = self.poly_eval(lam, x) == 0
+        x = self.beta_pow(-d)                                          # β^(-d): a root there is an error or an erasure at degree d
+        roots = self.poly_eval(lam[:L + 1], x) == 0
         if int(roots.sum()) != L or roots[self.n:].any():
             return None
-        dlam = lam.copy()
+        dlam = lam[:L + 1].copy()
         dlam[0::2] = 0                                                 # the formal derivative: odd terms, one degree down
         den = self.poly_eval(dlam[1:], x)
         if (den[roots] == 0).any():
@@ -189,39 +215,81 @@ class RSCode:
         e = self.mul(self.mul(self.poly_eval(om, x), self.inv(np.where(den == 0, 1, den))), self.beta_pow(d * (1 - self.fcr)))
         return np.where(roots, e, 0)
 
-    def decode_words_host(self, words: np.ndarray):
-        """Codewords (B x n) -> (messages B x k, status B): the definition, word by word."""
+    def decode_words_host(self, words: np.ndarray, erasures=None):
+        """Codewords (B x n) -> (messages B x k, status B): the definition, word by word.  ``erasures``: B x n, nonzero = erased."""
         w = np.atleast_2d(np.asarray(words, dtype=np.uint8))
         if w.shape[1] != self.n:
             raise ValueError(f"words must have n = {self.n} symbols")
         out, status = w[:, :self.k].copy(), np.zeros(w.shape[0], dtype=np.int32)
-        S = self.syndromes_host(w)
-        for b in np.flatnonzero(S.any(axis=1)):
+        if erasures is None:
+            era = np.zeros(w.shape, dtype=bool)
+        else:
+            era = np.atleast_2d(np.asarray(erasures)) != 0
+            if era.shape != w.shape:
+                raise ValueError("erasures must have one entry per symbol")
+        f = era.sum(axis=1)
+        wz = np.where(era, 0, w).astype(np.uint8)                      # the bytes at erased positions are not read past this line
+        S = self.syndromes_host(wz)
+        status[f > 2 * self.t] = -1
+        idx = self.n - 1 - np.arange(self.n)                           # the degree of position i
+        for b in np.flatnonzero((S.any(axis=1) | (f > 0)) & (f <= 2 * self.t)):
             status[b] = -1
-            e = self._candidate(S[b])
-            if e is None:
-                continue
-            c = w[b].astype(np.int64) ^ e[self.n - 1 - np.arange(self.n)]
-            nerr = int(np.count_nonzero(c != w[b]))
-            if 1 <= nerr <= self.t and not self.syndromes_host(c[None, :]).any():      # a codeword within t of the word: the one
+            if S[b].any():
+                e = self._candidate(S[b], idx[era[b]].tolist())
+                if e is None:
+                    continue
+                c = wz[b].astype(np.int64) ^ e[idx]
+            else:
+                c = wz[b].astype(np.int64)                             # the word with 0 at its erased positions is a codeword
+            nerr = int(np.count_nonzero((c != wz[b]) & ~era[b]))
+            # a codeword with 2 (changes outside the erased set) + f <= 2t: the one
+            if (nerr >= 1 or f[b] > 0) and 2 * nerr + int(f[b]) <= 2 * self.t and not self.syndromes_host(c[None, :]).any():
                 out[b], status[b] = c[:self.k], nerr
         return out, status
 
-    def decode_host(self, frames: np.ndarray, bits: bool = False):
-        """Frames (F x n I) -> (message frames F x k I, status F I int32, codeword b I + c at [b I + c])."""
+    def decode_host(self, frames: np.ndarray, bits: bool = False, erasures=None):
+        """Frames (F x n I) -> (message frames F x k I, status F I int32, codeword b I + c at [b I + c]).  ``erasures``: uint8 in
+        SYMBOL form whatever ``bits`` is, F x n I laid out like the frame, nonzero = erased (None: errors only)."""
         f = from_bits(frames) if bits else frames
-        msgs, status = self.decode_words_host(self._split(f, self.n))
+        era = None if erasures is None else self._split(erasures, self.n)
+        msgs, status = self.decode_words_host(self._split(f, self.n), era)
         out = self._join(msgs)
         return (to_bits(out) if bits else out), status
 
-    def counts_host(self, msg_out: np.ndarray, status: np.ndarray, ref: np.ndarray, bits: bool = False) -> list[int]:
-        """The five counts of ``wf_rs_decode`` from its outputs and the reference message frames."""
+    def mark_erasures_host(self, post: np.ndarray, f_max: int, below: float = float("inf")) -> np.ndarray:
+        """The erasure rule (``wf_rs_mark_erasures``): ``post`` F x 8 n I float32, the Λ of ``conv_siso`` for frames in bit form,
+        finite -> uint8 F x n I, 1 = erased.  ρ of a symbol = min |Λ| over its eight bits; per codeword the erased symbols are
+        the at most ``f_max`` symbols of smallest ρ among those with ρ < ``below`` (as ``below_f32`` makes it), ties to the
+        smaller index within the codeword."""
+        p = np.atleast_2d(np.asarray(post, dtype=np.float32))
+        if p.shape[1] != 8 * self.n * self.depth:
+            raise ValueError(f"a frame must hold 8 n depth = {8 * self.n * self.depth} values, not {p.shape[1]}")
+        f_max = int(f_max)
+        if not 0 <= f_max <= 2 * self.t:
+            raise ValueError(f"f_max = {f_max} outside 0 .. 2t = {2 * self.t}")
+        lim = np.float32(below_f32(below))
+        rho = np.abs(p).reshape(p.shape[0], self.n * self.depth, 8).min(axis=2)
+        rho = rho.reshape(p.shape[0], self.n, self.depth).transpose(0, 2, 1).reshape(-1, self.n)       # by codeword
+        era = np.zeros(rho.shape, dtype=np.uint8)
+        for b in range(rho.shape[0]):
+            order = np.argsort(rho[b], kind="stable")                  # equal ρ: the smaller index first
+            era[b, [i for i in order if rho[b, i] < lim][:f_max]] = 1
+        return self._join(era)
+
+    def counts_host(self, msg_out: np.ndarray, status: np.ndarray, ref: np.ndarray, bits: bool = False, erasures=None) -> list[int]:
+        """The five counts of ``wf_rs_decode`` from its outputs and the reference message frames; with ``erasures`` (symbol
+        form, as ``decode_host`` takes them) the six of ``wf_rs_decode_erasures``: the sixth is the erasures filled, summed over
+        the successful codewords."""
         a = self._split(from_bits(msg_out) if bits else msg_out, self.k)
         r = self._split(from_bits(ref) if bits else ref, self.k)
         be = np.unpackbits((a ^ r)[..., None], axis=-1).reshape(a.shape[0], -1).sum(axis=1)
         wrong = be > 0
-        return [int(be.sum()), int(wrong.sum()), int((status < 0).sum()), int(status[status > 0].sum()),
-                int(wrong.reshape(-1, self.depth).any(axis=1).sum())]
+        out = [int(be.sum()), int(wrong.sum()), int((status < 0).sum()), int(status[status > 0].sum()),
+               int(wrong.reshape(-1, self.depth).any(axis=1).sum())]
+        if erasures is not None:
+            f = (self._split(erasures, self.n) != 0).sum(axis=1)
+            out.append(int(f[np.asarray(status) >= 0].sum()))
+        return out
 
     # ------------------------------------------------------------------ device
     def handle(self) -> int:
@@ -255,14 +323,16 @@ class RSCode:
         m = np.ascontiguousarray(np.atleast_2d(np.asarray(msg_frames, dtype=np.uint8)))
         return _hip.to_host(dev.rs_encode(self, _hip.to_device(m), bits=bits))
 
-    def decode(self, frames: np.ndarray, bits: bool = False, ref=None) -> dict:
-        """Frames -> {"msg", "status", "counts"} as host arrays, decoded on the GPU (``waveforms_amd.device.rs_decode``)."""
+    def decode(self, frames: np.ndarray, bits: bool = False, ref=None, erasures=None) -> dict:
+        """Frames -> {"msg", "status", "counts"} as host arrays, decoded on the GPU (``waveforms_amd.device.rs_decode``);
+        ``erasures`` as ``decode_host`` takes them."""
         from .. import _hip
         from .. import device as dev
 
         f = np.ascontiguousarray(np.atleast_2d(np.asarray(frames, dtype=np.uint8)))
         r = None if ref is None else _hip.to_device(np.ascontiguousarray(np.atleast_2d(np.asarray(ref, dtype=np.uint8))))
-        out = dev.rs_decode(self, _hip.to_device(f), bits=bits, ref_msg=r)
+        era = None if erasures is None else _hip.to_device(np.ascontiguousarray(np.atleast_2d(np.asarray(erasures, dtype=np.uint8))))
+        out = dev.rs_decode(self, _hip.to_device(f), bits=bits, ref_msg=r, erasures=era)
         return {"msg": _hip.to_host(out["msg"]), "status": _hip.to_host(out["status"]),
                 "counts": None if out["counts"] is None else _hip.to_host(out["counts"])}
 

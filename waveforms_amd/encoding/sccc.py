@@ -53,7 +53,8 @@ class ConvSOQPSKLink(CodedSOQPSKLink):
         self.counts = _hip.zeros(2, "int64")
         self.pass_counts = _hip.zeros((self.outer, 2), "int64")
         self._last = _hip.zeros(2, "int64")
-        self.prior = self.decided = None
+        self.prior = self.decided = self.post = None
+        self.keep_post = False                 # a subclass that needs the last pass's Λ (conv_siso's info_post) sets it: ``post``
 
     # ---------------------------------------------------------------- stages
     def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
@@ -76,12 +77,12 @@ class ConvSOQPSKLink(CodedSOQPSKLink):
         ext, bits = dev.viterbi_soft_apriori(rows, None if first else self.prior, self.damping)
         return ext[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
 
-    def decode(self, ext, ref_info=None, counts=None) -> None:
+    def decode(self, ext, ref_info=None, counts=None, want_post: bool = False) -> None:
         """One decoder pass: the decisions (``decided``) and the next prior, in place; with ``ref_info`` the two counts are
-        added to ``counts``."""
+        added to ``counts``; with ``want_post`` the pass's Λ is kept as ``post``."""
         out = dev.conv_siso(self.code, ext, scale=self.llr_scale, ext=self.prior[1:1 + self.nbits], ext_stride=self.code.n_tx,
-                            ext_clip=self.ext_clip, ref_info=ref_info, counts=counts, want_post=False)
-        self.decided = out["info_bits"]
+                            ext_clip=self.ext_clip, ref_info=ref_info, counts=counts, want_post=want_post)
+        self.decided, self.post = out["info_bits"], out["info_post"]
 
     # ---------------------------------------------------------------- blocks
     def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
@@ -92,8 +93,8 @@ class ConvSOQPSKLink(CodedSOQPSKLink):
         if self.outer == 1:
             llr, hard = self.soft(rows)
             dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
-            out = dev.conv_siso(self.code, llr, scale=self.llr_scale, ref_info=info, counts=self._last, want_post=False, want_ext=False)
-            self.decided = out["info_bits"]
+            out = dev.conv_siso(self.code, llr, scale=self.llr_scale, ref_info=info, counts=self._last, want_post=self.keep_post, want_ext=False)
+            self.decided, self.post = out["info_bits"], out["info_post"]
         else:
             self.begin(int(rows.shape[0]))
             for o in range(self.outer):
@@ -101,7 +102,7 @@ class ConvSOQPSKLink(CodedSOQPSKLink):
                 if o == 0:
                     dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
                 if o == self.outer - 1:
-                    self.decode(ext, info, self._last)
+                    self.decode(ext, info, self._last, want_post=self.keep_post)
                 elif self.per_pass:
                     self.decode(ext, info, self.pass_counts[o])
                 else:
