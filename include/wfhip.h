@@ -943,6 +943,57 @@ int wf_frame_gather(wf_ctx *ctx, const double *d_llr, int64_t nllr, const void *
 int wf_frame_scatter(wf_ctx *ctx, const float *d_ext, int64_t ext_stride, const void *d_lock, uint64_t marker, int32_t L, int32_t n_tx,
                      const uint8_t *d_pn, int64_t ncw, float marker_prior, float *d_prior, int64_t nprior, void *stream);
 
+/* ---- Carrier phase and frequency: the impairment and a feed-forward, decision-directed recovery ------------------------
+ * (The reference has no synchroniser; these entry points are defined here.  waveforms_amd/sync/carrier.py restates each in
+ * numpy: carrier_offset_host, map_branch_host, carrier_stat_host, carrier_track_host, derotate_host.)
+ * wf_carrier_offset_c128, the impairment at sample rate: out_k = in_k exp(j φ_k), in float64 and in this order:
+ *   t = nu * (double)(first_index + k)   (turns; nu in cycles per sample);   f = t - floor(t)   (exact)
+ *   φ_k = theta0 + (2π * f)              (one product, one sum);             out_k = in_k (cos φ_k + j sin φ_k)
+ * so a sample index of 1e9 loses no phase beyond the rounding of t itself.  In-place allowed.  n < 1, first_index < 0,
+ * first_index + n > 2^53, theta0 or nu not finite, a NULL pointer or samples not 16-byte aligned: WF_ERR_VALUE before the
+ * context is touched. */
+int wf_carrier_offset_c128(wf_ctx *ctx, const double *d_in_ri, int64_t n, double theta0, double nu, int64_t first_index,
+                           double *d_out_ri, void *stream);
+/* wf_viterbi4_soft on 48-byte rows (the packed rows drop the quadrature components the statistic below reads) with one more
+ * output per row: d_branch[k] = the branch b* of column k % 2 with the smallest
+ *   T_k(b) = (ã_k(start b) + inc_k(b)) + b̃_{k+1}(end b),
+ * b = 2 start + lsb the index in the column's list order (end = (start & 1) + 2 lsb in column 0, (start & 2) + lsb in
+ * column 1), ties to the smallest b: the section-k branch of a maximum-likelihood path.  d_llr and d_bits are BITWISE
+ * wf_viterbi4_soft's: the first launch, the proof and the repairs are the same code, only the last launch differs.
+ * Everything else (alignment, warm-up, chunking, options, counters, scratch) as wf_viterbi4_soft; a NULL d_branch or any
+ * argument wf_viterbi4_soft refuses: WF_ERR_VALUE before the context is touched. */
+int wf_viterbi4_soft_branch(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int differential, int warmup, double *d_llr,
+                            uint8_t *d_bits, uint8_t *d_branch, void *stream);
+/* The decision-directed phase statistic per window of W rows (W a multiple of 64, 64 .. 8192); nwin = ceil(ncalls / W).
+ * q_k = state_exp_term[start b*_k] * z_k[idx(out b*_k)] = x_k + j y_k with state_exp_term = [+j, -1, +1, -j]: x and y are
+ * signed components of z (no product is rounded); x_k = inc_k(b*_k) is the metric of the decided branch, so a coherent
+ * burst has X << 0 and a rotation of the rows by θ turns (X, Y) by θ.  d_stat[w] = (X_w, Y_w), float64, in exactly this order:
+ *   p_l = sum_i x[w W + 64 i + l]   (i increasing, started from +0; rows at or beyond ncalls contribute nothing), l < 64
+ *   for d = 32, 16, .., 1:  p_l = p_l + p_{l+d}  for l < d;          X_w = p_0;  Y_w likewise from y.
+ * d_branch: ncalls bytes, 0 .. 7 (wf_viterbi4_soft_branch's).  W outside its range, ncalls < 1, a NULL pointer, rows not
+ * 16-byte or d_stat not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_carrier_stat(wf_ctx *ctx, const double *d_rows, const uint8_t *d_branch, int64_t ncalls, int W, double *d_stat, void *stream);
+/* Statistics -> a phase trajectory, on the device.  d_stat_h: H x nwin x 2 float64, the statistics of H passes over the
+ * whole burst whose rows were derotated by h π / H first (wf_rows_derotate, phase0 = h π / H), h < H; H = 1: a refinement.
+ *   h*_w = argmin_h X_{h,w} (ties to the smallest h);  ψ_w = ((double)h*_w * π) / H + atan2(-Y, -X) at h*_w
+ *   u_0 = ψ_0;  u_w = u_{w-1} + wrap(ψ_w - ψ_{w-1}),  wrap(x) = x - π ceil(x / π - 1/2) in (-π/2, π/2]   (w increasing)
+ *   d_phase[w] = (sum of u_j, j = max(0, w - r) .. min(nwin - 1, w + r), j increasing, from +0) / the number of terms, r = (span - 1) / 2
+ * The unwrapping is modulo π: the trellis is symmetric under π, and a framed link's polarity σ absorbs what remains.
+ * d_phase: nwin float64, d_choice: nwin bytes (h*).  The u_w pass through the context's detector scratch.  atan2 is the
+ * device library's and the running sum u_w is taken as a blocked scan (segment sums, then offsets): this stage agrees with a
+ * host statement to rounding - within 8 * 2^-52 * max(1, |phase|) * nwin - not bitwise.  H outside 1 .. 256, nwin < 1, span
+ * even or < 1, a NULL pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_carrier_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double *d_phase, uint8_t *d_choice, void *stream);
+/* Derotate 48-byte rows: z_k <- z_k exp(-j (phase0 + φ_k)), all three values of a row.  φ_k interpolates d_phase linearly
+ * between the window centres w W + (W - 1) / 2 and is held flat outside the first and the last one:
+ *   t = ((double)k - (W - 1) / 2) / W;   t <= 0: φ = phase[0];   t >= nwin - 1: φ = phase[nwin - 1];
+ *   otherwise w = floor(t), f = t - w, φ = phase[w] + (f * (phase[w + 1] - phase[w]))        (each operation rounded once)
+ * d_phase NULL: φ = 0, a constant rotation (W and nwin are then not read).  In-place allowed.  ncalls < 1, phase0 not
+ * finite, W outside 64 .. 8192 in steps of 64 or nwin < 1 (with d_phase), a NULL ctx / d_rows / d_out, rows not 16-byte or
+ * d_phase not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_rows_derotate(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int W, const double *d_phase, int64_t nwin, double phase0,
+                     double *d_out, void *stream);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

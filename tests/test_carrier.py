@@ -1,0 +1,452 @@
+"""Carrier phase and frequency recovery (waveforms_amd/sync/carrier.py; include/wfhip.h: wf_carrier_offset_c128,
+wf_viterbi4_soft_branch, wf_carrier_stat, wf_carrier_track, wf_rows_derotate).
+
+CPU: the host statements against the soft detector's restatement (tests/test_soft_detector.py), brute force on short bursts,
+the decision-directed estimator on the oracle's PT rows, and ``recover_host`` at constant rotations and at the documented
+frequency limit.  GPU: every device stage against its host statement - branches and statistics bitwise, the trajectory and
+the rotations within bounds that follow from the arithmetic (stated at each test) - and the whole recovery end to end.
+"""
+import ctypes
+import itertools
+import math
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import test_soft_detector as TS
+from waveforms_amd.sync import carrier as C
+
+SPS = 8
+EPS = 2.0 ** -52
+NAMES = ("wf_carrier_offset_c128", "wf_viterbi4_soft_branch", "wf_carrier_stat", "wf_carrier_track", "wf_rows_derotate")
+
+
+def _pt_rows(oracle, n, ebn0=None, seed=3):
+    _bits, rows = TS._detection_rows(oracle, n, ebn0, "PT", seed)
+    return np.ascontiguousarray(rows, dtype=np.complex128).reshape(-1, 3)
+
+
+def _rot(rows, deg=0.0, turns_per_window=0.0, window=C.DEFAULT_WINDOW):
+    k = np.arange(rows.shape[0], dtype=np.float64)
+    return rows * np.exp(1j * (math.radians(deg) + 2.0 * math.pi * turns_per_window * k / window))[:, None]
+
+
+def _up_to_polarity(bits, genie, guard):
+    g = slice(guard, bits.size - guard)
+    return min(int(np.count_nonzero(bits[g] != genie[g])), int(np.count_nonzero(bits[g] != 1 - genie[g])))
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_carrier_entry_points_exported_bound_and_declared():
+    from pathlib import Path
+
+    from waveforms_amd import _hip, device
+
+    header = (Path(__file__).resolve().parent.parent / "include" / "wfhip.h").read_text()
+    lib = _hip.lib()
+    for name in NAMES:
+        assert name in _hip.SIGNATURES and hasattr(lib, name) and f"int {name}(" in header, name
+    for name in ("carrier_offset", "viterbi_soft_branch", "carrier_stat", "carrier_track", "rows_derotate"):
+        assert callable(getattr(device, name))
+    for name in ("map_branch_host", "carrier_stat_host", "carrier_track_host", "derotate_host", "recover_host", "carrier_offset_host"):
+        assert callable(getattr(C, name))
+    rec = C.CarrierRecovery()
+    assert (rec.window, rec.span, rec.hypotheses, rec.refine) == (256, 5, 8, 1)
+
+
+def test_carrier_argument_validation_without_a_gpu():
+    """Bad arguments return WF_ERR_VALUE before the context is touched (a fake context: no device exists here)."""
+    from waveforms_amd import _hip
+
+    lib = _hip.lib()
+    fake = ctypes.create_string_buffer(1 << 16)
+    buf = ctypes.create_string_buffer(1 << 14)
+    a = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 16
+    b, c, d = a + 4096, a + 8192, a + 12288
+    V = _hip.WF_ERR_VALUE
+    nan, inf = float("nan"), float("inf")
+    # wf_carrier_offset_c128(ctx, in, n, theta0, nu, first_index, out, stream)
+    for args in ((None, a, 10, 0.0, 0.0, 0, b), (fake, None, 10, 0.0, 0.0, 0, b), (fake, a, 10, 0.0, 0.0, 0, None), (fake, a, 0, 0.0, 0.0, 0, b),
+                 (fake, a, 10, nan, 0.0, 0, b), (fake, a, 10, 0.0, inf, 0, b), (fake, a, 10, 0.0, 0.0, -1, b), (fake, a, 10, 0.0, 0.0, 1 << 53, b),
+                 (fake, a + 8, 10, 0.0, 0.0, 0, b), (fake, a, 10, 0.0, 0.0, 0, b + 8)):
+        assert lib.wf_carrier_offset_c128(*args, None) == V, args
+    # wf_viterbi4_soft_branch(ctx, rows, ncalls, differential, warmup, llr, bits, branch, stream)
+    for args in ((None, a, 10, 1, 0, b, c, d), (fake, None, 10, 1, 0, b, c, d), (fake, a, 0, 1, 0, b, c, d), (fake, a, 10, 1, -1, b, c, d),
+                 (fake, a, 10, 1, 0, None, c, d), (fake, a, 10, 1, 0, b, None, d), (fake, a, 10, 1, 0, b, c, None), (fake, a + 8, 10, 1, 0, b, c, d),
+                 (fake, a, 10, 1, 0, b + 4, c, d)):
+        assert lib.wf_viterbi4_soft_branch(*args, None) == V, args
+    # wf_carrier_stat(ctx, rows, branch, ncalls, W, stat, stream)
+    for args in ((None, a, b, 10, 64, c), (fake, None, b, 10, 64, c), (fake, a, None, 10, 64, c), (fake, a, b, 10, 64, None), (fake, a, b, 0, 64, c),
+                 (fake, a + 8, b, 10, 64, c), (fake, a, b, 10, 64, c + 4)) + tuple((fake, a, b, 10, w, c) for w in (0, 32, 63, 65, 96, 8256, 16384, -64)):
+        assert lib.wf_carrier_stat(*args, None) == V, args
+    # wf_carrier_track(ctx, stat_h, H, nwin, span, phase, choice, stream)
+    for args in ((None, a, 1, 4, 1, b, c), (fake, None, 1, 4, 1, b, c), (fake, a, 1, 4, 1, None, c), (fake, a, 1, 4, 1, b, None), (fake, a, 0, 4, 1, b, c),
+                 (fake, a, 257, 4, 1, b, c), (fake, a, 1, 0, 1, b, c), (fake, a, 1, 4, 0, b, c), (fake, a, 1, 4, 2, b, c), (fake, a, 1, 4, -1, b, c),
+                 (fake, a + 4, 1, 4, 1, b, c), (fake, a, 1, 4, 1, b + 4, c)):
+        assert lib.wf_carrier_track(*args, None) == V, args
+    # wf_rows_derotate(ctx, rows, ncalls, W, phase, nwin, phase0, out, stream)
+    for args in ((None, a, 10, 64, b, 1, 0.0, c), (fake, None, 10, 64, b, 1, 0.0, c), (fake, a, 10, 64, b, 1, 0.0, None), (fake, a, 0, 64, b, 1, 0.0, c),
+                 (fake, a, 10, 64, b, 1, nan, c), (fake, a, 10, 64, None, 0, inf, c), (fake, a, 10, 96, b, 1, 0.0, c), (fake, a, 10, 64, b, 0, 0.0, c),
+                 (fake, a + 8, 10, 64, b, 1, 0.0, c), (fake, a, 10, 64, b, 1, 0.0, c + 8), (fake, a, 10, 64, b + 4, 1, 0.0, c)):
+        assert lib.wf_rows_derotate(*args, None) == V, args
+    # ... and the Python layer's own
+    for kw in ({"window": 96}, {"window": 32}, {"window": 16384}, {"span": 4}, {"span": 0}, {"hypotheses": 0}, {"hypotheses": 257}, {"refine": -1}):
+        with pytest.raises(ValueError):
+            C.CarrierRecovery(**kw)
+    with pytest.raises(ValueError):
+        C.carrier_stat_host(np.zeros((4, 3), dtype=np.complex128), np.zeros(4, dtype=np.uint8), 100)
+    with pytest.raises(ValueError):
+        C.carrier_track_host(np.zeros((1, 4, 2)), 2)
+
+
+def test_links_refuse_recovery_without_framing():
+    from waveforms_amd.encoding import ldpc
+    from waveforms_amd.encoding.coded import CodedSOQPSKLink, IterativeSOQPSKLink
+
+    code = ldpc.demo_code()
+    for cls in (CodedSOQPSKLink, IterativeSOQPSKLink):
+        with pytest.raises(ValueError, match="framing"):
+            cls(code, 2, recovery=C.CarrierRecovery())
+        with pytest.raises(ValueError):
+            cls(code, 2, carrier=(float("nan"), 0.0))
+
+
+@pytest.mark.parametrize("differential", [True, False])
+def test_map_branch_agrees_with_the_soft_restatement(oracle, differential):
+    """λ and bits are the soft detector's, and the decided branch's input bit is (λ < 0) wherever λ is not zero."""
+    rng = np.random.default_rng(5 + differential)
+    rows = _pt_rows(oracle, 1500, 2.0)
+    for z in (rows, 2.0 * (rng.standard_normal((301, 3)) + 1j * rng.standard_normal((301, 3)))):
+        llr, bits, branch = C.map_branch_host(z, differential)
+        want_llr, want_bits = TS.soft_restatement(oracle, z, differential)
+        assert np.array_equal(llr.view(np.uint64), want_llr.view(np.uint64)) and np.array_equal(bits, want_bits)
+        brs = TS._branches(oracle, differential)
+        inp = np.array([brs[k & 1][int(b)][3] for k, b in enumerate(branch)])
+        live = llr != 0.0
+        assert live.sum() > 0.9 * llr.size and np.array_equal(inp[live], (llr < 0)[live].astype(int))
+    # the module's own trellis tables are the reference trellis's
+    assert C._branches(differential) == [[tuple(t) for t in col] for col in brs]
+
+
+@pytest.mark.parametrize("differential", [True, False])
+def test_map_branch_equals_brute_force_on_short_bursts(oracle, differential):
+    """On 8 rows: b*_k = the branch of section k with the cheapest path through it, over every start state and every input
+    sequence, ties to the smallest b.  Integer-valued rows: every sum is exact."""
+    t = oracle.trellis_tables(TS.TRELLIS[differential])
+    rng = np.random.default_rng(23 + differential)
+    for trial in range(6):
+        n = 8
+        rows = rng.integers(-8, 9, (n, 3)) + 1j * rng.integers(-8, 9, (n, 3))
+        if trial == 5:
+            rows[:] = 0                                  # every path ties: branch 0 everywhere
+        inc = TS._increments(oracle, rows, differential)
+        bidx = {}
+        for c, brs in enumerate(TS._branches(oracle, differential)):
+            for (b, s, _e, i, _x) in brs:
+                bidx[(c, s, i)] = b
+        best = np.full((n, 8), np.inf)
+        for s0 in range(4):
+            for u in itertools.product((0, 1), repeat=n):
+                s, cost, used = s0, 0.0, []
+                for k in range(n):
+                    b = bidx[(k & 1, s, u[k])]
+                    used.append(b)
+                    cost += inc[k, b]
+                    s = int(t["next"][k & 1, s, u[k]])
+                for k in range(n):
+                    best[k, used[k]] = min(best[k, used[k]], cost)
+        _llr, _bits, branch = C.map_branch_host(rows, differential)
+        assert np.array_equal(branch, np.argmin(best, axis=1)), (trial, branch, np.argmin(best, axis=1))
+
+
+def test_estimator_on_noiseless_pt_rows(oracle):
+    """The whole-burst decision-directed estimate follows a rotation of 5 and 15 degrees to 0.01 degree once the estimate at 0
+    is taken off.  That offset is a property of the rows, not of the rotation: recorded here, discussed in DESIGN.md."""
+    rows = _pt_rows(oracle, 3001)
+    e0 = math.degrees(C.estimate_host(rows))
+    print(f"estimate at 0 degrees: {e0:.4f} degrees")
+    assert 1.5 < e0 < 2.7, e0                     # 2.01 in the issue's check, 2.10 on these rows: a couple of degrees, and positive
+    for deg in (5.0, 15.0):
+        est = math.degrees(C.estimate_host(_rot(rows, deg))) - e0
+        print(f"rotation {deg}: estimate - estimate(0) = {est:.6f}")
+        assert abs(est - deg) < 0.01, (deg, est)
+    # the same through the windowed stages with one window over the burst
+    _l, _b, br = C.map_branch_host(_rot(rows, 15.0))
+    phase, choice = C.carrier_track_host(C.carrier_stat_host(_rot(rows, 15.0), br, 8192)[None], 1)
+    assert phase.shape == (1,) and choice[0] == 0 and abs(math.degrees(phase[0]) - e0 - 15.0) < 0.01
+
+
+@pytest.fixture(scope="module")
+def genie(oracle):
+    rows = _pt_rows(oracle, 3001)
+    return rows, C.map_branch_host(rows)[1]
+
+
+@pytest.mark.parametrize("deg", [0.0, 40.0, 85.0, 130.0, 220.0])
+def test_recover_host_constant_rotation(genie, deg):
+    """Defaults (H = 8, W = 256, span 5, one refinement): the decisions after recovery are the unrotated rows' decisions, or
+    their complement (220 degrees is there for that: the recovery is modulo π), outside a guard of one window at each end."""
+    rows, want = genie
+    out, phase, choice = C.recover_host(_rot(rows, deg))
+    assert phase.shape == choice.shape == (-(-rows.shape[0] // C.DEFAULT_WINDOW),)
+    assert _up_to_polarity(C.map_branch_host(out)[1], want, C.DEFAULT_WINDOW) == 0
+    assert np.abs(_wrap_deg(np.degrees(phase) - deg)).max() < 5.0, np.degrees(phase)
+
+
+def _wrap_deg(x):
+    return x - 180.0 * np.round(x / 180.0)
+
+
+@pytest.mark.parametrize("sign", [1.0, -1.0])
+def test_recover_host_at_the_documented_frequency_limit(genie, sign):
+    """A linear drift of MAX_DRIFT_TURNS turns per window on top of 40 degrees, either direction."""
+    rows, want = genie
+    assert C.MAX_DRIFT_TURNS == 0.05
+    out, phase, _choice = C.recover_host(_rot(rows, 40.0, sign * C.MAX_DRIFT_TURNS))
+    assert _up_to_polarity(C.map_branch_host(out)[1], want, C.DEFAULT_WINDOW) == 0
+    slope = np.diff(phase) / (2.0 * math.pi)
+    # (the decisions above are the check; this only says the trajectory is the drift and not a wrap of it: the self-noise of a
+    #  256-row window is a degree or two, 0.005 turns, per phase)
+    assert np.abs(slope[2:-2] - sign * C.MAX_DRIFT_TURNS).max() < 0.02, slope
+
+
+def test_host_statements_at_their_edges():
+    """Window sums in the stated order, the unwrapping modulo π, the clipped mean and the flat ends of the interpolation."""
+    rng = np.random.default_rng(3)
+    rows = rng.standard_normal((200, 3)) + 1j * rng.standard_normal((200, 3))
+    branch = rng.integers(0, 8, 200).astype(np.uint8)
+    x, y = C.branch_terms_host(rows, branch)
+    st = C.carrier_stat_host(rows, branch, 64)
+    assert st.shape == (4, 2)
+    p = np.zeros(64)
+    p[:8] = x[192:200]                                   # the last window holds 8 rows: one term per lane
+    d = 32
+    while d:
+        p[:d] = p[:d] + p[d:2 * d]
+        d //= 2
+    assert st[3, 0] == p[0]
+    np.testing.assert_allclose(st[:, 1], [y[64 * w:64 * w + 64].sum() for w in range(4)], rtol=1e-12, atol=1e-12)
+    # a trajectory that climbs 100 degrees per window is read as -80 per window: modulo π, the nearest
+    th = np.radians(100.0) * np.arange(6)
+    stat = np.stack([-np.cos(th), -np.sin(th)], axis=1)[None]
+    phase, choice = C.carrier_track_host(stat, 1)
+    np.testing.assert_allclose(np.diff(phase), np.radians(-80.0), atol=1e-12)
+    assert not choice.any()
+    sm, _ = C.carrier_track_host(stat, 3)
+    np.testing.assert_allclose(sm, [(phase[0] + phase[1]) / 2] + [phase[j - 1:j + 2].sum() / 3 for j in range(1, 5)] + [(phase[4] + phase[5]) / 2], atol=1e-12)
+    # ties between hypotheses go to the smallest h
+    tie = np.zeros((3, 2, 2))
+    tie[:, :, 0] = -1.0
+    assert not C.carrier_track_host(tie, 1)[1].any()
+    phi = C.interpolate_phase_host(256, 64, np.array([1.0, 2.0, 4.0, 4.0]))
+    assert (phi[:32] == 1.0).all() and (phi[224:] == 4.0).all() and phi[32] == 1.0 + 0.5 / 64 and abs(phi[127] - 3.0 + 1.0 / 64) < 1e-12
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+@pytest.fixture
+def ctx():
+    from waveforms_amd import _hip
+
+    handle = _hip.new_ctx()
+    _hip.set_option(handle, _hip.WF_OPT_DET_FINAL_VERIFY, 1)
+    yield handle
+    _hip.free_ctx(handle)
+
+
+def _counters(dev, handle):
+    return dev.viterbi_unmerged(reset=True, ctx=handle), dev.viterbi_repaired(reset=True, ctx=handle)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ebn0", [0.0, 10.0])
+def test_soft_branch_bitwise_on_oracle_rows(oracle, ctx, ebn0):
+    """20 001 rows in chunks of 64 (313 chunks): λ and bits bitwise wf_viterbi4_soft's, the branch exactly the host statement's,
+    with the default warm-up and through the repairs of a 2-row warm-up."""
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rows = _pt_rows(oracle, 20_002, ebn0)[:20_001]
+    want_llr, want_bits, want_branch = C.map_branch_host(rows)
+    _hip.set_option(ctx, _hip.WF_OPT_SOFT_CHUNK_CALLS, 64)
+    d_rows = _hip.to_device(rows)
+    _counters(dev, ctx)
+    for warmup in (0, 2):
+        ref_llr, ref_bits = dev.viterbi_soft(d_rows, True, warmup, 48, ctx=ctx)
+        _counters(dev, ctx)
+        llr, bits, branch = dev.viterbi_soft_branch(d_rows, True, warmup, ctx=ctx)
+        unproven, repaired = _counters(dev, ctx)
+        assert unproven == 0
+        assert np.array_equal(_hip.to_host(llr).view(np.uint64), _hip.to_host(ref_llr).view(np.uint64))
+        assert np.array_equal(_hip.to_host(bits), _hip.to_host(ref_bits))
+        assert np.array_equal(_hip.to_host(llr).view(np.uint64), want_llr.view(np.uint64)) and np.array_equal(_hip.to_host(bits), want_bits)
+        assert np.array_equal(_hip.to_host(branch), want_branch), int(np.count_nonzero(_hip.to_host(branch) != want_branch))
+        if warmup == 2:
+            assert repaired > 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("differential", [True, False])
+def test_soft_branch_short_bursts_and_exact_ties(ctx, differential):
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rng = np.random.default_rng(17)
+    for n in (1, 2, 63, 200):
+        for rows in (2.0 * (rng.standard_normal((n, 3)) + 1j * rng.standard_normal((n, 3))), np.zeros((n, 3), dtype=np.complex128),
+                     (rng.integers(-1, 2, (n, 3)) + 1j * rng.integers(-1, 2, (n, 3))).astype(np.complex128)):
+            want_llr, want_bits, want_branch = C.map_branch_host(rows, differential)
+            assert rows.any() or not want_branch.any()            # all-zero rows: every sum ties, the smallest b wins
+            for chunk in (0, 1, 7):
+                _hip.set_option(ctx, _hip.WF_OPT_SOFT_CHUNK_CALLS, chunk)
+                llr, bits, branch = dev.viterbi_soft_branch(_hip.to_device(rows), differential, 1, ctx=ctx)
+                assert np.array_equal(_hip.to_host(llr).view(np.uint64), want_llr.view(np.uint64)), (n, chunk)
+                assert np.array_equal(_hip.to_host(bits), want_bits) and np.array_equal(_hip.to_host(branch), want_branch), (n, chunk)
+                assert _counters(dev, ctx)[0] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("window", [64, 256])
+def test_carrier_stat_bitwise(ctx, window):
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rng = np.random.default_rng(window)
+    for n in (1, window - 1, window, 5 * window + 77, 2000):
+        rows = rng.standard_normal((n, 3)) + 1j * rng.standard_normal((n, 3))
+        rows[0] = 0.0                                     # signed zeros among the terms
+        branch = rng.integers(0, 8, n).astype(np.uint8)
+        want = C.carrier_stat_host(rows, branch, window)
+        got = _hip.to_host(dev.carrier_stat(_hip.to_device(rows), _hip.to_device(branch), window, ctx=ctx))
+        assert got.shape == want.shape == (-(-n // window), 2)
+        assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (n, np.abs(got - want).max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("span", [1, 5])
+@pytest.mark.parametrize("H", [1, 8])
+def test_carrier_track_on_the_devices_own_statistics(oracle, ctx, H, span):
+    """choice exact wherever the two best X differ; phase within 8 * 2^-52 * max(1, |phase|) * nwin of the host statement: each of
+    the nwin accumulated terms carries a few ulp of atan2 and of the wrap, and the sums add one rounding each."""
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rows = _rot(_pt_rows(oracle, 4097, 8.0), 65.0, 0.03)
+    for n, window in ((rows.shape[0], 64), (rows.shape[0], 256), (200, 256)):       # the last one: nwin = 1
+        d_rows = _hip.to_device(rows[:n])
+        nwin = -(-n // window)
+        stat = _hip.empty((H, nwin, 2), "float64")
+        for h in range(H):
+            work = dev.rows_derotate(d_rows, phase0=h * math.pi / H, ctx=ctx)
+            dev.carrier_stat(work, dev.viterbi_soft_branch(work, True, ctx=ctx)[2], window, out=stat[h], ctx=ctx)
+        phase, choice = dev.carrier_track(stat, span, ctx=ctx)
+        phase, choice, st = _hip.to_host(phase), _hip.to_host(choice), _hip.to_host(stat)
+        want_phase, want_choice = C.carrier_track_host(st, span)
+        xs = np.sort(st[:, :, 0], axis=0)
+        clear = np.ones(nwin, dtype=bool) if H == 1 else xs[0] != xs[1]
+        assert clear.all() and np.array_equal(choice, want_choice)
+        bound = 8.0 * EPS * np.maximum(1.0, np.abs(want_phase)) * nwin
+        assert (np.abs(phase - want_phase) <= bound).all(), (np.abs(phase - want_phase).max(), bound.min())
+        if H == 8 and window == 256 and n > 256:
+            assert np.abs(_wrap_deg(np.degrees(want_phase[2:-2]) - 65.0 - 0.03 * 360.0 * (np.arange(nwin)[2:-2] + 0.5))).max() < 8.0
+
+
+def _rot_bound(z, ang):
+    """|device - numpy| per element: both round sin, cos and the four products and two sums of a complex product, together
+    under 4 * 2^-52 |z|; a differently rounded argument would add 2^-52 |φ| |z| (the statements fix the argument's arithmetic, so
+    this term is slack)."""
+    return (4.0 * EPS + EPS * np.abs(ang)) * np.abs(z)
+
+
+@pytest.mark.gpu
+def test_rows_derotate_against_numpy(ctx):
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rng = np.random.default_rng(9)
+    n, window = 1000, 64
+    nwin = -(-n // window)
+    rows = 3.0 * (rng.standard_normal((n, 3)) + 1j * rng.standard_normal((n, 3)))
+    phase = np.cumsum(rng.uniform(-0.4, 0.4, nwin)) + 50.0
+    d_rows = _hip.to_device(rows)
+    for ph, phase0, w in ((phase, 0.0, window), (phase, -1.25, window), (None, 2.5, 64), (phase[:1], 0.3, 1024), (phase[:4], 0.0, 256)):
+        want = C.derotate_host(rows, w, ph, phase0)
+        ang = phase0 + (0.0 if ph is None else C.interpolate_phase_host(n, w, ph)) + np.zeros(n)
+        got = _hip.to_host(dev.rows_derotate(d_rows, w, None if ph is None else _hip.to_device(ph), phase0, ctx=ctx), True)
+        assert (np.abs(got - want) <= _rot_bound(rows, ang[:, None])).all(), np.abs(got - want).max()
+    # flat ends: the rows in front of the first centre and behind the last one turn by phase[0] and phase[-1]
+    ang = C.interpolate_phase_host(n, window, phase)
+    assert (ang[:32] == phase[0]).all() and (ang[(nwin - 1) * window + 32:] == phase[-1]).all()
+    # in place
+    buf = d_rows.clone()
+    out = dev.rows_derotate(buf, window, _hip.to_device(phase), 0.0, out=buf, ctx=ctx)
+    assert out.data_ptr() == buf.data_ptr()
+    assert (np.abs(_hip.to_host(buf, True) - C.derotate_host(rows, window, phase)) <= _rot_bound(rows, ang[:, None])).all()
+
+
+@pytest.mark.gpu
+def test_carrier_offset_against_numpy_and_the_exact_turn_count():
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rng = np.random.default_rng(4)
+    n = 100_003
+    x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+    d_x = _hip.to_device(x)
+    for theta0, nu, first in ((0.7, 1.2345678e-3, 10 ** 9), (-2.0, -3.3e-5, 10 ** 9), (0.0, 0.0, 0), (1.0, 0.25, 7)):
+        want = C.carrier_offset_host(x, theta0, nu, first)
+        got = _hip.to_host(dev.carrier_offset(d_x, theta0, nu, first), True)
+        phi = C.carrier_phase_host(n, theta0, nu, first)             # the element's own angle, as the host statement forms it
+        err, bound = np.abs(got - want), _rot_bound(x, phi)
+        print(f"theta0 {theta0}, nu {nu}, first {first}: max |device - numpy| / bound = {(err / bound).max():.3f}, max error / (2^-52 |z|) = {(err / (EPS * np.abs(x))).max():.3f}")
+        assert (err <= bound).all(), (theta0, nu, first, err.max())
+        # no phase is lost at index 1e9: against the exact fraction of nu * (first + k), the device is off by the rounding of that
+        # product to float64 (2^-53 of the turn count, in turns) and the rotation's own bound
+        for k in (0, 1, 12_345, n - 1):
+            turns = Fraction(nu) * (first + k)
+            fr = float(turns - math.floor(turns))
+            exact = x[k] * np.exp(1j * (theta0 + 2.0 * math.pi * fr))
+            slack = 2.0 * math.pi * 2.0 ** -53 * abs(float(turns)) * abs(x[k]) + 8.0 * EPS * abs(x[k])
+            assert abs(got[k] - exact) <= slack, (k, abs(got[k] - exact), slack)
+    buf = d_x.clone()
+    dev.carrier_offset(buf, 0.7, 1.2345678e-3, 10 ** 9, out=buf)
+    assert (np.abs(_hip.to_host(buf, True) - C.carrier_offset_host(x, 0.7, 1.2345678e-3, 10 ** 9)) <= _rot_bound(x, C.carrier_phase_host(n, 0.7, 1.2345678e-3, 10 ** 9))).all()
+
+
+CASES = [(40.0, 0.0), (130.0, 0.0), (40.0, 0.04)]
+
+
+@pytest.fixture(scope="module")
+def burst(oracle):
+    """4096 PT rows, noiseless and at 8 dB, with the genie decisions of each."""
+    out = {}
+    for ebn0 in (None, 8.0):
+        rows = _pt_rows(oracle, 4097, ebn0)
+        assert rows.shape[0] == 4096
+        out[ebn0] = (rows, C.map_branch_host(rows)[1])
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ebn0", [None, 8.0])
+@pytest.mark.parametrize("deg,drift", CASES)
+def test_recover_end_to_end(oracle, burst, ctx, ebn0, deg, drift):
+    from waveforms_amd import _hip
+    from waveforms_amd import device as dev
+
+    rows, want = burst[ebn0]
+    bad = _rot(rows, deg, drift)
+    rec = C.CarrierRecovery()
+    out, phase, choice = rec.recover(_hip.to_device(bad), True, ctx=ctx)
+    host_out, host_phase, host_choice = C.recover_host(bad)
+    assert np.array_equal(_hip.to_host(choice), host_choice)
+    np.testing.assert_allclose(_hip.to_host(phase), host_phase, rtol=0, atol=1e-9)     # (the stages' own tests hold the bounds)
+    _llr, bits, _br = dev.viterbi_soft_branch(out, True, ctx=ctx)
+    bits, out = _hip.to_host(bits), _hip.to_host(out, True)
+    assert np.array_equal(bits, TS.soft_restatement(oracle, out, True)[1])       # the tests' own restatement, not the package's
+    assert _counters(dev, ctx)[0] == 0
+    errs = _up_to_polarity(bits, want, rec.window)
+    print(f"Eb/N0 {ebn0}, {deg} degrees, drift {drift}: {errs} decisions differ from the genie's outside the guard")
+    if ebn0 is None:
+        assert errs == 0
+        assert _up_to_polarity(C.map_branch_host(bad)[1], want, rec.window) > 500      # without the recovery the burst is lost

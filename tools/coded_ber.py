@@ -6,6 +6,7 @@ decoder's speed; prints ONE JSON line.
                               [--framed [--lead-bits J] [--marker-prior X]] [--live-only [--guard G]]
     python tools/coded_ber.py --code conv-k3|conv-k7 [--info-bits K] [--interleave] [--outer N --damping D] [--ebn0 ...]
     python tools/coded_ber.py --code conv-k3|conv-k7 --rs 16|8 [--rs-depth I] [--rs-n N] [--rs-erasures F [--rs-erase-below X]] ...
+    python tools/coded_ber.py --carrier-phase DEG --carrier-freq NU --recover [--carrier-window W --carrier-hyp H] [--ebn0 ...]
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -54,6 +55,14 @@ reliability below ``--rs-erase-below``, from the last inner pass's Λ) and decod
 runs on the SAME decisions of the same blocks, and stays the ``"rs"`` entry.  Every point gains ``"rs_erasures"``: BER and FER,
 flagged failures, miscorrections, symbols corrected, erasures declared / filled, and from the same timed blocks the device-event
 times of ``rs_mark_erasures``, of ``rs_decode`` with erasures and of ``rs_decode`` without, with their ratio.
+
+With ``--carrier-phase DEG`` / ``--carrier-freq NU`` (cycles per sample) and ``--recover`` (SOQPSK-TG, LDPC codes) the tool runs
+three FRAMED CodedSOQPSKLink on the same blocks and prints three curves: ``genie`` (no carrier offset: today's link),
+``impaired`` (the offset, no recovery) and ``recovered`` (the offset and ``CarrierRecovery`` with ``--carrier-window`` rows per
+window, ``--carrier-hyp`` hypotheses, ``--carrier-span``, ``--carrier-refine``).  It also prints the recovery's kernel times per
+block (device events around every stage, summed over the passes, ``--steps`` blocks after one warm-up) beside one plain soft
+detection of the same rows, and ``loss_db_at_fer_1e-2``: recovered minus genie, both interpolated in log FER (null where a
+curve does not cross 1e-2 inside the sweep).
 """
 import argparse
 import json
@@ -110,6 +119,88 @@ def live_point(full, lv, differ, code, ebn0, first_block, steps, ncw):
             "live_per_pass": [{"windows": w, "live_rows": r, "open_on_entry": n} for w, r, n in lv.live_results()],
             "burst_rows": int(lv.prior.numel()), "final_decisions_differ": int(differ),
             "ms_per_block": ms(1), "full_loop_ms_per_block_same_run": ms(0)}
+
+
+def _ebn0_at_fer(points, key, target=1e-2):
+    """Eb/N0 where the curve ``key`` crosses ``target``, interpolated in log10 FER between the sweep's points (None: no crossing)."""
+    pts = sorted((p["ebn0_info_db"], p[key]["fer"]) for p in points)
+    for (e0, f0), (e1, f1) in zip(pts, pts[1:]):
+        if f0 >= target > f1:
+            if f1 <= 0.0:
+                f1 = 0.1 * target / max(1, points[0]["codewords"])       # (no error seen: the crossing is bounded, not located)
+            return e0 + (e1 - e0) * (np.log10(f0) - np.log10(target)) / (np.log10(f0) - np.log10(f1))
+    return None
+
+
+def main_carrier(args) -> None:
+    """The ``--recover`` form: genie, impaired and recovered framed links on the same blocks."""
+    import math
+
+    import torch
+
+    from waveforms_amd import device as dev
+    from waveforms_amd.encoding import ldpc
+    from waveforms_amd.encoding.coded import CodedSOQPSKLink
+    from waveforms_amd.encoding.framing import Framing
+    from waveforms_amd.sync.carrier import MAX_DRIFT_TURNS, CarrierRecovery
+
+    torch.cuda.set_device(0)
+    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
+    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
+    fr = Framing(code)
+    rec = CarrierRecovery(args.carrier_window, args.carrier_span, args.carrier_hyp, args.carrier_refine)
+    carrier = (math.radians(args.carrier_phase), args.carrier_freq)
+    kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
+    links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, carrier=carrier, **kw),
+             "recovered": CodedSOQPSKLink(code, per, carrier=carrier, recovery=rec, **kw)}
+    sps = links["genie"].sps
+    out = {"tool": "coded_ber", "form": "carrier", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
+           "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
+           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
+                       "drift_turns_per_window": abs(args.carrier_freq) * sps * rec.window, "documented_limit_turns_per_window": MAX_DRIFT_TURNS},
+           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine}, "points": []}
+    for e in args.ebn0:
+        point = {"ebn0_info_db": e}
+        b = 0
+        for name, lk in links.items():
+            lk.reset_counts()
+            b = 0
+            while b * per < args.codewords:
+                lk.run_block(e, seed=1, stream_id=b)
+                b += 1
+            be, fe, nc, m, mean_it = lk.result()
+            ue, um = lk.uncoded_result()
+            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
+                           "mean_iters": round(mean_it, 3), "uncoded_ber": ue / um, "wrong_locks": lk.sync_result()[1]}
+        point["codewords"] = b * per
+        # the recovery's stages on one burst, each bracketed by device events, beside one plain soft detection
+        lk = links["recovered"]
+        rows, _ = lk.front_end(dev.ldpc_encode(code, lk.info_bits(b)), e, 1, b)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        tot, soft_ms = {}, 0.0
+        rec.times = True
+        for s in range(args.steps + 1):
+            rec.recover(rows, True)
+            t = rec.stage_times()
+            ev[0].record()
+            dev.viterbi_soft(rows, True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            if s:                                                         # (the first round warms up)
+                soft_ms += ev[0].elapsed_time(ev[1])
+                for k, v in t.items():
+                    tot[k] = tot.get(k, 0.0) + v
+        rec.times = False
+        n = max(args.steps, 1)
+        point["recovery_ms_per_block"] = {k: round(v / n, 4) for k, v in tot.items()}
+        point["recovery_ms_per_block"]["total"] = round(sum(tot.values()) / n, 4)
+        point["soft_detector_ms"] = round(soft_ms / n, 4)
+        point["burst_rows"] = int(rows.shape[0])
+        out["points"].append(point)
+    g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
+    out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
+    out["loss_db_at_fer_1e-2"] = None if g is None or r is None else round(r - g, 3)
+    print(json.dumps(out))
 
 
 def main_conv(args) -> None:
@@ -278,7 +369,20 @@ def main() -> None:
     ap.add_argument("--marker-prior", type=float, default=None, help="prior of the marker rows in the framed loop (default ext_sat)")
     ap.add_argument("--live-only", action="store_true", help="also run the iterative loop(s) with the detector on the live windows only")
     ap.add_argument("--guard", type=int, default=128, help="guard rows of --live-only")
+    ap.add_argument("--carrier-phase", type=float, default=0.0, help="carrier phase offset of the modulated signal, degrees")
+    ap.add_argument("--carrier-freq", type=float, default=0.0, help="carrier frequency offset, cycles per sample")
+    ap.add_argument("--recover", action="store_true", help="genie, impaired and recovered framed links on the same blocks (CarrierRecovery)")
+    ap.add_argument("--carrier-window", type=int, default=256, help="--recover: rows per window")
+    ap.add_argument("--carrier-hyp", type=int, default=8, help="--recover: coarse hypotheses")
+    ap.add_argument("--carrier-span", type=int, default=5, help="--recover: windows of the centred mean")
+    ap.add_argument("--carrier-refine", type=int, default=1, help="--recover: refinement passes")
     args = ap.parse_args()
+    if args.recover or args.carrier_phase or args.carrier_freq:
+        if not args.recover:
+            ap.error("--carrier-phase / --carrier-freq go with --recover")
+        if args.waveform != "soqpsk" or args.code.startswith("conv") or args.outer or args.live_only:
+            ap.error("--recover is the framed CodedSOQPSKLink's: --waveform soqpsk, an LDPC code, no --outer / --live-only")
+        return main_carrier(args)
     if args.live_only and (args.waveform != "soqpsk" or args.outer < 1):
         ap.error("--live-only is the SOQPSK-TG loop's: it needs --waveform soqpsk and --outer N")
     if args.code.startswith("conv"):

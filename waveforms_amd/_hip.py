@@ -130,6 +130,11 @@ SIGNATURES = {
     "wf_frame_search": (c_int, [_P, _P, c_int64, c_uint64, ctypes.c_int32, c_int64, _P, _P, _P]),
     "wf_frame_gather": (c_int, [_P, _P, c_int64, _P, ctypes.c_int32, ctypes.c_int32, _P, c_int64, _P, _P]),
     "wf_frame_scatter": (c_int, [_P, _P, c_int64, _P, c_uint64, ctypes.c_int32, ctypes.c_int32, _P, c_int64, ctypes.c_float, _P, c_int64, _P]),
+    "wf_carrier_offset_c128": (c_int, [_P, _P, c_int64, c_double, c_double, c_int64, _P, _P]),
+    "wf_viterbi4_soft_branch": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P, _P, _P]),
+    "wf_carrier_stat": (c_int, [_P, _P, _P, c_int64, c_int, _P, _P]),
+    "wf_carrier_track": (c_int, [_P, _P, c_int, c_int64, c_int, _P, _P, _P]),
+    "wf_rows_derotate": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_double, _P, _P]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

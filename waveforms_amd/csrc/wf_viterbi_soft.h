@@ -153,6 +153,37 @@ __device__ __forceinline__ double soft_llr(const double a[4], double b[4], const
     return m1 - m0;
 }
 
+// soft_llr, and *branch = the branch b* (list order, b = 2 start + lsb) with the smallest of the eight sums
+// T(b) = (a(start b) + inc(b)) + b(end b) it forms, ties to the smallest b
+template <int COL, int DIFF, bool AP>
+__device__ __forceinline__ double soft_llr_branch(const double a[4], double b[4], const vit_comp &q, double pi, int *branch)
+{
+    double ia[4], ib[4], t[8];
+    soft_incs<COL, DIFF, false>(q, 0.0, ia, ib);
+    double m0 = __builtin_inf(), m1 = __builtin_inf();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int sa = COL == 0 ? (e & 1) : (e & 2), sb = COL == 0 ? (e & 1) + 2 : (e & 2) + 1;
+        const int lsb = COL == 0 ? e >> 1 : e & 1;
+        const double ta = (a[sa] + ia[e]) + b[e], tb = (a[sb] + ib[e]) + b[e];
+        if (soft_inp<COL, DIFF>(e, 0)) m1 = fmin(m1, ta); else m0 = fmin(m0, ta);
+        if (soft_inp<COL, DIFF>(e, 1)) m1 = fmin(m1, tb); else m0 = fmin(m0, tb);
+        t[2 * sa + lsb] = ta;
+        t[2 * sb + lsb] = tb;
+    }
+    int best = 0;
+    double tv = t[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) {
+        const bool lt = t[i] < tv;
+        best = lt ? i : best;
+        tv = lt ? t[i] : tv;
+    }
+    *branch = best;
+    soft_bwd<COL, DIFF, AP>(b, q, pi);
+    return m1 - m0;
+}
+
 // ---- a lane's chunk and its walks --------------------------------------------------------------------------------------------
 template <bool PACKED>
 __device__ __forceinline__ const double2 *soft_row(const double *rows, int64_t k)
@@ -278,6 +309,27 @@ __device__ __forceinline__ void soft_llr_body(const double *rows, const soft_pri
         const double lam = r & 1 ? soft_llr<1, DIFF, AP>(m, b, vit_components<1, PACKED>(z), pi) : soft_llr<0, DIFF, AP>(m, b, vit_components<0, PACKED>(z), pi);
         out[r] = lam;
         bits[r] = lam + pi < 0.0 ? 1 : 0;
+    }
+}
+
+// The last launch of wf_viterbi4_soft_branch: soft_llr_body, and the arg-min branch of every row beside its λ.
+template <bool PACKED, int DIFF, bool AP>
+__device__ __forceinline__ void soft_branch_body(const double *rows, const soft_prior_t<AP> &pr, const soft_chunk &k, const double *bedge, const double *alpha,
+                                                 double *out, uint8_t *bits, uint8_t *branch)
+{
+    double b[4], m[4];
+    soft_win_t<AP> w;
+    soft_get4(bedge + 8 * k.brec, b);
+    for (int64_t r = k.e - 1; r >= k.a; --r) {
+        soft_get4(alpha + 4 * ((r - k.a) * k.lanes + k.lane), m);
+        const double2 *z = soft_row<PACKED>(rows, r);
+        const double pi = soft_prior_at(pr, w, r);
+        int br;
+        const double lam = r & 1 ? soft_llr_branch<1, DIFF, AP>(m, b, vit_components<1, PACKED>(z), pi, &br)
+                                 : soft_llr_branch<0, DIFF, AP>(m, b, vit_components<0, PACKED>(z), pi, &br);
+        out[r] = lam;
+        bits[r] = lam + pi < 0.0 ? 1 : 0;
+        branch[r] = (uint8_t)br;
     }
 }
 

@@ -23,8 +23,8 @@
 // The result is bitwise the definition whatever `warmup` and the chunking; the warm-up only sets how often the
 // repairs run.
 //
-// This file owns the definition above, the plain kernels and the entry points wf_viterbi4_soft and
-// wf_viterbi4_soft_geometry.  The trellis steps and the walks of the three launches live in wf_viterbi_soft.h, shared with
+// This file owns the definition above, the plain kernels and the entry points wf_viterbi4_soft, wf_viterbi4_soft_geometry
+// and wf_viterbi4_soft_branch (the same launches with soft_branch_kernel as the last one: the decided branch per row).  The trellis steps and the walks of the three launches live in wf_viterbi_soft.h, shared with
 // wf_viterbi_soft_apriori.hip and wf_viterbi_live.hip; the kernels here are its AP = false form.  Without a prior no
 // branch's input bit enters the recursions, so only the last launch carries DIFF.
 #include "wf_viterbi_soft.h"
@@ -57,6 +57,17 @@ __global__ __launch_bounds__(SOFT_THREADS) void soft_llr_kernel(const double *__
     soft_llr_body<PACKED, DIFF, false>(rows, soft_no_prior{}, soft_burst_chunk(c, ch, n, nch), bedge, alpha, llr, bits);
 }
 
+// the last launch of wf_viterbi4_soft_branch (48-byte rows only: the packed rows drop the quadrature components its user reads)
+template <int DIFF>
+__global__ __launch_bounds__(SOFT_THREADS) void soft_branch_kernel(const double *__restrict__ rows, int64_t n, int ch, int64_t nch,
+                                                                 const double *__restrict__ bedge, const double *__restrict__ alpha,
+                                                                 double *__restrict__ llr, uint8_t *__restrict__ bits, uint8_t *__restrict__ branch)
+{
+    const int64_t c = (int64_t)blockIdx.x * SOFT_THREADS + threadIdx.x;
+    if (c >= nch) return;
+    soft_branch_body<false, DIFF, false>(rows, soft_no_prior{}, soft_burst_chunk(c, ch, n, nch), bedge, alpha, llr, bits, branch);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 
 extern "C" int wf_viterbi4_soft_geometry(wf_ctx *ctx, int64_t ncalls, int warmup, int64_t *h_geom)
@@ -71,7 +82,7 @@ extern "C" int wf_viterbi4_soft_geometry(wf_ctx *ctx, int64_t ncalls, int warmup
 }
 
 template <bool PACKED, int DIFF>
-static int soft_run(wf_ctx *ctx, const double *rows, int64_t n, const soft_geom &g, double *llr, uint8_t *bits, hipStream_t s)
+static int soft_run(wf_ctx *ctx, const double *rows, int64_t n, const soft_geom &g, double *llr, uint8_t *bits, hipStream_t s, uint8_t *branch = nullptr)
 {
     double *fedge = ctx->d_vit_edge, *bedge = fedge + g.off_b, *alpha = fedge + g.off_alpha;
     const unsigned grid = (unsigned)((g.nch + SOFT_THREADS - 1) / SOFT_THREADS);
@@ -84,6 +95,13 @@ static int soft_run(wf_ctx *ctx, const double *rows, int64_t n, const soft_geom 
                                ctx->d_vit_unmerged, mode);
         });
         if (rc) return rc;
+    }
+    if constexpr (!PACKED) {
+        if (branch) {
+            hipLaunchKernelGGL((soft_branch_kernel<DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, n, g.ch, g.nch, bedge, alpha, llr, bits, branch);
+            WF_LAUNCH_CHECK();
+            return WF_OK;
+        }
     }
     hipLaunchKernelGGL((soft_llr_kernel<PACKED, DIFF>), dim3(grid), dim3(SOFT_THREADS), 0, s, rows, n, g.ch, g.nch, bedge, alpha, llr, bits);
     WF_LAUNCH_CHECK();
@@ -104,4 +122,21 @@ extern "C" int wf_viterbi4_soft(wf_ctx *ctx, const double *d_rows, int64_t ncall
     return soft_dispatch(row_bytes, differential, [&](auto packed, auto diff) {
         return soft_run<decltype(packed)::value, decltype(diff)::value>(ctx, d_rows, ncalls, g, d_llr, d_bits, s);
     });
+}
+
+// wf_viterbi4_soft on 48-byte rows with the arg-min branch of every row (include/wfhip.h): the same first launch, proof and
+// repairs; only the last launch differs (soft_branch_body).
+extern "C" int wf_viterbi4_soft_branch(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int differential, int warmup, double *d_llr, uint8_t *d_bits,
+                                       uint8_t *d_branch, void *stream)
+{
+    static const char who[] = "wf_viterbi4_soft_branch";
+    int rc = soft_check_args(who, ctx, d_rows, ncalls, 48, warmup, nullptr, 0.0, nullptr, d_llr, d_bits, "rows must be 16-byte and llr 8-byte aligned");
+    if (rc) return rc;
+    WF_REQUIRE(d_branch, "%s: NULL argument", who);
+    const soft_geom g = soft_geometry(ctx, ncalls, warmup);
+    rc = soft_reserve(who, ctx, g.nch, g.words);
+    if (rc) return rc;
+    hipStream_t s = wf_stream(stream);
+    if (differential) return soft_run<false, 1>(ctx, d_rows, ncalls, g, d_llr, d_bits, s, d_branch);
+    return soft_run<false, 0>(ctx, d_rows, ncalls, g, d_llr, d_bits, s, d_branch);
 }

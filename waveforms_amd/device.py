@@ -237,6 +237,96 @@ def viterbi_soft_apriori(rows, apriori=None, apriori_scale: float = 1.0, differe
     return ext[:ncalls], bits[:ncalls]
 
 
+def _rows48(rows) -> int:
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    nbytes = rows.numel() * rows.element_size()
+    if nbytes % 48 or nbytes == 0 or rows.dtype != _hip.torch().float64:
+        raise ValueError(f"{nbytes} bytes of rows are not a whole number of 48-byte float64 rows")
+    return nbytes // 48
+
+
+def carrier_offset(signal, theta0: float, nu: float, first_index: int = 0, out=None):
+    """The carrier impairment at sample rate (``wf_carrier_offset_c128``; include/wfhip.h states the definition): out_k = in_k
+    exp(j (theta0 + 2π frac(nu (first_index + k)))), ``nu`` in cycles per sample.  ``signal``: contiguous device float64[n, 2];
+    ``out=signal`` works in place."""
+    torch = _hip.torch()
+    if signal.dtype != torch.float64 or not signal.is_contiguous() or signal.numel() % 2 or signal.numel() == 0:
+        raise ValueError("signal must be contiguous float64[n, 2]")
+    n = signal.numel() // 2
+    if out is None:
+        out = _hip.empty((n, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != signal.numel():
+        raise ValueError("out must be contiguous float64[n, 2]")
+    _hip.check(_hip.lib().wf_carrier_offset_c128(_hip.ctx(), _hip.ptr(signal), n, float(theta0), float(nu), int(first_index), _hip.ptr(out),
+                                                 _hip.stream()))
+    return out
+
+
+def viterbi_soft_branch(rows, differential: bool = True, warmup: int = 0, ctx=None):
+    """``viterbi_soft`` on 48-byte rows with the decided branch of every row (``wf_viterbi4_soft_branch``; include/wfhip.h
+    states the definition) -> (llr f64[ncalls], bits u8[ncalls], branch u8[ncalls]) on device.  llr and bits are bitwise
+    ``viterbi_soft``'s; branch[k] = 2 start + lsb of the section-k branch of a maximum-likelihood path."""
+    ncalls = _rows48(rows)
+    llr = _hip.empty(ncalls, "float64")
+    bits = _hip.empty(ncalls + 16, "uint8")
+    branch = _hip.empty(ncalls + 16, "uint8")
+    _hip.check(_hip.lib().wf_viterbi4_soft_branch(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(bool(differential)), int(warmup),
+                                                  _hip.ptr(llr), _hip.ptr(bits), _hip.ptr(branch), _hip.stream()))
+    return llr, bits[:ncalls], branch[:ncalls]
+
+
+def carrier_stat(rows, branch, window: int, out=None, ctx=None):
+    """The decision-directed phase statistic per window of ``window`` rows (``wf_carrier_stat``; include/wfhip.h states the
+    definition) -> device float64[nwin, 2] = (X_w, Y_w), nwin = ceil(ncalls / window).  ``out``: where to write (a row of the
+    H x nwin x 2 table ``carrier_track`` reads)."""
+    torch = _hip.torch()
+    ncalls = _rows48(rows)
+    if branch.dtype != torch.uint8 or not branch.is_contiguous() or branch.numel() != ncalls:
+        raise ValueError(f"branch must be {ncalls} contiguous bytes (one per row)")
+    nwin = -(-ncalls // int(window))
+    if out is None:
+        out = _hip.empty((nwin, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
+        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    _hip.check(_hip.lib().wf_carrier_stat(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), _hip.ptr(branch), ncalls, int(window), _hip.ptr(out),
+                                          _hip.stream()))
+    return out
+
+
+def carrier_track(stat, span: int = 1, ctx=None):
+    """Statistics of H hypothesis passes -> (phase f64[nwin], choice u8[nwin]) on device (``wf_carrier_track``; include/wfhip.h
+    states the definition).  ``stat``: contiguous device float64[H, nwin, 2], pass h over rows derotated by h π / H."""
+    if stat.dtype != _hip.torch().float64 or not stat.is_contiguous() or stat.dim() != 3 or stat.shape[2] != 2:
+        raise ValueError("stat must be contiguous float64[H, nwin, 2]")
+    H, nwin = int(stat.shape[0]), int(stat.shape[1])
+    phase = _hip.empty(max(nwin, 1), "float64")
+    choice = _hip.empty(max(nwin, 1) + 16, "uint8")
+    _hip.check(_hip.lib().wf_carrier_track(ctx if ctx is not None else _hip.ctx(), _hip.ptr(stat), H, nwin, int(span), _hip.ptr(phase), _hip.ptr(choice),
+                                           _hip.stream()))
+    return phase[:nwin], choice[:nwin]
+
+
+def rows_derotate(rows, window: int = 64, phase=None, phase0: float = 0.0, out=None, ctx=None):
+    """48-byte rows times exp(-j (phase0 + φ_k)) (``wf_rows_derotate``; include/wfhip.h states the definition), φ interpolated
+    between the centres of the windows of ``window`` rows from ``phase`` (device float64[nwin]; None: φ = 0).  ``out=rows``
+    works in place."""
+    torch = _hip.torch()
+    ncalls = _rows48(rows)
+    nwin = 0
+    if phase is not None:
+        if phase.dtype != torch.float64 or not phase.is_contiguous() or phase.numel() < 1:
+            raise ValueError("phase must be contiguous float64[nwin]")
+        nwin = int(phase.numel())
+    if out is None:
+        out = _hip.empty(tuple(rows.shape), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows.numel():
+        raise ValueError("out must be contiguous float64 of the rows' size")
+    _hip.check(_hip.lib().wf_rows_derotate(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(window), _hip.ptr(phase), nwin,
+                                           float(phase0), _hip.ptr(out), _hip.stream()))
+    return out
+
+
 def idd_windows(state, nrows: int, n_tx: int, period: int | None = None, row_offset: int = 1, lock=None, marker_bits: int = 0,
                 guard: int = 128, out=None, ctx=None):
     """The live windows of a burst from the decoder's freeze states (``wf_idd_windows``; include/wfhip.h states the definition,

@@ -13,6 +13,11 @@ All four classes take ``framing`` (a :class:`waveforms_amd.encoding.framing.Fram
 codewords itself: ``frame_search`` over the whole burst's λ, ``frame_gather`` into the decoder's input and, in the loops,
 ``frame_scatter`` of the decoder's extrinsic output (and the marker as a known-bits prior) back into the detector's prior
 buffer (``_Framed``).  With ``framing=None`` every class does exactly what it did without the keyword.
+
+The two SOQPSK-TG classes also take ``carrier=(theta0, nu)``, a carrier phase and frequency offset applied to the modulated
+signal (``carrier_offset``), and ``recovery``, a :class:`waveforms_amd.sync.carrier.CarrierRecovery` the rows pass through in
+front of the detector; ``recovery`` needs a ``framing`` (the phase comes back modulo π).  Both default to None: the same calls
+as before.
 """
 from __future__ import annotations
 
@@ -56,6 +61,32 @@ class _Framed:
         self.sync = _hip.zeros(2, "int64")                       # blocks searched, wrong locks
         self._true_lock = _hip.to_device(np.array([self.lead_bits, 1], dtype=np.int64))
         self._llr_in = _hip.empty((self.ncw, self.code.n_tx), "float64")
+
+    def _carrier_init(self, carrier, recovery) -> None:
+        """``carrier=(theta0, nu)``: the modulated signal is rotated by theta0 + 2π nu k (``carrier_offset``, nu in cycles per
+        sample) in front of the unchanged channel; ``recovery``: a ``waveforms_amd.sync.carrier.CarrierRecovery`` the rows pass
+        through before the detector.  Both None: nothing is added to the chain."""
+        if carrier is not None:
+            theta0, nu = (float(v) for v in carrier)
+            if not (math.isfinite(theta0) and math.isfinite(nu)):
+                raise ValueError("carrier = (theta0, nu) must be finite")
+            carrier = (theta0, nu)
+        if recovery is not None and self.framing is None:
+            raise ValueError("recovery needs a framing: the phase is recovered modulo π and the frame search's polarity resolves the rest")
+        self.carrier, self.recovery = carrier, recovery
+        self._carrier_phase = self._carrier_choice = None
+
+    def carrier_result(self):
+        """(phase float64[nwin] in radians, modulo π; choice uint8[nwin]) of the last block's recovery - synchronises."""
+        if self.recovery is None or self._carrier_phase is None:
+            raise RuntimeError("carrier_result needs a recovery and a block that ran")
+        return _hip.to_host(self._carrier_phase), _hip.to_host(self._carrier_choice)
+
+    def _recovered(self, rows):
+        if self.recovery is None:
+            return rows
+        rows, self._carrier_phase, self._carrier_choice = self.recovery.recover(rows, True)
+        return rows
 
     def _rate_db(self) -> float:
         """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""
@@ -105,7 +136,7 @@ class CodedSOQPSKLink(_Framed):
     is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0) -> None:
+                 lead_bits: int = 0, carrier=None, recovery=None) -> None:
         if detector not in TIMING_OFFSET:
             raise ValueError(f"unknown detector {detector!r}")
         if ncw < 1:
@@ -115,6 +146,7 @@ class CodedSOQPSKLink(_Framed):
         self.llr_scale = 1.0                    # (normalized min-sum does not depend on it)
         self.nbits = self.ncw * code.n_tx
         self._frame_init(framing, lead_bits)
+        self._carrier_init(carrier, recovery)
         self.nsym = self.nch + PAD_BITS
         pulse = freq_pulse_soqpsk_tg(self.sps)
         taps = (pt_matched_filter_taps if detector == "PT" else pam_matched_filter_taps)(pulse, 0.25, self.sps)
@@ -146,6 +178,8 @@ class CodedSOQPSKLink(_Framed):
         bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
         syms, _ = dev.fsm_encode(*self._tables, bits)
         sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
+        if self.carrier is not None:
+            dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
         first, ncols = dev.decimation(int(sig.shape[0]), self.sps, 2, TIMING_OFFSET[self.detector])
         if ncols < self.nch + 1:
             raise RuntimeError(f"{ncols} detector rows for {self.nch} channel bits")
@@ -165,7 +199,7 @@ class CodedSOQPSKLink(_Framed):
         info = self.info_bits(stream_id)
         tx = dev.ldpc_encode(self.code, info)
         rows, _ = self.front_end(tx, ebn0_db, seed, stream_id)
-        llr, _ = self.soft(rows)
+        llr, _ = self.soft(self._recovered(rows))
         return llr.contiguous(), info.view(self.ncw, self.code.k)
 
     # ---------------------------------------------------------------- blocks
@@ -174,7 +208,7 @@ class CodedSOQPSKLink(_Framed):
         info = self.info_bits(stream_id)
         tx = dev.ldpc_encode(self.code, info)
         rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
-        llr, hard = self.soft(rows)
+        llr, hard = self.soft(self._recovered(rows))
         dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
         dev.ldpc_decode(self.code, llr, scale=self.llr_scale, alpha=self.alpha, max_iter=self.max_iter, ref_info=info,
                         counts=self.counts)
@@ -230,7 +264,8 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
-                 lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD) -> None:
+                 lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD, carrier=None,
+                 recovery=None) -> None:
         if outer < 1 or inner < 1:
             raise ValueError("outer and inner must be at least 1")
         if int(guard) < 0:
@@ -246,7 +281,7 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         self.marker_prior = self.ext_sat if marker_prior is None else float(marker_prior)
         if not math.isfinite(self.marker_prior):
             raise ValueError("marker_prior must be finite")
-        super().__init__(code, ncw, sps, detector, alpha, max_iter=inner, framing=framing, lead_bits=lead_bits)
+        super().__init__(code, ncw, sps, detector, alpha, max_iter=inner, framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
         self.per_pass = bool(per_pass)
         self.pass_counts = _hip.zeros((self.outer, 4), "int64")
         self.prior = self.state = self.iters = self.decided = self.ext = None
@@ -314,6 +349,7 @@ class IterativeSOQPSKLink(CodedSOQPSKLink):
         info = self.info_bits(stream_id)
         tx = dev.ldpc_encode(self.code, info)
         rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
+        rows = self._recovered(rows)
         self.begin(int(rows.shape[0]))
         for o in range(self.outer):
             ext, hard = self.detect(rows, first=o == 0, o=o)
