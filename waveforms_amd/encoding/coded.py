@@ -1,14 +1,22 @@
-"""Coded SOQPSK-TG chain on the GPU: info bits -> LDPC encode -> SOQPSK-TG modulate + AWGN + PT / PAM bank -> max-log-MAP
-soft detector (``viterbi_soft``) -> LDPC decode -> error counts (``CodedSOQPSKLink``), and the same chain closed into a
-loop: soft detector with a prior <-> LDPC decoder with extrinsic output (``IterativeSOQPSKLink``).
+"""Coded chains on the GPU: info bits -> encoder -> modulate + AWGN + matched filters -> max-log-MAP soft detector -> decoder ->
+error counts, and the same chains closed into a loop, soft detector with a prior <-> decoder with extrinsic output.  Every
+stage is an existing device entry point (waveforms_amd.device); nothing leaves the GPU inside a block.  The fused ``SOQPSKLink``
+and ``CPMLink`` are not used and not changed.
 
-``CodedCPMLink`` / ``IterativeCPMLink`` are the same two chains for the waveforms of the generic CPM trellis, ARTM multi-h and
-PCM/FM: mapper -> modulate -> AWGN -> matched-filter rows -> ``cpm_soft`` / ``cpm_soft_apriori`` on the full-phase trellis.
+A link class is a waveform, a code and a kind of loop, each stated once:
 
-Every stage is an existing device entry point (waveforms_amd.device); nothing leaves the GPU inside a block.  The fused
-``SOQPSKLink`` and ``CPMLink`` are not used and not changed.
+    ``_Framed``   the burst around the codewords: sync marker, randomiser, frame search; carrier offset and recovery
+    ``_Link``     what every link does: PN23 information bits, ``channel_llrs`` through the ``encode`` hook, the counters, the
+                  view of the detector's output as codewords (``_coded``) and of the prior buffer (``_prior_coded``), ``detect``
+    ``_SOQPSK``   SOQPSK-TG: pad, tables, PT / PAM front end, ``viterbi_soft`` (``_apriori``), the uncoded count, λ offset 1
+    ``_CPM``      ARTM multi-h and PCM/FM on the generic CPM trellis: the same list with ``cpm_soft`` (``_apriori``), λ offset 0
+    ``_LDPC``     one ``ldpc_decode`` per block: ``CodedSOQPSKLink`` = ``_LDPC`` on ``_SOQPSK``, ``CodedCPMLink`` = ``_LDPC`` on ``_CPM``
+    ``_LDPCLoop`` the loop with frozen codewords: ``IterativeSOQPSKLink`` (adds ``live_only``), ``IterativeCPMLink`` (``prior_warmup``)
 
-All four classes take ``framing`` (a :class:`waveforms_amd.encoding.framing.Framing`) and ``lead_bits``: the burst is then
+The clipped loops without a freeze state (``ConvSOQPSKLink``, ``TurboSOQPSKLink``, ``RSConvSOQPSKLink``) are in sccc.py, pccc.py
+and rsconv.py, on ``_SOQPSK``.
+
+The four classes here take ``framing`` (a :class:`waveforms_amd.encoding.framing.Framing`) and ``lead_bits``: the burst is then
 ``lead_bits`` pseudo-random bits, ``ncw`` frames (sync marker + randomised codeword) and the pad, and the receiver finds the
 codewords itself: ``frame_search`` over the whole burst's λ, ``frame_gather`` into the decoder's input and, in the loops,
 ``frame_scatter`` of the decoder's extrinsic output (and the marker as a known-bits prior) back into the detector's prior
@@ -36,6 +44,8 @@ from ..link import sigma_for_ebn0
 
 TIMING_OFFSET = {"PT": -1, "PAM": 0}      # SOQPSK-TG (examples/soqpsk_detection.py)
 PAD_BITS = 16                             # tail after the burst's last codeword: every coded bit gets its λ
+PAD_SYMS = 8                              # CPM chains: zero symbols after the burst's last codeword
+CPM_WAVEFORMS = {"multih": 1, "pcmfm": 2}  # -> symbol_map kind (the reference's natural-binary mappers)
 
 
 class _Framed:
@@ -125,52 +135,118 @@ class _Framed:
         return blocks, wrong, (int(rec[0]), int(rec[1]), best, other)
 
 
-class CodedSOQPSKLink(_Framed):
-    """One block = ``ncw`` codewords of ``code`` sent back to back as ONE SOQPSK-TG burst (plus ``PAD_BITS`` zero bits).
+class _Link(_Framed):
+    """What every coded link does, whatever its waveform, its code and its loop: one block = ``ncw`` codewords of ``code`` sent
+    back to back as ONE burst, PN23 information bits by ``stream_id``, Eb/N0 per INFORMATION bit (``_rate_db``).
 
-    Eb/N0 is per INFORMATION bit: the channel's σ is ``sigma_for_ebn0(ebn0_db + 10 log10(k / n_tx), sps)``, i.e. the
-    channel runs at Eb/N0 + 10 log10(rate) per transmitted bit (-3.01 dB for the rate-1/2 demo code).
+    The waveform base under this class supplies ``bits_per_symbol``, ``_wave_init`` (pad, ``nsym``, device tables), ``front_end``,
+    ``sigma``, the detector calls ``_soft`` / ``_soft_apriori``, ``count_uncoded`` and ``_lam0``: transmitted bit j pairs with the
+    detector's λ[j + _lam0], and ``_coded`` / ``_prior_coded`` are the only two places that use it.  The code supplies ``encode``
+    and ``_ncounts``, the width of ``counts``."""
 
-    The information bits are PN23 (from the all-ones state), block b = ``stream_id`` taking the segment that starts at
-    bit b ncw k.  The noise is the library's counter-based AWGN keyed by (``seed``, ``stream_id``).  Transmitted bit j
-    is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
+    _ncounts = 4
 
-    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0, carrier=None, recovery=None) -> None:
-        if detector not in TIMING_OFFSET:
-            raise ValueError(f"unknown detector {detector!r}")
+    def __init__(self, code, ncw: int, sps: int, framing=None, lead_bits: int = 0, carrier=None, recovery=None) -> None:
         if ncw < 1:
             raise ValueError("ncw must be at least 1")
-        self.code, self.ncw, self.sps, self.detector = code, int(ncw), int(sps), detector
-        self.alpha, self.max_iter = float(alpha), int(max_iter)
-        self.llr_scale = 1.0                    # (normalized min-sum does not depend on it)
+        self.code, self.ncw, self.sps = code, int(ncw), int(sps)
+        self.llr_scale = 1.0                    # (max-log-MAP and normalized min-sum do not depend on it)
         self.nbits = self.ncw * code.n_tx
-        self._frame_init(framing, lead_bits)
+        self._frame_init(framing, lead_bits, self.bits_per_symbol)
         self._carrier_init(carrier, recovery)
-        self.nsym = self.nch + PAD_BITS
-        pulse = freq_pulse_soqpsk_tg(self.sps)
-        taps = (pt_matched_filter_taps if detector == "PT" else pam_matched_filter_taps)(pulse, 0.25, self.sps)
-        self._d_h = _hip.to_device(np.array([0.25]))
-        self._d_pulse = _hip.to_device(pulse)
-        self._d_taps = _hip.to_device(np.ascontiguousarray(taps))
-        self._tables = SOQPSKTrellis4x2DiffEncoded.dense_tables()
-        self._pad = _hip.zeros(PAD_BITS, "uint8")
+        self._wave_init()
         self._mask = generate_mask(23)
-        self.counts = _hip.zeros(4, "int64")
+        self.counts = _hip.zeros(self._ncounts, "int64")
         self.uncoded = _hip.zeros(2, "int64")
         self.blocks = 0
         code.handle()
 
-    def sigma(self, ebn0_db: float | None) -> float:
-        if ebn0_db is None:
-            return 0.0
-        return sigma_for_ebn0(float(ebn0_db) + self._rate_db(), self.sps)
+    def _loop_args(self, damping: float, **passes: int) -> None:
+        """A loop's pass counts (``outer``, and ``inner`` where there is one) and ``damping``, checked before anything touches the
+        device, and kept as attributes."""
+        if min(passes.values()) < 1:
+            raise ValueError(" and ".join(passes) + " must be at least 1")
+        if not (math.isfinite(damping) and damping > 0.0):
+            raise ValueError("damping must be finite and positive")
+        self.damping = float(damping)
+        for name, n in passes.items():
+            setattr(self, name, int(n))
 
     # ---------------------------------------------------------------- stages
     def info_bits(self, stream_id: int = 0):
         n = self.ncw * self.code.k
         bits, _ = dev.lfsr_bits(23, self._mask, (1 << 23) - 1, n, skip=int(stream_id) * n)
         return bits
+
+    def _coded(self, lam, bits, search: bool = True):
+        """A detector's (λ, bits) of the whole burst -> (λ of the coded bits, ncw x n_tx view; hard decisions of the channel bits
+        in front of the pad).  Framed, the view is ``deframe``'s (``search``: lock first)."""
+        j = self._lam0
+        if self.framing is not None:
+            return self.deframe(lam[j:], search), bits[j:j + self.nch]
+        return lam[j:j + self.nbits].view(self.ncw, self.code.n_tx), bits[j:j + self.nbits]
+
+    def _prior_coded(self):
+        """The prior buffer's slice of the coded bits, where a decoder writes the next prior at stride n_tx; framed, the slice
+        from channel bit 0 on that ``frame_scatter`` writes at the lock's position."""
+        j = self._lam0
+        return self.prior[j:] if self.framing is not None else self.prior[j:j + self.nbits]
+
+    def soft(self, rows):
+        """Rows -> (λ of the coded bits, ncw x n_tx view; hard decisions of the same λ)."""
+        return self._coded(*self._soft(rows))
+
+    def detect(self, rows, first: bool = False, o: int | None = None):
+        """One detector pass of a loop -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first
+        pass of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
+        return self._coded(*self._soft_apriori(rows, None if first else self.prior), search=first)
+
+    def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """(λ ncw x n_tx of the plain detector, information bits ncw x k) of one block, on the device."""
+        info = self.info_bits(stream_id)
+        rows, _ = self.front_end(self.encode(info), ebn0_db, seed, stream_id)
+        llr, _ = self.soft(self._recovered(rows))
+        return llr.contiguous(), info.view(self.ncw, self.code.k)
+
+    # ---------------------------------------------------------------- counts
+    def reset_counts(self) -> None:
+        self.counts.zero_()
+        self.uncoded.zero_()
+        self.blocks = 0
+        if self.framing is not None:
+            self.sync.zero_()
+
+    def uncoded_result(self) -> tuple[int, int]:
+        """(bit errors of λ < 0 against the channel bits in front of the pad, bits compared) over the same blocks."""
+        return int(self.uncoded.cpu()[1]), self.blocks * self.nch
+
+
+class _SOQPSK(_Link):
+    """The SOQPSK-TG side of a link: the channel bits plus ``PAD_BITS`` zero bits, differentially precoded, through the PT or PAM
+    bank and ``viterbi_soft`` (``CodedSOQPSKLink`` states the conventions)."""
+
+    bits_per_symbol, _lam0 = 1, 1
+
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", **burst) -> None:
+        if detector not in TIMING_OFFSET:
+            raise ValueError(f"unknown detector {detector!r}")
+        self.detector = detector
+        super().__init__(code, ncw, sps, **burst)
+
+    def _wave_init(self) -> None:
+        self.nsym = self.nch + PAD_BITS
+        pulse = freq_pulse_soqpsk_tg(self.sps)
+        taps = (pt_matched_filter_taps if self.detector == "PT" else pam_matched_filter_taps)(pulse, 0.25, self.sps)
+        self._d_h = _hip.to_device(np.array([0.25]))
+        self._d_pulse = _hip.to_device(pulse)
+        self._d_taps = _hip.to_device(np.ascontiguousarray(taps))
+        self._tables = SOQPSKTrellis4x2DiffEncoded.dense_tables()
+        self._pad = _hip.zeros(PAD_BITS, "uint8")
+
+    def sigma(self, ebn0_db: float | None) -> float:
+        if ebn0_db is None:
+            return 0.0
+        return sigma_for_ebn0(float(ebn0_db) + self._rate_db(), self.sps)
 
     def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
         """Coded bits (device ncw x n_tx) -> matched-filter rows of the burst."""
@@ -187,39 +263,98 @@ class CodedSOQPSKLink(_Framed):
                                 np.exp(-1j * np.pi / 4))
         return rows, syms
 
-    def soft(self, rows):
-        """Rows -> (λ of the coded bits, ncw x n_tx view; hard decisions of the same λ)."""
-        llr, bits = dev.viterbi_soft(rows, True)
-        if self.framing is not None:
-            return self.deframe(llr[1:]), bits[1:1 + self.nch]
-        return llr[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
+    def _soft(self, rows):
+        return dev.viterbi_soft(rows, True)
 
-    def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
-        """(λ ncw x n_tx, information bits ncw x k) of one block, on the device."""
-        info = self.info_bits(stream_id)
-        tx = dev.ldpc_encode(self.code, info)
-        rows, _ = self.front_end(tx, ebn0_db, seed, stream_id)
-        llr, _ = self.soft(self._recovered(rows))
-        return llr.contiguous(), info.view(self.ncw, self.code.k)
+    def _soft_apriori(self, rows, prior):
+        return dev.viterbi_soft_apriori(rows, prior, self.damping)
 
-    # ---------------------------------------------------------------- blocks
+    def count_uncoded(self, hard, tx, syms) -> None:
+        dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
+
+
+class _CPM(_Link):
+    """The ARTM multi-h / PCM/FM side of a link: the channel bits from call 0 plus ``PAD_SYMS`` zero symbols, through the generic
+    CPM trellis and ``cpm_soft`` (``CodedCPMLink`` states the chain and the conventions)."""
+
+    _lam0 = 0
+    bits_per_symbol = property(lambda self: self.spec.bits_per_symbol)
+
+    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, **burst) -> None:
+        from ..viterbi import cpm
+
+        if waveform not in CPM_WAVEFORMS:
+            raise ValueError(f"unknown waveform {waveform!r}")
+        if waveform == "multih" and code.n_tx % 2:
+            raise ValueError(f"ARTM sends two bits per symbol: a code with an odd n_tx = {code.n_tx} is refused")
+        self.waveform, self.spec = waveform, cpm.ARTM_64 if waveform == "multih" else cpm.PCMFM_20
+        super().__init__(code, ncw, sps, **burst)
+
+    def _wave_init(self) -> None:
+        from ..viterbi import cpm
+
+        if self.waveform == "multih":
+            from ..cpm.multih import freq_pulse_multih_irig as freq_pulse
+        else:
+            from ..cpm.pcmfm import freq_pulse_pcmfm as freq_pulse
+        spec, lg = self.spec, self.spec.bits_per_symbol
+        self.nsym = (self.nch + lg - 1) // lg + PAD_SYMS
+        pulse = np.asarray(freq_pulse(self.sps), dtype=np.float64)
+        geo = cpm.filter_geometry(pulse.size, self.sps, spec, self.nsym)
+        self.start0, self.ncalls = int(geo["start0"]), int(geo["ncalls"])
+        if self.ncalls * lg < self.nch:
+            raise RuntimeError(f"{self.ncalls} detector calls for {self.nch} channel bits")
+        self._d_h = _hip.to_device(spec.mod_index)
+        self._d_pulse = _hip.to_device(pulse)
+        self._d_templates = _hip.to_device(cpm.matched_filter_templates(pulse, self.sps, cpm.full_phase(spec)))
+        self._d_rot = _hip.to_device(cpm.rotation_table(spec))
+        self._pad = _hip.zeros(PAD_SYMS * lg, "uint8")
+
+    def sigma(self, ebn0_db: float | None) -> float:
+        from ..viterbi.cpm import sigma_for_ebn0 as cpm_sigma
+
+        if ebn0_db is None:
+            return 0.0
+        return cpm_sigma(float(ebn0_db) + self._rate_db(), self.sps, self.spec.bits_per_symbol)
+
+    def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst float64[ncalls, nfilt, 2], its symbols)."""
+        torch = _hip.torch()
+        bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
+        syms = dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
+        sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
+        received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
+        rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
+        return rows, syms
+
+    def _soft(self, rows):
+        return dev.cpm_soft(rows, self.spec, 0, 0, d_rot=self._d_rot)
+
+    def _soft_apriori(self, rows, prior):
+        return dev.cpm_soft_apriori(rows, self.spec, prior, self.damping, 0, 0 if prior is None else self.prior_warmup, d_rot=self._d_rot)
+
+    def count_uncoded(self, hard, tx, syms=None) -> None:
+        flat = tx.reshape(-1) if self.framing is None else self.sent
+        dev.count_errors(hard, flat, hard, flat, self.nch, self.uncoded)     # (bits in both pairs: [1] is what is read)
+
+
+class _LDPC:
+    """An LDPC code on a link: ``ldpc_encode``, and per block one ``ldpc_decode`` (normalized min-sum with ``alpha``, at most
+    ``max_iter`` iterations) that also counts."""
+
+    def encode(self, info):
+        return dev.ldpc_encode(self.code, info)
+
     def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
         """Queue one block on the current stream; the counts accumulate on the device."""
         info = self.info_bits(stream_id)
-        tx = dev.ldpc_encode(self.code, info)
+        tx = self.encode(info)
         rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
         llr, hard = self.soft(self._recovered(rows))
-        dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
+        self.count_uncoded(hard, tx, syms)
         dev.ldpc_decode(self.code, llr, scale=self.llr_scale, alpha=self.alpha, max_iter=self.max_iter, ref_info=info,
                         counts=self.counts)
         self.blocks += 1
-
-    def reset_counts(self) -> None:
-        self.counts.zero_()
-        self.uncoded.zero_()
-        self.blocks = 0
-        if self.framing is not None:
-            self.sync.zero_()
 
     def result(self) -> tuple[int, int, int, int, float]:
         """(information bit errors, codeword errors, codewords not converged, information bits compared, mean
@@ -229,170 +364,24 @@ class CodedSOQPSKLink(_Framed):
         ncw = self.blocks * self.ncw
         return be, fe, nc, ncw * self.code.k, (its / ncw if ncw else 0.0)
 
-    def uncoded_result(self) -> tuple[int, int]:
-        """(bit errors of λ < 0 against the channel bits in front of the pad, bits compared) over the same blocks."""
-        return int(self.uncoded.cpu()[1]), self.blocks * self.nch
+
+class CodedSOQPSKLink(_LDPC, _SOQPSK):
+    """One block = ``ncw`` codewords of ``code`` sent back to back as ONE SOQPSK-TG burst (plus ``PAD_BITS`` zero bits).
+
+    Eb/N0 is per INFORMATION bit: the channel's σ is ``sigma_for_ebn0(ebn0_db + 10 log10(k / n_tx), sps)``, i.e. the
+    channel runs at Eb/N0 + 10 log10(rate) per transmitted bit (-3.01 dB for the rate-1/2 demo code).
+
+    The information bits are PN23 (from the all-ones state), block b = ``stream_id`` taking the segment that starts at
+    bit b ncw k.  The noise is the library's counter-based AWGN keyed by (``seed``, ``stream_id``).  Transmitted bit j
+    is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
+
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
+                 lead_bits: int = 0, carrier=None, recovery=None) -> None:
+        self.alpha, self.max_iter = float(alpha), int(max_iter)
+        super().__init__(code, ncw, sps, detector, framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
 
 
-class IterativeSOQPSKLink(CodedSOQPSKLink):
-    """``CodedSOQPSKLink`` with iterative detection and decoding: same block layout, PN23 information bits, noise keys,
-    Eb/N0 convention and result tuples; the front end runs once per block, then ``outer`` passes of
-
-        soft detector with the burst's prior buffer (``viterbi_soft_apriori``, apriori_scale = ``damping``)
-        -> ``ldpc_decode_ext`` (``inner`` iterations from a cold start) writing the next prior at offset +1, stride n_tx
-
-    and one ``ldpc_count``.  A codeword whose syndrome is zero is FROZEN: its prior becomes ±``ext_sat`` by its decisions and
-    later passes leave it alone (without this a converged codeword would hand back zero extrinsic and be decoded from
-    scratch on the next pass, and the loop oscillates).  Row 0 and the tail rows keep prior 0.  Max-log-MAP and
-    normalized min-sum are both scale-invariant, so the loop needs no noise-variance scale (``llr_scale`` stays 1).
-
-    ``ext_sat`` / ``ext_clip`` are in the detector's metric units, which grow linearly with ``sps`` (the matched filters
-    sum sps + 1 unit-magnitude taps): the defaults are ext_sat = 6.25 sps (50 at sps 8, where mean |λ| is about 11 at
-    4.5 dB) and no clip.  ``outer`` is fixed per block and nothing synchronises with the host inside one; every pass is
-    queued even when every codeword is already frozen (the decoder's workgroups then retire at once, the detector
-    still runs).  ``per_pass=True`` also accumulates the four counts after every pass (``pass_results``).
-
-    ``live_only=True`` is the answer to that last remark: pass 1 is unchanged, every later pass first turns the states the
-    previous decoder pass left into the burst's live windows (``idd_windows``: the rows of the open codewords and ``guard``
-    rows on either side, on the device) and runs the detector on those rows only (``viterbi_soft_apriori_windows``), into the
-    ONE ext / bits buffer the block keeps: rows outside the windows hold an earlier pass's values, and the decoder never
-    reads a frozen codeword's input.  Still no host synchronisation and a fixed ``outer``; a pass with nothing open costs
-    launches that find nothing.  A window's edges start from free metrics instead of the burst's history, so this is the
-    full loop exactly only when the metrics merge within the guard; the frozen neighbours' saturated priors pin the trellis
-    within a few rows, and INTEGRATION.md has the counts behind the default of 128 rows (``guard >= nrows`` makes any open
-    codeword's window the whole burst: the full loop bit for bit).  ``live_results`` returns what each pass worked on."""
-
-    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
-                 damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
-                 lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD, carrier=None,
-                 recovery=None) -> None:
-        if outer < 1 or inner < 1:
-            raise ValueError("outer and inner must be at least 1")
-        if int(guard) < 0:
-            raise ValueError(f"guard = {guard} must not be negative")
-        self.live_only, self.guard = bool(live_only), int(guard)
-        if not (math.isfinite(damping) and damping > 0.0):
-            raise ValueError("damping must be finite and positive")
-        self.outer, self.inner, self.damping = int(outer), int(inner), float(damping)
-        self.ext_sat = 6.25 * int(sps) if ext_sat is None else float(ext_sat)
-        self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
-        if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
-            raise ValueError("ext_sat must be finite and positive, ext_clip positive")
-        self.marker_prior = self.ext_sat if marker_prior is None else float(marker_prior)
-        if not math.isfinite(self.marker_prior):
-            raise ValueError("marker_prior must be finite")
-        super().__init__(code, ncw, sps, detector, alpha, max_iter=inner, framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
-        self.per_pass = bool(per_pass)
-        self.pass_counts = _hip.zeros((self.outer, 4), "int64")
-        self.prior = self.state = self.iters = self.decided = self.ext = None
-        self.live_counts = _hip.zeros((self.outer, 3), "int64") if self.live_only else None
-        self.windows = _hip.zeros(4 + 2 * self.ncw, "int64") if self.live_only else None
-        self._live_out, self._live_first = None, 0          # the block's ext / bits buffers; first passes run
-
-    # ---------------------------------------------------------------- stages
-    def begin(self, nrows: int) -> None:
-        """Fresh loop state of one block: prior 0 on every row, every codeword open, no iterations."""
-        self._live_out = None
-        if self.prior is None or self.prior.numel() != nrows:
-            self.prior = _hip.zeros(nrows, "float32")
-            self.state = _hip.zeros(self.ncw, "uint8")
-            self.iters = _hip.zeros(self.ncw, "int32")
-            self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
-            self.ext = None if self.framing is None else _hip.zeros((self.ncw, self.code.n_tx), "float32")
-        else:
-            for t in (self.prior, self.state, self.iters, self.decided, self.ext):
-                if t is not None:
-                    t.zero_()
-
-    def live_windows(self, nrows: int):
-        """The live windows of the burst's ``nrows`` rows for the states as they are now -> the device table of ``idd_windows``
-        (kept in ``windows``).  Coded bit j is row j + 1; framed, codeword 0 starts behind the lock's p̂ and one marker."""
-        if self.framing is None:
-            return dev.idd_windows(self.state, nrows, self.code.n_tx, guard=self.guard, out=self.windows)
-        return dev.idd_windows(self.state, nrows, self.code.n_tx, self.framing.period, 1, self.lock, self.framing.L, self.guard, out=self.windows)
-
-    def detect(self, rows, first: bool = False, o: int | None = None):
-        """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
-        of a block has prior 0 everywhere and takes the plain detector (bitwise the same result).  ``live_only``: every
-        later pass works on the live windows only and writes into the first pass's buffers; ``o`` is the pass whose entry
-        of ``live_results`` gets the table's counts (None: nobody's)."""
-        if self.live_only and not first:
-            if self._live_out is None:
-                raise RuntimeError("live_only: the block's first pass (first=True) has not run")
-            table = self.live_windows(int(self._live_out[0].numel()))
-            if o is not None:
-                self.live_counts[o] += table[:3]
-            ext, bits = dev.viterbi_soft_apriori_windows(rows, self.prior, table, self.damping, out=self._live_out)
-        else:
-            ext, bits = dev.viterbi_soft_apriori(rows, None if first else self.prior, self.damping)
-            if self.live_only:
-                self._live_out = (ext, bits)
-                self._live_first += o is not None
-        if self.framing is not None:
-            return self.deframe(ext[1:], search=first), bits[1:1 + self.nch]
-        return ext[1:1 + self.nbits].view(self.ncw, self.code.n_tx), bits[1:1 + self.nbits]
-
-    def decode(self, ext) -> None:
-        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place.  Framed: the
-        extrinsic values go to the contiguous ``ext`` buffer (frozen codewords keep theirs) and ``frame_scatter`` puts all of
-        them, and ±``marker_prior`` on the marker rows, into the prior at the lock's position."""
-        if self.framing is not None:
-            dev.ldpc_decode_ext(self.code, ext, self.state, self.ext, self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
-                                max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
-            self.framing.scatter(self.ext, self.lock, self.prior[1:], self.marker_prior)
-            return
-        dev.ldpc_decode_ext(self.code, ext, self.state, self.prior[1:1 + self.nbits], self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
-                            max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
-
-    # ---------------------------------------------------------------- blocks
-    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
-        info = self.info_bits(stream_id)
-        tx = dev.ldpc_encode(self.code, info)
-        rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
-        rows = self._recovered(rows)
-        self.begin(int(rows.shape[0]))
-        for o in range(self.outer):
-            ext, hard = self.detect(rows, first=o == 0, o=o)
-            if o == 0:
-                dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
-            self.decode(ext)
-            if self.per_pass:
-                dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.pass_counts[o])
-        dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.counts)
-        self.blocks += 1
-
-    def reset_counts(self) -> None:
-        super().reset_counts()
-        self.pass_counts.zero_()
-        if self.live_only:
-            self.live_counts.zero_()
-            self._live_first = 0
-
-    def pass_results(self) -> list[tuple[int, int, int, float]]:
-        """Per outer pass (``per_pass=True``): (information bit errors, codeword errors, codewords still open, mean
-        iterations so far) over the blocks run - synchronises."""
-        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
-        ncw = self.blocks * self.ncw
-        return [(int(be), int(fe), int(nc), (int(its) / ncw if ncw else 0.0)) for be, fe, nc, its in self.pass_counts.cpu().tolist()]
-
-    def live_results(self) -> list[tuple[int, int, int]]:
-        """Per outer pass (``live_only=True``): (windows, live rows, codewords open on entry), summed over the blocks
-        run since ``reset_counts`` - synchronises.  Pass 1 is the plain detector on the whole burst: one
-        window of every row, every codeword open.  The later entries are the words [0 .. 2] of the passes' window tables,
-        added up on the device."""
-        if not self.live_only:
-            raise RuntimeError("live_results needs live_only=True")
-        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
-        rest = [tuple(int(v) for v in row) for row in self.live_counts.cpu().tolist()[1:]]
-        nrows = 0 if self.prior is None else int(self.prior.numel())
-        return [(self._live_first, self._live_first * nrows, self._live_first * self.ncw)] + rest
-
-
-PAD_SYMS = 8                              # CPM chains: zero symbols after the burst's last codeword
-CPM_WAVEFORMS = {"multih": 1, "pcmfm": 2}  # -> symbol_map kind (the reference's natural-binary mappers)
-
-
-class CodedCPMLink(_Framed):
+class CodedCPMLink(_LDPC, _CPM):
     """``CodedSOQPSKLink`` for ARTM multi-h (``waveform="multih"``) and PCM/FM (``"pcmfm"``): one block = ``ncw`` codewords of
     ``code`` sent back to back as ONE burst from call 0, plus ``PAD_SYMS`` zero symbols.
 
@@ -410,112 +399,181 @@ class CodedCPMLink(_Framed):
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50, framing=None,
                  lead_bits: int = 0) -> None:
-        from ..viterbi import cpm
-
-        if waveform not in CPM_WAVEFORMS:
-            raise ValueError(f"unknown waveform {waveform!r}")
-        if ncw < 1:
-            raise ValueError("ncw must be at least 1")
-        if waveform == "multih":
-            from ..cpm.multih import freq_pulse_multih_irig
-
-            pulse, spec = freq_pulse_multih_irig(int(sps)), cpm.ARTM_64
-            if code.n_tx % 2:
-                raise ValueError(f"ARTM sends two bits per symbol: a code with an odd n_tx = {code.n_tx} is refused")
-        else:
-            from ..cpm.pcmfm import freq_pulse_pcmfm
-
-            pulse, spec = freq_pulse_pcmfm(int(sps)), cpm.PCMFM_20
-        self.code, self.ncw, self.sps, self.waveform, self.spec = code, int(ncw), int(sps), waveform, spec
         self.alpha, self.max_iter = float(alpha), int(max_iter)
-        self.llr_scale = 1.0
-        lg = spec.bits_per_symbol
-        self.nbits = self.ncw * code.n_tx
-        self._frame_init(framing, lead_bits, lg)
-        self.nsym = (self.nch + lg - 1) // lg + PAD_SYMS
-        pulse = np.asarray(pulse, dtype=np.float64)
-        geo = cpm.filter_geometry(pulse.size, self.sps, spec, self.nsym)
-        self.start0, self.ncalls = int(geo["start0"]), int(geo["ncalls"])
-        if self.ncalls * lg < self.nch:
-            raise RuntimeError(f"{self.ncalls} detector calls for {self.nch} channel bits")
-        self._d_h = _hip.to_device(spec.mod_index)
-        self._d_pulse = _hip.to_device(pulse)
-        self._d_templates = _hip.to_device(cpm.matched_filter_templates(pulse, self.sps, cpm.full_phase(spec)))
-        self._d_rot = _hip.to_device(cpm.rotation_table(spec))
-        self._pad = _hip.zeros(PAD_SYMS * lg, "uint8")
-        self._mask = generate_mask(23)
-        self.counts = _hip.zeros(4, "int64")
-        self.uncoded = _hip.zeros(2, "int64")
-        self.blocks = 0
-        code.handle()
+        super().__init__(code, ncw, waveform, sps, framing=framing, lead_bits=lead_bits)
 
-    def sigma(self, ebn0_db: float | None) -> float:
-        from ..viterbi.cpm import sigma_for_ebn0 as cpm_sigma
 
-        if ebn0_db is None:
-            return 0.0
-        return cpm_sigma(float(ebn0_db) + self._rate_db(), self.sps, self.spec.bits_per_symbol)
+class _LDPCLoop:
+    """Iterative detection and decoding over a ``Coded*Link`` (which it precedes in the bases): the front end runs once per
+    block, then ``outer`` passes of
+
+        the waveform's soft detector with the burst's prior buffer (apriori_scale = ``damping``)
+        -> ``ldpc_decode_ext`` (``inner`` iterations from a cold start) writing the next prior at ``_prior_coded``, stride n_tx
+
+    and one ``ldpc_count``.  A codeword whose syndrome is zero is FROZEN: its prior becomes ±``ext_sat`` by its decisions and
+    later passes leave it alone (without this a converged codeword would hand back zero extrinsic and be decoded from
+    scratch on the next pass, and the loop oscillates).  The rows or calls outside the coded bits keep prior 0.  Max-log-MAP and
+    normalized min-sum are both scale-invariant, so the loop needs no noise-variance scale (``llr_scale`` stays 1).
+
+    ``ext_sat`` / ``ext_clip`` are in the detector's metric units, which grow linearly with ``sps`` (the matched filters
+    sum sps + 1 unit-magnitude taps): the defaults are ext_sat = 6.25 sps (50 at sps 8) and no clip.  ``outer`` is fixed per
+    block and nothing synchronises with the host inside one; every pass is queued even when every codeword is already frozen
+    (the decoder's workgroups then retire at once, the detector still runs).  ``per_pass=True`` also accumulates the four
+    counts after every pass (``pass_results``).  Framed, ``marker_prior`` (default ``ext_sat``) is the known-bits prior on the
+    marker rows."""
+
+    def __init__(self, code, ncw: int, *, sps: int, outer: int, inner: int, damping: float, ext_clip: float | None, ext_sat: float | None,
+                 per_pass: bool, marker_prior: float | None, **link) -> None:
+        self._loop_args(damping, outer=outer, inner=inner)
+        self.ext_sat = 6.25 * int(sps) if ext_sat is None else float(ext_sat)
+        self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
+        if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
+            raise ValueError("ext_sat must be finite and positive, ext_clip positive")
+        self.marker_prior = self.ext_sat if marker_prior is None else float(marker_prior)
+        if not math.isfinite(self.marker_prior):
+            raise ValueError("marker_prior must be finite")
+        super().__init__(code, ncw, sps=sps, max_iter=inner, **link)
+        self.per_pass = bool(per_pass)
+        self.pass_counts = _hip.zeros((self.outer, 4), "int64")
+        self.prior = self.state = self.iters = self.decided = self.ext = None
 
     # ---------------------------------------------------------------- stages
-    def info_bits(self, stream_id: int = 0):
-        n = self.ncw * self.code.k
-        bits, _ = dev.lfsr_bits(23, self._mask, (1 << 23) - 1, n, skip=int(stream_id) * n)
-        return bits
+    def _begin(self, n: int) -> None:
+        """Fresh loop state of one block for a prior of ``n`` values: prior 0, every codeword open, no iterations."""
+        if self.prior is None or self.prior.numel() != n:
+            self.prior = _hip.zeros(n, "float32")
+            self.state = _hip.zeros(self.ncw, "uint8")
+            self.iters = _hip.zeros(self.ncw, "int32")
+            self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
+            self.ext = None if self.framing is None else _hip.zeros((self.ncw, self.code.n_tx), "float32")
+        else:
+            for t in (self.prior, self.state, self.iters, self.decided, self.ext):
+                if t is not None:
+                    t.zero_()
 
-    def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
-        """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst float64[ncalls, nfilt, 2], its symbols)."""
-        torch = _hip.torch()
-        bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
-        syms = dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
-        sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
-        received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
-        rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
-        return rows, syms
-
-    def soft(self, rows):
-        """Rows -> (λ of the coded bits, ncw x n_tx view; hard decisions of the same λ)."""
-        llr, bits = dev.cpm_soft(rows, self.spec, 0, 0, d_rot=self._d_rot)
+    def decode(self, ext) -> None:
+        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place.  Framed: the
+        extrinsic values go to the contiguous ``ext`` buffer (frozen codewords keep theirs) and ``frame_scatter`` puts all of
+        them, and ±``marker_prior`` on the marker rows, into the prior at the lock's position."""
+        dev.ldpc_decode_ext(self.code, ext, self.state, self._prior_coded() if self.framing is None else self.ext, self.code.n_tx,
+                            scale=self.llr_scale, alpha=self.alpha, max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat,
+                            info_bits=self.decided, iters=self.iters)
         if self.framing is not None:
-            return self.deframe(llr), bits[:self.nch]
-        return llr[:self.nbits].view(self.ncw, self.code.n_tx), bits[:self.nbits]
-
-    def channel_llrs(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
-        """(λ ncw x n_tx, information bits ncw x k) of one block, on the device."""
-        info = self.info_bits(stream_id)
-        tx = dev.ldpc_encode(self.code, info)
-        rows, _ = self.front_end(tx, ebn0_db, seed, stream_id)
-        llr, _ = self.soft(rows)
-        return llr.contiguous(), info.view(self.ncw, self.code.k)
-
-    def count_uncoded(self, hard, tx) -> None:
-        flat = tx.reshape(-1) if self.framing is None else self.sent
-        dev.count_errors(hard, flat, hard, flat, self.nch, self.uncoded)     # (bits in both pairs: [1] is what is read)
+            self.framing.scatter(self.ext, self.lock, self._prior_coded(), self.marker_prior)
 
     # ---------------------------------------------------------------- blocks
     def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
-        """Queue one block on the current stream; the counts accumulate on the device."""
         info = self.info_bits(stream_id)
-        tx = dev.ldpc_encode(self.code, info)
-        rows, _syms = self.front_end(tx, ebn0_db, seed, stream_id)
-        llr, hard = self.soft(rows)
-        self.count_uncoded(hard, tx)
-        dev.ldpc_decode(self.code, llr, scale=self.llr_scale, alpha=self.alpha, max_iter=self.max_iter, ref_info=info,
-                        counts=self.counts)
+        tx = self.encode(info)
+        rows, syms = self.front_end(tx, ebn0_db, seed, stream_id)
+        rows = self._recovered(rows)
+        self.begin(int(rows.shape[0]))
+        for o in range(self.outer):
+            ext, hard = self.detect(rows, first=o == 0, o=o)
+            if o == 0:
+                self.count_uncoded(hard, tx, syms)
+            self.decode(ext)
+            if self.per_pass:
+                dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.pass_counts[o])
+        dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.counts)
         self.blocks += 1
 
-    reset_counts = CodedSOQPSKLink.reset_counts
-    result = CodedSOQPSKLink.result
-    uncoded_result = CodedSOQPSKLink.uncoded_result
+    def reset_counts(self) -> None:
+        super().reset_counts()
+        self.pass_counts.zero_()
+
+    def pass_results(self) -> list[tuple[int, int, int, float]]:
+        """Per outer pass (``per_pass=True``): (information bit errors, codeword errors, codewords still open, mean
+        iterations so far) over the blocks run - synchronises."""
+        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
+        ncw = self.blocks * self.ncw
+        return [(int(be), int(fe), int(nc), (int(its) / ncw if ncw else 0.0)) for be, fe, nc, its in self.pass_counts.cpu().tolist()]
 
 
-class IterativeCPMLink(CodedCPMLink):
-    """``CodedCPMLink`` with iterative detection and decoding, the loop of ``IterativeSOQPSKLink`` on the generic CPM trellis:
-    the front end runs once per block, then ``outer`` passes of
+class IterativeSOQPSKLink(_LDPCLoop, CodedSOQPSKLink):
+    """``CodedSOQPSKLink`` with iterative detection and decoding (``_LDPCLoop``): same block layout, PN23 information bits, noise
+    keys, Eb/N0 convention and result tuples; the detector is ``viterbi_soft_apriori`` and the next prior is written at offset
+    +1: row 0 and the tail rows keep prior 0.  At the default ``ext_sat`` of 50 at sps 8, mean |λ| is about 11 at 4.5 dB.
 
-        ``cpm_soft_apriori`` with the burst's prior buffer (apriori_scale = ``damping``)
-        -> ``ldpc_decode_ext`` (``inner`` iterations from a cold start) writing the next prior at offset 0, stride n_tx
+    ``live_only=True`` is the answer to the loop's remark that the detector runs even when every codeword is frozen: pass 1 is
+    unchanged, every later pass first turns the states the
+    previous decoder pass left into the burst's live windows (``idd_windows``: the rows of the open codewords and ``guard``
+    rows on either side, on the device) and runs the detector on those rows only (``viterbi_soft_apriori_windows``), into the
+    ONE ext / bits buffer the block keeps: rows outside the windows hold an earlier pass's values, and the decoder never
+    reads a frozen codeword's input.  Still no host synchronisation and a fixed ``outer``; a pass with nothing open costs
+    launches that find nothing.  A window's edges start from free metrics instead of the burst's history, so this is the
+    full loop exactly only when the metrics merge within the guard; the frozen neighbours' saturated priors pin the trellis
+    within a few rows, and INTEGRATION.md has the counts behind the default of 128 rows (``guard >= nrows`` makes any open
+    codeword's window the whole burst: the full loop bit for bit).  ``live_results`` returns what each pass worked on."""
 
-    and one ``ldpc_count``.  The detector's output is extrinsic per BIT: for ARTM the prior of the other bit of the same
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
+                 damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
+                 lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD, carrier=None,
+                 recovery=None) -> None:
+        if int(guard) < 0:
+            raise ValueError(f"guard = {guard} must not be negative")
+        self.live_only, self.guard = bool(live_only), int(guard)
+        super().__init__(code, ncw, sps=sps, detector=detector, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
+                         ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, carrier=carrier,
+                         recovery=recovery)
+        self.live_counts = _hip.zeros((self.outer, 3), "int64") if self.live_only else None
+        self.windows = _hip.zeros(4 + 2 * self.ncw, "int64") if self.live_only else None
+        self._live_out, self._live_first = None, 0          # the block's ext / bits buffers; first passes run
+
+    # ---------------------------------------------------------------- stages
+    def begin(self, nrows: int) -> None:
+        """Fresh loop state of one block: prior 0 on every row, every codeword open, no iterations."""
+        self._live_out = None
+        self._begin(nrows)
+
+    def live_windows(self, nrows: int):
+        """The live windows of the burst's ``nrows`` rows for the states as they are now -> the device table of ``idd_windows``
+        (kept in ``windows``).  Coded bit j is row j + 1; framed, codeword 0 starts behind the lock's p̂ and one marker."""
+        if self.framing is None:
+            return dev.idd_windows(self.state, nrows, self.code.n_tx, guard=self.guard, out=self.windows)
+        return dev.idd_windows(self.state, nrows, self.code.n_tx, self.framing.period, 1, self.lock, self.framing.L, self.guard, out=self.windows)
+
+    def detect(self, rows, first: bool = False, o: int | None = None):
+        """One detector pass, as every loop's.  ``live_only``: every later pass works on the live windows only and writes into
+        the first pass's buffers; ``o`` is the pass whose entry of ``live_results`` gets the table's counts (None: nobody's)."""
+        if not self.live_only:
+            return super().detect(rows, first)
+        if first:
+            ext, bits = self._live_out = self._soft_apriori(rows, None)
+            self._live_first += o is not None
+        else:
+            if self._live_out is None:
+                raise RuntimeError("live_only: the block's first pass (first=True) has not run")
+            table = self.live_windows(int(self._live_out[0].numel()))
+            if o is not None:
+                self.live_counts[o] += table[:3]
+            ext, bits = dev.viterbi_soft_apriori_windows(rows, self.prior, table, self.damping, out=self._live_out)
+        return self._coded(ext, bits, search=first)
+
+    # ---------------------------------------------------------------- blocks
+    def reset_counts(self) -> None:
+        super().reset_counts()
+        if self.live_only:
+            self.live_counts.zero_()
+            self._live_first = 0
+
+    def live_results(self) -> list[tuple[int, int, int]]:
+        """Per outer pass (``live_only=True``): (windows, live rows, codewords open on entry), summed over the blocks
+        run since ``reset_counts`` - synchronises.  Pass 1 is the plain detector on the whole burst: one
+        window of every row, every codeword open.  The later entries are the words [0 .. 2] of the passes' window tables,
+        added up on the device."""
+        if not self.live_only:
+            raise RuntimeError("live_results needs live_only=True")
+        _hip.check(_hip.lib().wf_ctx_check(_hip.ctx(), _hip.stream()))
+        rest = [tuple(int(v) for v in row) for row in self.live_counts.cpu().tolist()[1:]]
+        nrows = 0 if self.prior is None else int(self.prior.numel())
+        return [(self._live_first, self._live_first * nrows, self._live_first * self.ncw)] + rest
+
+
+class IterativeCPMLink(_LDPCLoop, CodedCPMLink):
+    """``CodedCPMLink`` with iterative detection and decoding, the loop of ``IterativeSOQPSKLink`` (``_LDPCLoop``) on the generic
+    CPM trellis: the detector is ``cpm_soft_apriori`` and the next prior is written at offset 0.  The detector's output is
+    extrinsic per BIT: for ARTM the prior of the other bit of the same
     quaternary symbol stays in, a bit's own never does.  Frozen codewords, ``per_pass``, ``ext_clip`` and the result tuples
     are ``IterativeSOQPSKLink``'s; the tail calls keep prior 0.  The phase state makes a CPM modulator a recursive inner code,
     which is where iterating pays most.
@@ -536,78 +594,12 @@ class IterativeCPMLink(CodedCPMLink):
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False,
                  prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None) -> None:
-        if outer < 1 or inner < 1:
-            raise ValueError("outer and inner must be at least 1")
-        if not (math.isfinite(damping) and damping > 0.0):
-            raise ValueError("damping must be finite and positive")
         if prior_warmup < 0:
             raise ValueError("prior_warmup must not be negative")
-        self.outer, self.inner, self.damping, self.prior_warmup = int(outer), int(inner), float(damping), int(prior_warmup)
-        self.ext_sat = 6.25 * int(sps) if ext_sat is None else float(ext_sat)
-        self.ext_clip = math.inf if ext_clip is None else float(ext_clip)
-        if not (math.isfinite(self.ext_sat) and self.ext_sat > 0.0 and self.ext_clip > 0.0):
-            raise ValueError("ext_sat must be finite and positive, ext_clip positive")
-        self.marker_prior = self.ext_sat if marker_prior is None else float(marker_prior)
-        if not math.isfinite(self.marker_prior):
-            raise ValueError("marker_prior must be finite")
-        super().__init__(code, ncw, waveform, sps, alpha, max_iter=inner, framing=framing, lead_bits=lead_bits)
-        self.per_pass = bool(per_pass)
-        self.pass_counts = _hip.zeros((self.outer, 4), "int64")
-        self.prior = self.state = self.iters = self.decided = self.ext = None
+        self.prior_warmup = int(prior_warmup)
+        super().__init__(code, ncw, waveform=waveform, sps=sps, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
+                         ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior)
 
-    # ---------------------------------------------------------------- stages
     def begin(self, ncalls: int | None = None) -> None:
         """Fresh loop state of one block: prior 0 on every bit of every call, every codeword open, no iterations."""
-        n = (self.ncalls if ncalls is None else int(ncalls)) * self.spec.bits_per_symbol
-        if self.prior is None or self.prior.numel() != n:
-            self.prior = _hip.zeros(n, "float32")
-            self.state = _hip.zeros(self.ncw, "uint8")
-            self.iters = _hip.zeros(self.ncw, "int32")
-            self.decided = _hip.zeros((self.ncw, self.code.k), "uint8")
-            self.ext = None if self.framing is None else _hip.zeros((self.ncw, self.code.n_tx), "float32")
-        else:
-            for t in (self.prior, self.state, self.iters, self.decided, self.ext):
-                if t is not None:
-                    t.zero_()
-
-    def detect(self, rows, first: bool = False):
-        """One detector pass -> (extrinsic λ of the coded bits, ncw x n_tx view; hard decisions of λ + π).  The first pass
-        of a block has prior 0 everywhere and takes the plain detector (bitwise the same result)."""
-        ext, bits = dev.cpm_soft_apriori(rows, self.spec, None if first else self.prior, self.damping, 0, 0 if first else self.prior_warmup,
-                                         d_rot=self._d_rot)
-        if self.framing is not None:
-            return self.deframe(ext, search=first), bits[:self.nch]
-        return ext[:self.nbits].view(self.ncw, self.code.n_tx), bits[:self.nbits]
-
-    def decode(self, ext) -> None:
-        """One decoder pass over the open codewords: decisions, iterations, states and the next prior, in place (framed: as
-        ``IterativeSOQPSKLink.decode``, the prior at offset 0)."""
-        if self.framing is not None:
-            dev.ldpc_decode_ext(self.code, ext, self.state, self.ext, self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
-                                max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
-            self.framing.scatter(self.ext, self.lock, self.prior, self.marker_prior)
-            return
-        dev.ldpc_decode_ext(self.code, ext, self.state, self.prior[:self.nbits], self.code.n_tx, scale=self.llr_scale, alpha=self.alpha,
-                            max_iter=self.inner, ext_clip=self.ext_clip, ext_sat=self.ext_sat, info_bits=self.decided, iters=self.iters)
-
-    # ---------------------------------------------------------------- blocks
-    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
-        info = self.info_bits(stream_id)
-        tx = dev.ldpc_encode(self.code, info)
-        rows, _syms = self.front_end(tx, ebn0_db, seed, stream_id)
-        self.begin(int(rows.shape[0]))
-        for o in range(self.outer):
-            ext, hard = self.detect(rows, first=o == 0)
-            if o == 0:
-                self.count_uncoded(hard, tx)
-            self.decode(ext)
-            if self.per_pass:
-                dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.pass_counts[o])
-        dev.ldpc_count(self.code, self.decided, info, self.state, self.iters, self.counts)
-        self.blocks += 1
-
-    def reset_counts(self) -> None:
-        super().reset_counts()
-        self.pass_counts.zero_()
-
-    pass_results = IterativeSOQPSKLink.pass_results
+        self._begin((self.ncalls if ncalls is None else int(ncalls)) * self.spec.bits_per_symbol)
