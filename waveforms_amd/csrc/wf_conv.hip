@@ -16,9 +16,6 @@
 // the segment's serial loop, so that loop holds no load from global memory.
 #include "wf_conv_common.h"
 
-#include <algorithm>
-#include <cmath>
-
 #define CONV_ENC_RUN 8              // steps per encoder thread
 #define CONV_ENC_THREADS 256
 
@@ -31,10 +28,7 @@ struct wf_conv_code {
     const int32_t *d_tx_var = nullptr;    // n_tx
 };
 
-struct conv_geom {
-    int G = 1;
-    int64_t waves = 0, per_launch = 0;
-    int nseg = 0;
+struct conv_geom : wf_wave_geom {
     size_t lds_bytes = 0, scratch_bytes = 0;
 };
 
@@ -47,13 +41,9 @@ static size_t conv_lds_bytes(int nu, int n_out)
 static conv_geom conv_geometry(const wf_ctx *ctx, const wf_conv_code *c, int64_t ncw)
 {
     conv_geom g;
-    g.G = 64 >> c->nu;
-    g.waves = (ncw + g.G - 1) / g.G;
-    g.nseg = (c->T + CONV_C - 1) / CONV_C;
-    const int64_t per_wave = (int64_t)g.nseg * 64 * 4;
-    g.per_launch = std::max<int64_t>(1, std::min<int64_t>(g.waves, std::min<int64_t>((int64_t)std::max(ctx->cus, 1) * 64, CONV_SCRATCH_CAP / per_wave)));
+    static_cast<wf_wave_geom &>(g) = wf_wave_geometry(ctx, c->nu, c->T, ncw, 0);
     g.lds_bytes = conv_lds_bytes(c->nu, c->n_out);
-    g.scratch_bytes = (size_t)(g.per_launch * per_wave);
+    g.scratch_bytes = (size_t)(g.per_launch * g.per_wave);
     return g;
 }
 
@@ -230,35 +220,20 @@ extern "C" int wf_conv_code_create(wf_ctx *ctx, int32_t K, int32_t n_out, const 
     WF_REQUIRE(n_out >= 2 && n_out <= 4, "wf_conv_code_create: n_out = %d outside 2 .. 4", n_out);
     const int nu = K - 1;
     for (int j = 0; j < n_out; ++j)
-        WF_REQUIRE(h_gen[j] < (1u << K) && ((h_gen[j] >> nu) & 1u) && (h_gen[j] & 1u),
-                   "wf_conv_code_create: generator %d = 0%o must be a K-bit mask with bit K - 1 and bit 0 set", j, h_gen[j]);
+        WF_REQUIRE(wf_tap_mask_ok(h_gen[j], K), "wf_conv_code_create: generator %d = 0%o must be a K-bit mask with bit K - 1 and bit 0 set", j, h_gen[j]);
     WF_REQUIRE(k >= 1 && (int64_t)n_out * ((int64_t)k + nu) <= CONV_MAX_N, "wf_conv_code_create: k = %d: N = n_out (k + K - 1) outside n_out K .. %d", k,
                CONV_MAX_N);
     const int32_t T = k + nu, N = n_out * T;
     WF_REQUIRE(n_tx >= 1 && n_tx <= N, "wf_conv_code_create: n_tx = %d outside 1 .. N = %d", n_tx, N);
     std::vector<int32_t> blob((size_t)N + n_tx, -1);
-    for (int t = 0; t < n_tx; ++t) {
-        const int v = h_tx_var[t];
-        WF_REQUIRE(v >= 0 && v < N, "wf_conv_code_create: tx_var[%d] = %d outside the code", t, v);
-        WF_REQUIRE(blob[v] < 0, "wf_conv_code_create: variable %d is transmitted twice", v);
-        blob[v] = t;
-        blob[(size_t)N + t] = v;
-    }
+    WF_TRY(wf_tx_table("wf_conv_code_create", h_tx_var, n_tx, N, blob.data(), blob.data() + N));
 
+    void *d_block;
+    WF_TRY(wf_code_upload("wf_conv_code_create", ctx->device, blob.data(), blob.size() * sizeof(int32_t), &d_block));
     wf_conv_code *c = new wf_conv_code();
-    c->device = ctx->device;
+    c->device = ctx->device, c->d_block = d_block;
     c->K = K, c->nu = nu, c->n_out = n_out, c->k = k, c->T = T, c->N = N, c->n_tx = n_tx;
     for (int j = 0; j < n_out; ++j) c->gen[j] = h_gen[j];
-    auto fail = [c](hipError_t e, const char *what) {
-        wf_set_error("wf_conv_code_create: %s failed: %s", what, hipGetErrorString(e));
-        if (c->d_block) (void)hipFree(c->d_block);
-        delete c;
-        return WF_ERR_HIP;
-    };
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return fail(e, "hipSetDevice");
-    if ((e = hipMalloc(&c->d_block, blob.size() * sizeof(int32_t))) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(c->d_block, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     c->d_var_src = static_cast<const int32_t *>(c->d_block);
     c->d_tx_var = c->d_var_src + N;
     *out = c;
@@ -268,21 +243,16 @@ extern "C" int wf_conv_code_create(wf_ctx *ctx, int32_t K, int32_t n_out, const 
 extern "C" int wf_conv_code_free(wf_conv_code *code)
 {
     if (!code) return WF_OK;
-    (void)hipSetDevice(code->device);
-    const hipError_t e = code->d_block ? hipFree(code->d_block) : hipSuccess;
+    const int rc = wf_code_release("wf_conv_code_free", code->device, {code->d_block});
     delete code;                          // (whatever hipFree said: the host struct never outlives the call)
-    if (e != hipSuccess) {
-        wf_set_error("wf_conv_code_free: hipFree failed: %s", hipGetErrorString(e));
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
+    return rc;
 }
 
 extern "C" int wf_conv_encode(wf_ctx *ctx, const wf_conv_code *code, const uint8_t *d_info, int64_t ncw, uint8_t *d_tx, void *stream)
 {
     WF_REQUIRE(ctx && code && d_info && d_tx, "wf_conv_encode: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_conv_encode: ncw must be at least 1");
-    WF_REQUIRE(code->device == ctx->device, "wf_conv_encode: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE_SAME_DEVICE("wf_conv_encode", code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     const int64_t work = ncw * ((code->T + CONV_ENC_RUN - 1) / CONV_ENC_RUN);
     const int grid = wf_grid_for(work, CONV_ENC_THREADS, std::max(ctx->cus, 1) * 16);
@@ -318,18 +288,15 @@ extern "C" int wf_conv_siso(wf_ctx *ctx, const wf_conv_code *code, const double 
 {
     WF_REQUIRE(ctx && code && d_llr, "wf_conv_siso: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_conv_siso: ncw must be at least 1");
-    WF_REQUIRE(std::isfinite(scale) && scale > 0.0, "wf_conv_siso: scale must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(scale), "wf_conv_siso: scale must be finite and positive");
     WF_REQUIRE(!d_ext || (ext_stride >= code->n_tx && ext_clip > 0.0f), "wf_conv_siso: d_ext needs ext_stride >= n_tx and ext_clip > 0");
     WF_REQUIRE(!d_ref_info || d_counts, "wf_conv_siso: d_ref_info needs d_counts");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_llr) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_info_prior) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_info_post) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_ext) & 3) == 0,
+    WF_REQUIRE(wf_aligned(d_llr, 8) && wf_aligned(d_counts, 8) && wf_aligned(d_info_prior, 4) && wf_aligned(d_info_post, 4) && wf_aligned(d_ext, 4),
                "wf_conv_siso: llr and counts must be 8-byte, prior, post and ext 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_conv_siso: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE_SAME_DEVICE("wf_conv_siso", code, ctx);
     const conv_geom g = conv_geometry(ctx, code, ncw);
     WF_HIP(hipSetDevice(ctx->device));
-    const int rc = wf_ctx_reserve_vit(ctx, (g.scratch_bytes + 7) / 8);
-    if (rc) return rc;
+    WF_TRY(wf_ctx_reserve_vit(ctx, (g.scratch_bytes + 7) / 8));
     conv_siso_args a;
     a.var_src = code->d_var_src;
     a.ckpt = reinterpret_cast<float *>(ctx->d_vit_edge);
@@ -338,9 +305,8 @@ extern "C" int wf_conv_siso(wf_ctx *ctx, const wf_conv_code *code, const double 
     for (int j = 0; j < 4; ++j) a.gen[j] = code->gen[j];
     a.counts = reinterpret_cast<unsigned long long *>(d_counts);
     // launches of at most g.per_launch waves (the checkpoints in the scratch are sized for that many)
-    const int64_t cws = g.per_launch * g.G;
-    for (int64_t b0 = 0; b0 < ncw; b0 += cws) {
-        a.ncw = std::min(cws, ncw - b0);
+    return wf_for_slices(ncw, g.per_launch * g.G, [&](int64_t b0, int64_t count) -> int {
+        a.ncw = count;
         a.llr = d_llr + b0 * code->n_tx;
         a.prior = d_info_prior ? d_info_prior + b0 * code->k : nullptr;
         a.bits = d_info_bits ? d_info_bits + b0 * code->k : nullptr;
@@ -357,6 +323,6 @@ extern "C" int wf_conv_siso(wf_ctx *ctx, const wf_conv_code *code, const double 
         default: conv_siso_launch<6>(code->n_out, grid, st, a); break;
         }
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
 }

@@ -1,12 +1,31 @@
 // wf_conv_common.h — device helpers of the trellis decoders whose lanes are states (wf_conv.hip: feed-forward convolutional
 // codes; wf_turbo.hip: recursive systematic constituents of a turbo code): a branch's gamma, the masked -INFINITY selects and
-// the all-reduce over the S lanes of a codeword.
+// the all-reduce over the S lanes of a codeword; and the launch geometry the two share on the host.
 #pragma once
-#include "wf_common.h"
+#include "wf_code.h"
 
 #define CONV_MAX_N 32768
 #define CONV_C 32                   // checkpoint spacing = steps per segment
 #define CONV_SCRATCH_CAP (128ll << 20)   // scratch bytes one launch may use
+
+// A wave decodes G = 64 / 2^nu codewords in lockstep, in segments of CONV_C of their T steps; one launch takes as many waves as
+// the device holds at once and as the scratch cap has room for at per_wave bytes each: a 256-byte checkpoint row per segment
+// plus `more_per_wave`.
+struct wf_wave_geom {
+    int G = 1, nseg = 0;
+    int64_t waves = 0, per_launch = 0, per_wave = 0;
+};
+
+static wf_wave_geom wf_wave_geometry(const wf_ctx *ctx, int nu, int T, int64_t ncw, int64_t more_per_wave)
+{
+    wf_wave_geom g;
+    g.G = 64 >> nu;
+    g.waves = (ncw + g.G - 1) / g.G;
+    g.nseg = (T + CONV_C - 1) / CONV_C;
+    g.per_wave = (int64_t)g.nseg * 64 * 4 + more_per_wave;
+    g.per_launch = std::max<int64_t>(1, std::min<int64_t>(g.waves, std::min<int64_t>((int64_t)std::max(ctx->cus, 1) * 64, CONV_SCRATCH_CAP / g.per_wave)));
+    return g;
+}
 
 #ifdef __HIPCC__
 // gamma of one branch: start (u ? -A : +0), then minus L_j where the branch's code bit j is 1, j increasing.  (x - (+0) is x

@@ -150,36 +150,26 @@ extern "C" int wf_ldpc_decode_ext(wf_ctx *ctx, const wf_ldpc_code *code, const d
     WF_REQUIRE(ctx && code && d_llr && d_state && d_ext, "wf_ldpc_decode_ext: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_ldpc_decode_ext: ncw must be at least 1");
     WF_REQUIRE(max_iter >= 1 && max_iter <= 10000, "wf_ldpc_decode_ext: max_iter = %d outside 1 .. 10000", max_iter);
-    WF_REQUIRE(std::isfinite(scale) && scale > 0.0, "wf_ldpc_decode_ext: scale must be finite and positive");
-    WF_REQUIRE(std::isfinite(alpha) && alpha > 0.0f, "wf_ldpc_decode_ext: alpha must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(scale), "wf_ldpc_decode_ext: scale must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(alpha), "wf_ldpc_decode_ext: alpha must be finite and positive");
     WF_REQUIRE(ext_stride >= code->n_tx, "wf_ldpc_decode_ext: ext_stride = %lld is below n_tx = %d", (long long)ext_stride, code->n_tx);
     WF_REQUIRE(ext_clip > 0.0f, "wf_ldpc_decode_ext: ext_clip must be positive (INFINITY: no clip)");
-    WF_REQUIRE(std::isfinite(ext_sat) && ext_sat > 0.0f, "wf_ldpc_decode_ext: ext_sat must be finite and positive");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_llr) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_post) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_iters) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_ext) & 3) == 0,
+    WF_REQUIRE(wf_finite_pos(ext_sat), "wf_ldpc_decode_ext: ext_sat must be finite and positive");
+    WF_REQUIRE(wf_aligned(d_llr, 8) && wf_aligned(d_post, 4) && wf_aligned(d_iters, 4) && wf_aligned(d_ext, 4),
                "wf_ldpc_decode_ext: llr must be 8-byte, post, iters and ext 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_ldpc_decode_ext: the code lives on device %d, the context on %d", code->device, ctx->device);
-    const ldpc_geom g = ldpc_geometry(ctx, code, ncw);
-    WF_HIP(hipSetDevice(ctx->device));
+    WF_REQUIRE_SAME_DEVICE("wf_ldpc_decode_ext", code, ctx);
+    ldpc_geom g;
     idd_dec_args a;
+    WF_TRY(ldpc_prepare(ctx, code, ncw, reinterpret_cast<const void *>(&idd_decode_kernel<true>), reinterpret_cast<const void *>(&idd_decode_kernel<false>), &g,
+                        &a.gstate));
     a.layer = code->d_layer, a.ell = code->d_ell, a.check_ptr = code->d_check_ptr, a.edge_var = code->d_edge_var;
     a.var_src = code->d_var_src, a.info_var = code->d_info_var, a.tx_var = code->d_tx_var;
     a.n = code->n, a.m = code->m, a.nlayers = code->nlayers, a.n_tx = code->n_tx, a.k = code->k, a.G = g.G, a.max_iter = max_iter;
     a.ext_stride = ext_stride;
     a.scale = scale, a.alpha = alpha, a.ext_clip = ext_clip, a.ext_sat = ext_sat;
-    a.gstate = nullptr;
-    if (!g.lds_state) {
-        const int rc = wf_ctx_reserve_vit(ctx, (g.scratch_bytes + 7) / 8);
-        if (rc) return rc;
-        a.gstate = reinterpret_cast<uint4 *>(ctx->d_vit_edge);
-    }
-    const void *fn = g.lds_state ? reinterpret_cast<const void *>(&idd_decode_kernel<true>) : reinterpret_cast<const void *>(&idd_decode_kernel<false>);
-    if (g.lds_bytes > LDPC_LDS_CAP - 1024)     // (the kernel's own static LDS comes on top)
-        WF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
     // slices of at most g.grid workgroups, as wf_ldpc_decode (the scratch form's check state is sized for that many)
-    const int64_t per_launch = g.grid * g.G;
-    for (int64_t b0 = 0; b0 < ncw; b0 += per_launch) {
-        a.ncw = std::min(per_launch, ncw - b0);
+    return wf_for_slices(ncw, g.grid * g.G, [&](int64_t b0, int64_t count) -> int {
+        a.ncw = count;
         a.llr = d_llr + b0 * code->n_tx;
         a.state = d_state + b0;
         a.info_bits = d_info_bits ? d_info_bits + b0 * code->k : nullptr;
@@ -192,8 +182,8 @@ extern "C" int wf_ldpc_decode_ext(wf_ctx *ctx, const wf_ldpc_code *code, const d
         else
             hipLaunchKernelGGL(idd_decode_kernel<false>, dim3(grid), dim3(LDPC_THREADS), g.lds_bytes, wf_stream(stream), a);
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
 }
 
 extern "C" int wf_ldpc_count(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_t *d_info_bits, const uint8_t *d_ref_info,
@@ -201,9 +191,8 @@ extern "C" int wf_ldpc_count(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_
 {
     WF_REQUIRE(ctx && code && d_info_bits && d_ref_info && d_state && d_iters && d_counts, "wf_ldpc_count: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_ldpc_count: ncw must be at least 1");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_iters) & 3) == 0,
-               "wf_ldpc_count: counts must be 8-byte and iters 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_ldpc_count: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE(wf_aligned(d_counts, 8) && wf_aligned(d_iters, 4), "wf_ldpc_count: counts must be 8-byte and iters 4-byte aligned");
+    WF_REQUIRE_SAME_DEVICE("wf_ldpc_count", code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     const unsigned grid = (unsigned)std::min<int64_t>(ncw, (int64_t)std::max(ctx->cus, 1) * 8);
     hipLaunchKernelGGL(idd_count_kernel, dim3(grid), dim3(LDPC_THREADS), 0, wf_stream(stream), d_info_bits, d_ref_info, d_state, d_iters, ncw,

@@ -2,10 +2,7 @@
 // (wf_ldpc.hip) and the iterative-detection form of it (wf_idd.hip).
 #pragma once
 
-#include "wf_common.h"
-
-#include <algorithm>
-#include <cmath>
+#include "wf_code.h"
 
 #define LDPC_THREADS 256
 #define LDPC_MAX_G 8
@@ -60,6 +57,22 @@ static ldpc_geom ldpc_geometry(const wf_ctx *ctx, const wf_ldpc_code *c, int64_t
     g.grid = g.lds_state ? g.groups : std::min<int64_t>(g.groups, (int64_t)std::max(ctx->cus, 1) * per_cu);
     g.scratch_bytes = g.lds_state ? 0 : (size_t)g.grid * G * st_bytes;
     return g;
+}
+
+// What the two decoders do before their launches: the geometry, the device, the scratch form's check states (*gstate, else
+// null) and room for the dynamic LDS.  fn_lds / fn_scratch: the decoder's kernel in its two forms.
+static int ldpc_prepare(wf_ctx *ctx, const wf_ldpc_code *code, int64_t ncw, const void *fn_lds, const void *fn_scratch, ldpc_geom *g, uint4 **gstate)
+{
+    *g = ldpc_geometry(ctx, code, ncw);
+    WF_HIP(hipSetDevice(ctx->device));
+    *gstate = nullptr;
+    if (!g->lds_state) {
+        WF_TRY(wf_ctx_reserve_vit(ctx, (g->scratch_bytes + 7) / 8));
+        *gstate = reinterpret_cast<uint4 *>(ctx->d_vit_edge);
+    }
+    if (g->lds_bytes > LDPC_LDS_CAP - 1024)     // (the kernel's own static LDS comes on top)
+        WF_HIP(hipFuncSetAttribute(g->lds_state ? fn_lds : fn_scratch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->lds_bytes));
+    return WF_OK;
 }
 
 // R_e rebuilt bitwise from a check's state {r1, r2, argmin, sign word}

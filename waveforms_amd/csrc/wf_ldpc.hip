@@ -201,12 +201,7 @@ extern "C" int wf_ldpc_code_create(wf_ctx *ctx, int32_t n, int32_t m, const int3
         slots_total += slots * (h_layer_ptr[l + 1] - h_layer_ptr[l]);
     }
     std::vector<int32_t> var_src(n, -1);
-    for (int t = 0; t < n_tx; ++t) {
-        const int v = h_tx_var[t];
-        WF_REQUIRE(v >= 0 && v < n, "wf_ldpc_code_create: tx_var[%d] = %d outside the code", t, v);
-        WF_REQUIRE(var_src[v] < 0, "wf_ldpc_code_create: variable %d is transmitted twice", v);
-        var_src[v] = t;
-    }
+    WF_TRY(wf_tx_table("wf_ldpc_code_create", h_tx_var, n_tx, n, var_src.data(), nullptr));
     std::vector<int32_t> is_info(n, 0);
     for (int i = 0; i < k; ++i) {
         const int v = h_info_var[i];
@@ -242,26 +237,19 @@ extern "C" int wf_ldpc_code_create(wf_ctx *ctx, int32_t n, int32_t m, const int3
                  o_evar = put(h_edge_var, (size_t)nedges), o_src = put(var_src.data(), (size_t)n), o_tx = put(h_tx_var, (size_t)n_tx),
                  o_info = put(h_info_var, (size_t)k), o_par = put(par.data(), par.size());
 
+    void *d_block, *d_gen = nullptr;
+    WF_TRY(wf_code_upload("wf_ldpc_code_create", ctx->device, blob.data(), blob.size() * sizeof(int32_t), &d_block));
+    if (h_parity_gen) {
+        const int rc = wf_code_upload("wf_ldpc_code_create", ctx->device, h_parity_gen, (size_t)(n - k) * ((k + 63) / 64) * sizeof(uint64_t), &d_gen);
+        if (rc) {
+            (void)hipFree(d_block);
+            return rc;
+        }
+    }
     wf_ldpc_code *c = new wf_ldpc_code();
-    c->device = ctx->device;
+    c->device = ctx->device, c->d_block = d_block, c->d_gen = static_cast<uint64_t *>(d_gen);
     c->n = n, c->m = m, c->nlayers = nlayers, c->n_tx = n_tx, c->k = k, c->kw = (k + 63) / 64, c->lmax = lmax, c->nedges = nedges;
     c->has_gen = h_parity_gen != nullptr;
-    auto fail = [c](hipError_t e, const char *what) {
-        wf_set_error("wf_ldpc_code_create: %s failed: %s", what, hipGetErrorString(e));
-        if (c->d_block) (void)hipFree(c->d_block);
-        if (c->d_gen) (void)hipFree(c->d_gen);
-        delete c;
-        return WF_ERR_HIP;
-    };
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return fail(e, "hipSetDevice");
-    if ((e = hipMalloc(&c->d_block, blob.size() * sizeof(int32_t))) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(c->d_block, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
-    if (c->has_gen) {
-        const size_t words = (size_t)(n - k) * c->kw;
-        if ((e = hipMalloc(&c->d_gen, words * sizeof(uint64_t))) != hipSuccess) return fail(e, "hipMalloc");
-        if ((e = hipMemcpy(c->d_gen, h_parity_gen, words * sizeof(uint64_t), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
-    }
     const int32_t *base = static_cast<const int32_t *>(c->d_block);
     c->d_layer = base + o_layer, c->d_ell = base + o_ell, c->d_check_ptr = base + o_cptr, c->d_edge_var = base + o_evar;
     c->d_var_src = base + o_src, c->d_tx_var = base + o_tx, c->d_info_var = base + o_info, c->d_par_var = base + o_par;
@@ -272,11 +260,9 @@ extern "C" int wf_ldpc_code_create(wf_ctx *ctx, int32_t n, int32_t m, const int3
 extern "C" int wf_ldpc_code_free(wf_ldpc_code *code)
 {
     if (!code) return WF_OK;
-    (void)hipSetDevice(code->device);
-    if (code->d_block) WF_HIP(hipFree(code->d_block));
-    if (code->d_gen) WF_HIP(hipFree(code->d_gen));
-    delete code;
-    return WF_OK;
+    const int rc = wf_code_release("wf_ldpc_code_free", code->device, {code->d_block, code->d_gen});
+    delete code;                          // (whatever hipFree said: the host struct never outlives the call)
+    return rc;
 }
 
 extern "C" int wf_ldpc_encode(wf_ctx *ctx, const wf_ldpc_code *code, const uint8_t *d_info, int64_t ncw, uint8_t *d_tx, void *stream)
@@ -284,7 +270,7 @@ extern "C" int wf_ldpc_encode(wf_ctx *ctx, const wf_ldpc_code *code, const uint8
     WF_REQUIRE(ctx && code && d_info && d_tx, "wf_ldpc_encode: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_ldpc_encode: ncw must be at least 1");
     WF_REQUIRE(code->has_gen, "wf_ldpc_encode: the code was created without a parity generator (decode only)");
-    WF_REQUIRE(code->device == ctx->device, "wf_ldpc_encode: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE_SAME_DEVICE("wf_ldpc_encode", code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     const unsigned grid = (unsigned)std::min<int64_t>(ncw, (int64_t)std::max(ctx->cus, 1) * 4);
     hipLaunchKernelGGL(ldpc_encode_kernel, dim3(grid), dim3(LDPC_THREADS), 0, wf_stream(stream), d_info, ncw, code->k, code->kw,
@@ -312,34 +298,24 @@ extern "C" int wf_ldpc_decode(wf_ctx *ctx, const wf_ldpc_code *code, const doubl
     WF_REQUIRE(ctx && code && d_llr, "wf_ldpc_decode: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_ldpc_decode: ncw must be at least 1");
     WF_REQUIRE(max_iter >= 1 && max_iter <= 10000, "wf_ldpc_decode: max_iter = %d outside 1 .. 10000", max_iter);
-    WF_REQUIRE(std::isfinite(scale) && scale > 0.0, "wf_ldpc_decode: scale must be finite and positive");
-    WF_REQUIRE(std::isfinite(alpha) && alpha > 0.0f, "wf_ldpc_decode: alpha must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(scale), "wf_ldpc_decode: scale must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(alpha), "wf_ldpc_decode: alpha must be finite and positive");
     WF_REQUIRE(!d_ref_info || d_counts, "wf_ldpc_decode: d_ref_info needs d_counts");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_llr) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_post) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_iters) & 3) == 0,
+    WF_REQUIRE(wf_aligned(d_llr, 8) && wf_aligned(d_counts, 8) && wf_aligned(d_post, 4) && wf_aligned(d_iters, 4),
                "wf_ldpc_decode: llr and counts must be 8-byte, post and iters 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_ldpc_decode: the code lives on device %d, the context on %d", code->device, ctx->device);
-    const ldpc_geom g = ldpc_geometry(ctx, code, ncw);
-    WF_HIP(hipSetDevice(ctx->device));
+    WF_REQUIRE_SAME_DEVICE("wf_ldpc_decode", code, ctx);
+    ldpc_geom g;
     ldpc_dec_args a;
+    WF_TRY(ldpc_prepare(ctx, code, ncw, reinterpret_cast<const void *>(&ldpc_decode_kernel<true>), reinterpret_cast<const void *>(&ldpc_decode_kernel<false>), &g,
+                        &a.gstate));
     a.layer = code->d_layer, a.ell = code->d_ell, a.check_ptr = code->d_check_ptr, a.edge_var = code->d_edge_var;
     a.var_src = code->d_var_src, a.info_var = code->d_info_var;
     a.n = code->n, a.m = code->m, a.nlayers = code->nlayers, a.n_tx = code->n_tx, a.k = code->k, a.G = g.G, a.max_iter = max_iter;
     a.scale = scale, a.alpha = alpha;
     a.counts = reinterpret_cast<unsigned long long *>(d_counts);
-    a.gstate = nullptr;
-    if (!g.lds_state) {
-        const int rc = wf_ctx_reserve_vit(ctx, (g.scratch_bytes + 7) / 8);
-        if (rc) return rc;
-        a.gstate = reinterpret_cast<uint4 *>(ctx->d_vit_edge);
-    }
-    const void *fn = g.lds_state ? reinterpret_cast<const void *>(&ldpc_decode_kernel<true>) : reinterpret_cast<const void *>(&ldpc_decode_kernel<false>);
-    if (g.lds_bytes > LDPC_LDS_CAP - 1024)     // (the kernel's own static LDS comes on top)
-        WF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds_bytes));
     // slices of at most g.grid workgroups (the scratch form's check state is sized for that many)
-    const int64_t per_launch = g.grid * g.G;
-    for (int64_t b0 = 0; b0 < ncw; b0 += per_launch) {
-        a.ncw = std::min(per_launch, ncw - b0);
+    return wf_for_slices(ncw, g.grid * g.G, [&](int64_t b0, int64_t count) -> int {
+        a.ncw = count;
         a.llr = d_llr + b0 * code->n_tx;
         a.info_bits = d_info_bits ? d_info_bits + b0 * code->k : nullptr;
         a.post = d_post ? d_post + b0 * code->n : nullptr;
@@ -351,6 +327,6 @@ extern "C" int wf_ldpc_decode(wf_ctx *ctx, const wf_ldpc_code *code, const doubl
         else
             hipLaunchKernelGGL(ldpc_decode_kernel<false>, dim3(grid), dim3(LDPC_THREADS), g.lds_bytes, wf_stream(stream), a);
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
 }

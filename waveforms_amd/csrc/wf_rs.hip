@@ -29,10 +29,8 @@
 // measured on one MI355X on blocks of 2 443 codewords (profiles/rs_multiply_ab.json) the register form takes
 // 1.5 times as long where nearly every syndrome is zero and 1.7 times where nearly every codeword is corrected.  The other
 // form is a compile-time switch (-DRS_MUL_TABLES=0) kept for that comparison; both compute the same bytes.
-#include "wf_common.h"
+#include "wf_code.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstring>
 
 #define RS_MAX_DEPTH 8
@@ -460,19 +458,11 @@ extern "C" int wf_rs_code_create(wf_ctx *ctx, int32_t prim, int32_t fcr, int32_t
     }
     for (int j = 0; j < t2; ++j) tab[RS_TAB_GEN + j] = (uint8_t)g[j];
 
+    void *d_tab;
+    WF_TRY(wf_code_upload("wf_rs_code_create", ctx->device, tab.data(), tab.size(), &d_tab));
     wf_rs_code *c = new wf_rs_code();
-    c->device = ctx->device;
+    c->device = ctx->device, c->d_tab = static_cast<uint8_t *>(d_tab);
     c->prim = prim, c->fcr = fcr, c->step = step, c->n = n, c->k = k, c->t = t2 / 2, c->depth = depth;
-    auto fail = [c](hipError_t e, const char *what) {
-        wf_set_error("wf_rs_code_create: %s failed: %s", what, hipGetErrorString(e));
-        if (c->d_tab) (void)hipFree(c->d_tab);
-        delete c;
-        return WF_ERR_HIP;
-    };
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return fail(e, "hipSetDevice");
-    if ((e = hipMalloc(reinterpret_cast<void **>(&c->d_tab), tab.size())) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(c->d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     *out = c;
     return WF_OK;
 }
@@ -480,14 +470,9 @@ extern "C" int wf_rs_code_create(wf_ctx *ctx, int32_t prim, int32_t fcr, int32_t
 extern "C" int wf_rs_code_free(wf_rs_code *code)
 {
     if (!code) return WF_OK;
-    (void)hipSetDevice(code->device);
-    const hipError_t e = code->d_tab ? hipFree(code->d_tab) : hipSuccess;
-    delete code;
-    if (e != hipSuccess) {
-        wf_set_error("wf_rs_code_free: hipFree failed: %s", hipGetErrorString(e));
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
+    const int rc = wf_code_release("wf_rs_code_free", code->device, {code->d_tab});
+    delete code;                          // (whatever hipFree said: the host struct never outlives the call)
+    return rc;
 }
 
 static rs_args rs_make_args(const wf_rs_code *code, int bits, const void *in, const void *out, const void *ref)
@@ -505,18 +490,17 @@ extern "C" int wf_rs_encode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *
     WF_REQUIRE(ctx && code && d_msg && d_tx, "wf_rs_encode: NULL argument");
     WF_REQUIRE(nframes >= 1, "wf_rs_encode: nframes must be at least 1");
     WF_REQUIRE(bits == 0 || bits == 1, "wf_rs_encode: bits = %d outside {0, 1}", bits);
-    WF_REQUIRE(code->device == ctx->device, "wf_rs_encode: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE_SAME_DEVICE("wf_rs_encode", code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     rs_args a = rs_make_args(code, bits, d_msg, d_tx, nullptr);
     const int64_t sym = bits ? 8 : 1, in_frame = sym * code->k * code->depth, out_frame = sym * code->n * code->depth;
-    for (int64_t f0 = 0; f0 < nframes; f0 += RS_MAX_GRID) {
-        const unsigned grid = (unsigned)std::min<int64_t>(RS_MAX_GRID, nframes - f0);
+    return wf_for_slices(nframes, RS_MAX_GRID, [&](int64_t f0, int64_t count) -> int {
         a.in = d_msg + f0 * in_frame;
         a.out = d_tx + f0 * out_frame;
-        hipLaunchKernelGGL(rs_encode_kernel<RS_MUL_TABLES != 0>, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
+        hipLaunchKernelGGL(rs_encode_kernel<RS_MUL_TABLES != 0>, dim3((unsigned)count), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
 }
 
 extern "C" int wf_rs_decode_geometry(wf_ctx *ctx, const wf_rs_code *code, int64_t nframes, int64_t *h_geom)
@@ -530,57 +514,44 @@ extern "C" int wf_rs_decode_geometry(wf_ctx *ctx, const wf_rs_code *code, int64_
     return WF_OK;
 }
 
-extern "C" int wf_rs_decode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, int64_t nframes, int32_t bits, uint8_t *d_msg_out,
-                            int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream)
+// wf_rs_decode (eras = false: d_erase is null and stays unread) and wf_rs_decode_erasures (eras = true)
+static int rs_decode_call(const char *fn, bool eras, wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, const uint8_t *d_erase, int64_t nframes,
+                          int32_t bits, uint8_t *d_msg_out, int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream)
 {
-    WF_REQUIRE(ctx && code && d_rx && d_msg_out, "wf_rs_decode: NULL argument");
-    WF_REQUIRE(nframes >= 1, "wf_rs_decode: nframes must be at least 1");
-    WF_REQUIRE(bits == 0 || bits == 1, "wf_rs_decode: bits = %d outside {0, 1}", bits);
-    WF_REQUIRE(!d_ref_msg || d_counts, "wf_rs_decode: d_ref_msg needs d_counts");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3) == 0,
-               "wf_rs_decode: counts must be 8-byte, status 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_rs_decode: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE(ctx && code && d_rx && (d_erase || !eras) && d_msg_out, "%s: NULL argument", fn);
+    WF_REQUIRE(nframes >= 1, "%s: nframes must be at least 1", fn);
+    WF_REQUIRE(bits == 0 || bits == 1, "%s: bits = %d outside {0, 1}", fn, bits);
+    WF_REQUIRE(!d_ref_msg || d_counts, "%s: d_ref_msg needs d_counts", fn);
+    WF_REQUIRE(wf_aligned(d_counts, 8) && wf_aligned(d_status, 4), "%s: counts must be 8-byte, status 4-byte aligned", fn);
+    WF_REQUIRE_SAME_DEVICE(fn, code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     rs_args a = rs_make_args(code, bits, d_rx, d_msg_out, d_ref_msg);
     a.counts = reinterpret_cast<unsigned long long *>(d_counts);
     const int64_t sym = bits ? 8 : 1, in_frame = sym * code->n * code->depth, msg_frame = sym * code->k * code->depth;
-    for (int64_t f0 = 0; f0 < nframes; f0 += RS_MAX_GRID) {
-        const unsigned grid = (unsigned)std::min<int64_t>(RS_MAX_GRID, nframes - f0);
+    return wf_for_slices(nframes, RS_MAX_GRID, [&](int64_t f0, int64_t count) -> int {
         a.in = d_rx + f0 * in_frame;
+        a.erase = eras ? d_erase + f0 * code->n * code->depth : nullptr;
         a.out = d_msg_out + f0 * msg_frame;
         a.ref = d_ref_msg ? d_ref_msg + f0 * msg_frame : nullptr;
         a.status = d_status ? d_status + f0 * code->depth : nullptr;
-        hipLaunchKernelGGL(rs_decode_kernel<RS_MUL_TABLES != 0>, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
+        const dim3 grid((unsigned)count), block(WF_WAVE * code->depth);
+        if (!eras) hipLaunchKernelGGL(rs_decode_kernel<RS_MUL_TABLES != 0>, grid, block, 0, wf_stream(stream), a);
+        else hipLaunchKernelGGL(rse_decode_kernel<RS_MUL_TABLES != 0>, grid, block, 0, wf_stream(stream), a);
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
+}
+
+extern "C" int wf_rs_decode(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, int64_t nframes, int32_t bits, uint8_t *d_msg_out,
+                            int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream)
+{
+    return rs_decode_call("wf_rs_decode", false, ctx, code, d_rx, nullptr, nframes, bits, d_msg_out, d_status, d_ref_msg, d_counts, stream);
 }
 
 extern "C" int wf_rs_decode_erasures(wf_ctx *ctx, const wf_rs_code *code, const uint8_t *d_rx, const uint8_t *d_erase, int64_t nframes, int32_t bits,
                                      uint8_t *d_msg_out, int32_t *d_status, const uint8_t *d_ref_msg, int64_t *d_counts, void *stream)
 {
-    WF_REQUIRE(ctx && code && d_rx && d_erase && d_msg_out, "wf_rs_decode_erasures: NULL argument");
-    WF_REQUIRE(nframes >= 1, "wf_rs_decode_erasures: nframes must be at least 1");
-    WF_REQUIRE(bits == 0 || bits == 1, "wf_rs_decode_erasures: bits = %d outside {0, 1}", bits);
-    WF_REQUIRE(!d_ref_msg || d_counts, "wf_rs_decode_erasures: d_ref_msg needs d_counts");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_status) & 3) == 0,
-               "wf_rs_decode_erasures: counts must be 8-byte, status 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_rs_decode_erasures: the code lives on device %d, the context on %d", code->device, ctx->device);
-    WF_HIP(hipSetDevice(ctx->device));
-    rs_args a = rs_make_args(code, bits, d_rx, d_msg_out, d_ref_msg);
-    a.counts = reinterpret_cast<unsigned long long *>(d_counts);
-    const int64_t sym = bits ? 8 : 1, in_frame = sym * code->n * code->depth, msg_frame = sym * code->k * code->depth;
-    for (int64_t f0 = 0; f0 < nframes; f0 += RS_MAX_GRID) {
-        const unsigned grid = (unsigned)std::min<int64_t>(RS_MAX_GRID, nframes - f0);
-        a.in = d_rx + f0 * in_frame;
-        a.erase = d_erase + f0 * code->n * code->depth;
-        a.out = d_msg_out + f0 * msg_frame;
-        a.ref = d_ref_msg ? d_ref_msg + f0 * msg_frame : nullptr;
-        a.status = d_status ? d_status + f0 * code->depth : nullptr;
-        hipLaunchKernelGGL(rse_decode_kernel<RS_MUL_TABLES != 0>, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
-        WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+    return rs_decode_call("wf_rs_decode_erasures", true, ctx, code, d_rx, d_erase, nframes, bits, d_msg_out, d_status, d_ref_msg, d_counts, stream);
 }
 
 extern "C" int wf_rs_mark_erasures(wf_ctx *ctx, const wf_rs_code *code, const float *d_post, int64_t nframes, int32_t f_max, float below,
@@ -590,20 +561,19 @@ extern "C" int wf_rs_mark_erasures(wf_ctx *ctx, const wf_rs_code *code, const fl
     WF_REQUIRE(nframes >= 1, "wf_rs_mark_erasures: nframes must be at least 1");
     WF_REQUIRE(f_max >= 0 && f_max <= 2 * code->t, "wf_rs_mark_erasures: f_max = %d outside 0 .. 2t = %d", f_max, 2 * code->t);
     WF_REQUIRE(std::isfinite(below), "wf_rs_mark_erasures: below must be finite");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_post) & 3) == 0, "wf_rs_mark_erasures: d_post must be 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_rs_mark_erasures: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE(wf_aligned(d_post, 4), "wf_rs_mark_erasures: d_post must be 4-byte aligned");
+    WF_REQUIRE_SAME_DEVICE("wf_rs_mark_erasures", code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     rs_mark_args a;
     a.n = code->n, a.depth = code->depth, a.f_max = f_max;
     a.below = 0;
     if (below > 0.0f) std::memcpy(&a.below, &below, 4);
     const int64_t frame = (int64_t)code->n * code->depth;
-    for (int64_t f0 = 0; f0 < nframes; f0 += RS_MAX_GRID) {
-        const unsigned grid = (unsigned)std::min<int64_t>(RS_MAX_GRID, nframes - f0);
+    return wf_for_slices(nframes, RS_MAX_GRID, [&](int64_t f0, int64_t count) -> int {
         a.post = reinterpret_cast<const uint32_t *>(d_post) + 8 * f0 * frame;
         a.erase = d_erase + f0 * frame;
-        hipLaunchKernelGGL(rse_mark_kernel, dim3(grid), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
+        hipLaunchKernelGGL(rse_mark_kernel, dim3((unsigned)count), dim3(WF_WAVE * code->depth), 0, wf_stream(stream), a);
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
 }

@@ -20,9 +20,6 @@
 // the state-map scan of wf_encode.hip) hands every run its start state, and the run is walked again to emit its bits.
 #include "wf_conv_common.h"
 
-#include <algorithm>
-#include <cmath>
-
 #define TURBO_ENC_THREADS 256       // = the most runs of one constituent
 #define TURBO_ENC_MIN_RUN 8         // message steps per encoder thread, at least
 
@@ -52,10 +49,7 @@ struct turbo_cold {
     int32_t n_tx;
 };
 
-struct turbo_geom {
-    int G = 1;
-    int64_t waves = 0, per_launch = 0;
-    int nseg = 0;
+struct turbo_geom : wf_wave_geom {
     size_t lds_bytes = 0, scratch_bytes = 0;
     size_t off_a1 = 0, off_a2 = 0, off_d1 = 0;      // byte offsets in the scratch behind the checkpoints
 };
@@ -69,12 +63,9 @@ static size_t turbo_lds_bytes(int nu, int m)
 static turbo_geom turbo_geometry(const wf_ctx *ctx, const wf_turbo_code *c, int64_t ncw)
 {
     turbo_geom g;
-    g.G = 64 >> c->nu;
-    g.waves = (ncw + g.G - 1) / g.G;
-    g.nseg = (c->T + CONV_C - 1) / CONV_C;
     // per wave: the checkpoints, A1 and A2 (G x k floats each) and constituent 1's decisions (G x k bytes)
-    const int64_t gk = (int64_t)g.G * c->k, per_wave = (int64_t)g.nseg * 64 * 4 + 9 * gk;
-    g.per_launch = std::max<int64_t>(1, std::min<int64_t>(g.waves, std::min<int64_t>((int64_t)std::max(ctx->cus, 1) * 64, CONV_SCRATCH_CAP / per_wave)));
+    const int64_t gk = (int64_t)(64 >> c->nu) * c->k;
+    static_cast<wf_wave_geom &>(g) = wf_wave_geometry(ctx, c->nu, c->T, ncw, 9 * gk);
     g.lds_bytes = turbo_lds_bytes(c->nu, c->m);
     g.off_a1 = (size_t)(g.per_launch * g.nseg * 64 * 4);
     g.off_a2 = g.off_a1 + (size_t)(g.per_launch * gk * 4);
@@ -379,10 +370,10 @@ extern "C" int wf_turbo_code_create(wf_ctx *ctx, int32_t K, int32_t n_par, uint3
     WF_REQUIRE(K >= 3 && K <= 5, "wf_turbo_code_create: K = %d outside 3 .. 5", K);
     WF_REQUIRE(n_par >= 1 && n_par <= 3, "wf_turbo_code_create: n_par = %d outside 1 .. 3", n_par);
     const int nu = K - 1, m = 1 + n_par;
-    WF_REQUIRE(fb < (1u << K) && ((fb >> nu) & 1u) && (fb & 1u), "wf_turbo_code_create: feedback mask 0%o must be a K-bit mask with bit K - 1 and bit 0 set", fb);
+    WF_REQUIRE(wf_tap_mask_ok(fb, K), "wf_turbo_code_create: feedback mask 0%o must be a K-bit mask with bit K - 1 and bit 0 set", fb);
     for (int j = 0; j < n_par; ++j) {
-        WF_REQUIRE(h_gen[j] < (1u << K) && ((h_gen[j] >> nu) & 1u) && (h_gen[j] & 1u),
-                   "wf_turbo_code_create: parity generator %d = 0%o must be a K-bit mask with bit K - 1 and bit 0 set", j, h_gen[j]);
+        WF_REQUIRE(wf_tap_mask_ok(h_gen[j], K), "wf_turbo_code_create: parity generator %d = 0%o must be a K-bit mask with bit K - 1 and bit 0 set", j,
+                   h_gen[j]);
         WF_REQUIRE(h_gen[j] != fb, "wf_turbo_code_create: parity generator %d equals the feedback mask 0%o", j, fb);
     }
     WF_REQUIRE(k >= 1 && 2 * (int64_t)m * ((int64_t)k + nu) <= CONV_MAX_N, "wf_turbo_code_create: k = %d: N = 2 m (k + K - 1) outside 2 m K .. %d", k,
@@ -398,16 +389,12 @@ extern "C" int wf_turbo_code_create(wf_ctx *ctx, int32_t K, int32_t n_par, uint3
         blob[(size_t)k + p] = i;
     }
     int32_t *var_src = blob.data() + 2 * (size_t)k;
-    for (int t = 0; t < n_tx; ++t) {
-        const int v = h_tx_var[t];
-        WF_REQUIRE(v >= 0 && v < N, "wf_turbo_code_create: tx_var[%d] = %d outside the code", t, v);
-        WF_REQUIRE(var_src[v] < 0, "wf_turbo_code_create: variable %d is transmitted twice", v);
-        var_src[v] = t;
-        var_src[(size_t)N + t] = v;
-    }
+    WF_TRY(wf_tx_table("wf_turbo_code_create", h_tx_var, n_tx, N, var_src, var_src + N));
 
+    void *d_block;
+    WF_TRY(wf_code_upload("wf_turbo_code_create", ctx->device, blob.data(), blob.size() * sizeof(int32_t), &d_block));
     wf_turbo_code *c = new wf_turbo_code();
-    c->device = ctx->device;
+    c->device = ctx->device, c->d_block = d_block;
     c->K = K, c->nu = nu, c->n_par = n_par, c->m = m, c->k = k, c->T = T, c->N = N, c->n_tx = n_tx;
     c->gen[0] = fb;
     for (int j = 0; j < n_par; ++j) c->gen[1 + j] = h_gen[j];
@@ -425,16 +412,6 @@ extern "C" int wf_turbo_code_create(wf_ctx *ctx, int32_t K, int32_t n_par, uint3
         c->enc_pow[d] = A;
         A = turbo_matmul(A, A);
     }
-    auto fail = [c](hipError_t e, const char *what) {
-        wf_set_error("wf_turbo_code_create: %s failed: %s", what, hipGetErrorString(e));
-        if (c->d_block) (void)hipFree(c->d_block);
-        delete c;
-        return WF_ERR_HIP;
-    };
-    hipError_t e = hipSetDevice(ctx->device);
-    if (e != hipSuccess) return fail(e, "hipSetDevice");
-    if ((e = hipMalloc(&c->d_block, blob.size() * sizeof(int32_t))) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(c->d_block, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "hipMemcpy");
     c->d_perm = static_cast<const int32_t *>(c->d_block);
     c->d_inv = c->d_perm + k;
     c->d_var_src = c->d_inv + k;
@@ -446,21 +423,16 @@ extern "C" int wf_turbo_code_create(wf_ctx *ctx, int32_t K, int32_t n_par, uint3
 extern "C" int wf_turbo_code_free(wf_turbo_code *code)
 {
     if (!code) return WF_OK;
-    (void)hipSetDevice(code->device);
-    const hipError_t e = code->d_block ? hipFree(code->d_block) : hipSuccess;
+    const int rc = wf_code_release("wf_turbo_code_free", code->device, {code->d_block});
     delete code;                          // (whatever hipFree said: the host struct never outlives the call)
-    if (e != hipSuccess) {
-        wf_set_error("wf_turbo_code_free: hipFree failed: %s", hipGetErrorString(e));
-        return WF_ERR_HIP;
-    }
-    return WF_OK;
+    return rc;
 }
 
 extern "C" int wf_turbo_encode(wf_ctx *ctx, const wf_turbo_code *code, const uint8_t *d_info, int64_t ncw, uint8_t *d_tx, void *stream)
 {
     WF_REQUIRE(ctx && code && d_info && d_tx, "wf_turbo_encode: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_turbo_encode: ncw must be at least 1");
-    WF_REQUIRE(code->device == ctx->device, "wf_turbo_encode: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE_SAME_DEVICE("wf_turbo_encode", code, ctx);
     WF_HIP(hipSetDevice(ctx->device));
     turbo_enc_args a;
     a.info = d_info, a.out = d_tx, a.perm = code->d_perm, a.var_src = code->d_var_src, a.ncw = ncw;
@@ -499,21 +471,19 @@ extern "C" int wf_turbo_decode(wf_ctx *ctx, const wf_turbo_code *code, const dou
 {
     WF_REQUIRE(ctx && code && d_llr, "wf_turbo_decode: NULL argument");
     WF_REQUIRE(ncw >= 1, "wf_turbo_decode: ncw must be at least 1");
-    WF_REQUIRE(std::isfinite(scale) && scale > 0.0, "wf_turbo_decode: scale must be finite and positive");
-    WF_REQUIRE(std::isfinite(ext_scale) && ext_scale > 0.0f, "wf_turbo_decode: ext_scale must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(scale), "wf_turbo_decode: scale must be finite and positive");
+    WF_REQUIRE(wf_finite_pos(ext_scale), "wf_turbo_decode: ext_scale must be finite and positive");
     WF_REQUIRE(half_iters >= 1 && half_iters <= 64, "wf_turbo_decode: half_iters = %d outside 1 .. 64", half_iters);
     WF_REQUIRE(!d_ext || (half_iters % 2 == 0 && ext_stride >= code->n_tx && ext_clip > 0.0f),
                "wf_turbo_decode: d_ext needs an even half_iters, ext_stride >= n_tx and ext_clip > 0");
     WF_REQUIRE(!d_ref_info || d_counts, "wf_turbo_decode: d_ref_info needs d_counts");
-    WF_REQUIRE((reinterpret_cast<uintptr_t>(d_llr) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_counts) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_a1) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_info_post) & 3) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_ext) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_iters) & 3) == 0,
+    WF_REQUIRE(wf_aligned(d_llr, 8) && wf_aligned(d_counts, 8) && wf_aligned(d_a1, 4) && wf_aligned(d_info_post, 4) && wf_aligned(d_ext, 4) &&
+                   wf_aligned(d_iters, 4),
                "wf_turbo_decode: llr and counts must be 8-byte, a1, post, ext and iters 4-byte aligned");
-    WF_REQUIRE(code->device == ctx->device, "wf_turbo_decode: the code lives on device %d, the context on %d", code->device, ctx->device);
+    WF_REQUIRE_SAME_DEVICE("wf_turbo_decode", code, ctx);
     const turbo_geom g = turbo_geometry(ctx, code, ncw);
     WF_HIP(hipSetDevice(ctx->device));
-    const int rc = wf_ctx_reserve_vit(ctx, (g.scratch_bytes + 7) / 8);
-    if (rc) return rc;
+    WF_TRY(wf_ctx_reserve_vit(ctx, (g.scratch_bytes + 7) / 8));
     turbo_dec_args a;
     a.perm = code->d_perm, a.inv = code->d_inv, a.var_src = code->d_var_src;
     char *scratch = reinterpret_cast<char *>(ctx->d_vit_edge);
@@ -526,9 +496,8 @@ extern "C" int wf_turbo_decode(wf_ctx *ctx, const wf_turbo_code *code, const dou
     for (int j = 0; j < 4; ++j) a.gen[j] = code->gen[j];
     a.counts = reinterpret_cast<unsigned long long *>(d_counts);
     // launches of at most g.per_launch waves (the scratch is sized for that many)
-    const int64_t cws = g.per_launch * g.G;
-    for (int64_t b0 = 0; b0 < ncw; b0 += cws) {
-        a.ncw = std::min(cws, ncw - b0);
+    return wf_for_slices(ncw, g.per_launch * g.G, [&](int64_t b0, int64_t count) -> int {
+        a.ncw = count;
         a.llr = d_llr + b0 * code->n_tx;
         a.a1 = d_a1 ? d_a1 + b0 * code->k : s_a1;
         a.bits = d_info_bits ? d_info_bits + b0 * code->k : nullptr;
@@ -544,6 +513,6 @@ extern "C" int wf_turbo_decode(wf_ctx *ctx, const wf_turbo_code *code, const dou
         default: turbo_decode_launch<4>(code->n_par, grid, st, a); break;
         }
         WF_LAUNCH_CHECK();
-    }
-    return WF_OK;
+        return WF_OK;
+    });
 }

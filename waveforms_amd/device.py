@@ -16,6 +16,18 @@ from . import _hip
 _u64 = lambda v: ctypes.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)  # noqa: E731
 
 
+def _ctx(ctx):
+    """The caller's private wf_ctx, or the device's shared one."""
+    return ctx if ctx is not None else _hip.ctx()
+
+
+def _geometry(c_fn: str, names, *args) -> dict:
+    """The int64 words a ``wf_*_geometry`` entry point writes behind ``args``, by name."""
+    g = (ctypes.c_int64 * len(names))()
+    _hip.check(getattr(_hip.lib(), c_fn)(*args, g))
+    return dict(zip(names, (int(v) for v in g)))
+
+
 def lfsr_bits(degree: int, mask: int, state: int, n: int, skip: int = 0):
     """K1 -> (bits u8[n] on device, register state after skip+n steps)."""
     out = _hip.empty(max(n, 1) + 16, "uint8")
@@ -163,7 +175,7 @@ def viterbi_detect(mf_rows, differential: bool = True, warmup: int = 0, state=No
     ncalls = int(mf_rows.shape[0])
     bits = _hip.empty(ncalls + 16, "uint8")
     syms = _hip.empty(ncalls + 16, "int8")
-    _hip.check(_hip.lib().wf_viterbi4_detect(ctx if ctx is not None else _hip.ctx(), _hip.ptr(mf_rows), ncalls, int(bool(differential)),
+    _hip.check(_hip.lib().wf_viterbi4_detect(_ctx(ctx), _hip.ptr(mf_rows), ncalls, int(bool(differential)),
                                              warmup, _hip.ptr(bits), _hip.ptr(syms), _hip.ptr(state),
                                              _hip.stream()))
     return bits[:ncalls], syms[:ncalls]
@@ -175,7 +187,7 @@ def viterbi_detect_window(mf_rows, length: int, differential: bool = True, warmu
     ncalls = int(mf_rows.shape[0])
     bits = _hip.empty(ncalls + 16, "uint8")
     syms = _hip.empty(ncalls + 16, "int8")
-    _hip.check(_hip.lib().wf_viterbi4_detect_window(ctx if ctx is not None else _hip.ctx(), _hip.ptr(mf_rows), ncalls, int(length),
+    _hip.check(_hip.lib().wf_viterbi4_detect_window(_ctx(ctx), _hip.ptr(mf_rows), ncalls, int(length),
                                                     int(bool(differential)), warmup, _hip.ptr(bits), _hip.ptr(syms),
                                                     _hip.ptr(state), _hip.stream()))
     return bits[:ncalls], syms[:ncalls]
@@ -189,26 +201,17 @@ def viterbi_soft(rows, differential: bool = True, warmup: int = 0, row_bytes: in
     λ is in metric units: λ/σ² over-states the confidence of the PT and PAM metrics (see tools/soft_bench.py for the
     fitted scale).  The hard decisions are the ML sequence, not the length-2 detector's, and can have MORE bit errors
     than it.  Proof counters as for the hard detectors (viterbi_unmerged / viterbi_repaired)."""
-    if row_bytes not in (32, 48):
-        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
-    if not rows.is_contiguous():
-        raise ValueError("rows must be contiguous")
-    nbytes = rows.numel() * rows.element_size()
-    if nbytes % row_bytes:
-        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
-    ncalls = nbytes // row_bytes
+    ncalls = _rows(rows, row_bytes, allow_empty=True)
     llr = _hip.empty(max(ncalls, 1), "float64")
     bits = _hip.empty(ncalls + 16, "uint8")
-    _hip.check(_hip.lib().wf_viterbi4_soft(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(row_bytes),
+    _hip.check(_hip.lib().wf_viterbi4_soft(_ctx(ctx), _hip.ptr(rows), ncalls, int(row_bytes),
                                            int(bool(differential)), int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.stream()))
     return llr[:ncalls], bits[:ncalls]
 
 
 def viterbi_soft_geometry(ncalls: int, warmup: int = 0, ctx=None) -> dict:
     """What ``viterbi_soft`` launches for a burst of ``ncalls`` rows on this context (``wf_viterbi4_soft_geometry``)."""
-    g = (ctypes.c_int64 * 4)()
-    _hip.check(_hip.lib().wf_viterbi4_soft_geometry(ctx if ctx is not None else _hip.ctx(), int(ncalls), int(warmup), g))
-    return dict(zip(("chunk_calls", "lanes", "warmup", "scratch_bytes"), (int(v) for v in g)))
+    return _geometry("wf_viterbi4_soft_geometry", ("chunk_calls", "lanes", "warmup", "scratch_bytes"), _ctx(ctx), int(ncalls), int(warmup))
 
 
 def viterbi_soft_apriori(rows, apriori=None, apriori_scale: float = 1.0, differential: bool = True, warmup: int = 0,
@@ -218,23 +221,28 @@ def viterbi_soft_apriori(rows, apriori=None, apriori_scale: float = 1.0, differe
     ncalls values (row k's prior at [k]: transmitted bit j's at [j + 1]) or None (= ``viterbi_soft``, bitwise);
     π = ``apriori_scale`` * apriori > 0 favours bit 0.  ``ext`` leaves the prior of its own bit out (it is what an outer
     decoder is fed); ``bits`` are the decisions of ext + π.  Geometry: ``viterbi_soft_geometry``."""
-    if row_bytes not in (32, 48):
-        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
-    if not rows.is_contiguous():
-        raise ValueError("rows must be contiguous")
-    nbytes = rows.numel() * rows.element_size()
-    if nbytes % row_bytes:
-        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
-    ncalls = nbytes // row_bytes
+    ncalls = _rows(rows, row_bytes, allow_empty=True)
     if apriori is not None:
         if apriori.dtype != _hip.torch().float32 or not apriori.is_contiguous() or apriori.numel() != ncalls:
             raise ValueError(f"apriori must be {ncalls} contiguous float32 values (one per row)")
     ext = _hip.empty(max(ncalls, 1), "float64")
     bits = _hip.empty(ncalls + 16, "uint8")
-    _hip.check(_hip.lib().wf_viterbi4_soft_apriori(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(row_bytes),
+    _hip.check(_hip.lib().wf_viterbi4_soft_apriori(_ctx(ctx), _hip.ptr(rows), ncalls, int(row_bytes),
                                                    int(bool(differential)), int(warmup), _hip.ptr(apriori), float(apriori_scale),
                                                    _hip.ptr(ext), _hip.ptr(bits), _hip.stream()))
     return ext[:ncalls], bits[:ncalls]
+
+
+def _rows(rows, row_bytes: int, allow_empty: bool) -> int:
+    """The number of rows in a contiguous tensor of 32- or 48-byte detector rows."""
+    if row_bytes not in (32, 48):
+        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    nbytes = rows.numel() * rows.element_size()
+    if nbytes % row_bytes or (nbytes == 0 and not allow_empty):
+        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
+    return nbytes // row_bytes
 
 
 def _rows48(rows) -> int:
@@ -271,7 +279,7 @@ def viterbi_soft_branch(rows, differential: bool = True, warmup: int = 0, ctx=No
     llr = _hip.empty(ncalls, "float64")
     bits = _hip.empty(ncalls + 16, "uint8")
     branch = _hip.empty(ncalls + 16, "uint8")
-    _hip.check(_hip.lib().wf_viterbi4_soft_branch(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(bool(differential)), int(warmup),
+    _hip.check(_hip.lib().wf_viterbi4_soft_branch(_ctx(ctx), _hip.ptr(rows), ncalls, int(bool(differential)), int(warmup),
                                                   _hip.ptr(llr), _hip.ptr(bits), _hip.ptr(branch), _hip.stream()))
     return llr, bits[:ncalls], branch[:ncalls]
 
@@ -289,7 +297,7 @@ def carrier_stat(rows, branch, window: int, out=None, ctx=None):
         out = _hip.empty((nwin, 2), "float64")
     elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
         raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
-    _hip.check(_hip.lib().wf_carrier_stat(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), _hip.ptr(branch), ncalls, int(window), _hip.ptr(out),
+    _hip.check(_hip.lib().wf_carrier_stat(_ctx(ctx), _hip.ptr(rows), _hip.ptr(branch), ncalls, int(window), _hip.ptr(out),
                                           _hip.stream()))
     return out
 
@@ -302,7 +310,7 @@ def carrier_track(stat, span: int = 1, ctx=None):
     H, nwin = int(stat.shape[0]), int(stat.shape[1])
     phase = _hip.empty(max(nwin, 1), "float64")
     choice = _hip.empty(max(nwin, 1) + 16, "uint8")
-    _hip.check(_hip.lib().wf_carrier_track(ctx if ctx is not None else _hip.ctx(), _hip.ptr(stat), H, nwin, int(span), _hip.ptr(phase), _hip.ptr(choice),
+    _hip.check(_hip.lib().wf_carrier_track(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), _hip.ptr(phase), _hip.ptr(choice),
                                            _hip.stream()))
     return phase[:nwin], choice[:nwin]
 
@@ -322,7 +330,7 @@ def rows_derotate(rows, window: int = 64, phase=None, phase0: float = 0.0, out=N
         out = _hip.empty(tuple(rows.shape), "float64")
     elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows.numel():
         raise ValueError("out must be contiguous float64 of the rows' size")
-    _hip.check(_hip.lib().wf_rows_derotate(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(window), _hip.ptr(phase), nwin,
+    _hip.check(_hip.lib().wf_rows_derotate(_ctx(ctx), _hip.ptr(rows), ncalls, int(window), _hip.ptr(phase), nwin,
                                            float(phase0), _hip.ptr(out), _hip.stream()))
     return out
 
@@ -347,7 +355,7 @@ def idd_windows(state, nrows: int, n_tx: int, period: int | None = None, row_off
         out = _hip.empty(4 + 2 * ncw, "int64")
     elif out.dtype != torch.int64 or out.numel() < 4 + 2 * ncw or not out.is_contiguous():
         raise ValueError("out must hold 4 + 2 ncw contiguous int64")
-    _hip.check(_hip.lib().wf_idd_windows(ctx if ctx is not None else _hip.ctx(), _hip.ptr(state), ncw, int(nrows), int(n_tx), period,
+    _hip.check(_hip.lib().wf_idd_windows(_ctx(ctx), _hip.ptr(state), ncw, int(nrows), int(n_tx), period,
                                          int(row_offset), None if lock is None else _hip.ptr(_frame_lock(lock)), int(marker_bits), int(guard),
                                          _hip.ptr(out), _hip.stream()))
     return out
@@ -361,14 +369,7 @@ def viterbi_soft_apriori_windows(rows, apriori, windows, apriori_scale: float = 
     is bitwise ``viterbi_soft_apriori`` of the slice; rows outside every window are NOT written: pass ``out`` = (ext, bits) of
     an earlier pass to keep their values (fresh, uninitialised buffers otherwise)."""
     torch = _hip.torch()
-    if row_bytes not in (32, 48):
-        raise ValueError(f"row_bytes must be 32 or 48, not {row_bytes}")
-    if not rows.is_contiguous():
-        raise ValueError("rows must be contiguous")
-    nbytes = rows.numel() * rows.element_size()
-    if nbytes % row_bytes or nbytes == 0:
-        raise ValueError(f"{nbytes} bytes of rows are not a whole number of {row_bytes}-byte rows")
-    ncalls = nbytes // row_bytes
+    ncalls = _rows(rows, row_bytes, allow_empty=False)
     if apriori is None or apriori.dtype != torch.float32 or not apriori.is_contiguous() or apriori.numel() != ncalls:
         raise ValueError(f"apriori must be {ncalls} contiguous float32 values (one per row)")
     if windows.dtype != torch.int64 or not windows.is_contiguous() or windows.numel() < 6:
@@ -385,7 +386,7 @@ def viterbi_soft_apriori_windows(rows, apriori, windows, apriori_scale: float = 
             raise ValueError("out[0] must hold ncalls contiguous float64")
         if bits.dtype != torch.uint8 or not bits.is_contiguous() or bits.numel() < ncalls:
             raise ValueError("out[1] must hold ncalls contiguous bytes")
-    _hip.check(_hip.lib().wf_viterbi4_soft_apriori_windows(ctx if ctx is not None else _hip.ctx(), _hip.ptr(rows), ncalls, int(row_bytes),
+    _hip.check(_hip.lib().wf_viterbi4_soft_apriori_windows(_ctx(ctx), _hip.ptr(rows), ncalls, int(row_bytes),
                                                            int(bool(differential)), int(warmup), _hip.ptr(apriori), float(apriori_scale),
                                                            _hip.ptr(windows), max_windows, _hip.ptr(ext), _hip.ptr(bits), _hip.stream()))
     return ext[:ncalls], bits[:ncalls]
@@ -412,7 +413,7 @@ def cpm_soft(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=N
     llr = _hip.empty(max(n * lg, 1), "float64")
     bits = _hip.empty(n * lg + 16, "uint8")
     cfg = spec.c_config()
-    _hip.check(_hip.lib().wf_cpm_soft(ctx if ctx is not None else _hip.ctx(), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
+    _hip.check(_hip.lib().wf_cpm_soft(_ctx(ctx), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
                                       int(first_call), int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.stream()))
     return llr[:n * lg], bits[:n * lg]
 
@@ -442,7 +443,7 @@ def cpm_soft_apriori(rows, spec, apriori=None, apriori_scale: float = 1.0, first
     ext = _hip.empty(max(n * lg, 1), "float64")
     bits = _hip.empty(n * lg + 16, "uint8")
     cfg = spec.c_config()
-    _hip.check(_hip.lib().wf_cpm_soft_apriori(ctx if ctx is not None else _hip.ctx(), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
+    _hip.check(_hip.lib().wf_cpm_soft_apriori(_ctx(ctx), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
                                               int(first_call), int(warmup), _hip.ptr(apriori), float(apriori_scale), _hip.ptr(ext),
                                               _hip.ptr(bits), _hip.stream()))
     return ext[:n * lg], bits[:n * lg]
@@ -450,10 +451,7 @@ def cpm_soft_apriori(rows, spec, apriori=None, apriori_scale: float = 1.0, first
 
 def cpm_soft_geometry(spec, ncalls: int, warmup: int = 0, ctx=None) -> dict:
     """What ``cpm_soft`` launches for a burst of ``ncalls`` calls on this context (``wf_cpm_soft_geometry``)."""
-    g = (ctypes.c_int64 * 4)()
-    cfg = spec.c_config()
-    _hip.check(_hip.lib().wf_cpm_soft_geometry(ctx if ctx is not None else _hip.ctx(), ctypes.byref(cfg), int(ncalls), int(warmup), g))
-    return dict(zip(("chunk_calls", "chunks", "warmup", "scratch_bytes"), (int(v) for v in g)))
+    return _geometry("wf_cpm_soft_geometry", ("chunk_calls", "chunks", "warmup", "scratch_bytes"), _ctx(ctx), ctypes.byref(spec.c_config()), int(ncalls), int(warmup))
 
 
 def viterbi_unmerged(reset: bool = True, ctx=None) -> int:
@@ -462,7 +460,7 @@ def viterbi_unmerged(reset: bool = True, ctx=None) -> int:
     that miss their warm-up are repaired on the device (cascading into the following chunks where needed), is
     always the case unless the context's WF_OPT_DET_REPAIR option turned the repairs off."""
     n = ctypes.c_int64(0)
-    _hip.check(_hip.lib().wf_viterbi4_unmerged(ctx if ctx is not None else _hip.ctx(), ctypes.byref(n), int(reset), _hip.stream()))
+    _hip.check(_hip.lib().wf_viterbi4_unmerged(_ctx(ctx), ctypes.byref(n), int(reset), _hip.stream()))
     return int(n.value)
 
 
@@ -470,7 +468,7 @@ def viterbi_repaired(reset: bool = True, ctx=None) -> int:
     """Chunk repairs the detectors ran on the device since the last reset, every round counted
     (``wf_viterbi_repaired``; synchronises): chunks that missed their warm-up, run again from the true state."""
     n = ctypes.c_int64(0)
-    _hip.check(_hip.lib().wf_viterbi_repaired(ctx if ctx is not None else _hip.ctx(), ctypes.byref(n), int(reset), _hip.stream()))
+    _hip.check(_hip.lib().wf_viterbi_repaired(_ctx(ctx), ctypes.byref(n), int(reset), _hip.stream()))
     return int(n.value)
 
 
@@ -478,7 +476,7 @@ def viterbi_cascaded(reset: bool = True, ctx=None) -> int:
     """Of those repairs, the ones whose chunk ENDED in a different state than before and therefore handed on to
     the next chunk (``wf_viterbi_cascaded``; synchronises)."""
     n = ctypes.c_int64(0)
-    _hip.check(_hip.lib().wf_viterbi_cascaded(ctx if ctx is not None else _hip.ctx(), ctypes.byref(n), int(reset), _hip.stream()))
+    _hip.check(_hip.lib().wf_viterbi_cascaded(_ctx(ctx), ctypes.byref(n), int(reset), _hip.stream()))
     return int(n.value)
 
 
@@ -520,15 +518,51 @@ def cpm_count_errors(decided_u, ref_alpha, M: int, m: int, counts=None):
     return counts
 
 
-def ldpc_encode(code, d_info):
-    """LDPC encoder (``wf_ldpc_encode``): device messages (ncw x k bits, u8) -> transmitted bits (ncw x n_tx, u8) in
-    transmit order.  ``code``: a :class:`waveforms_amd.encoding.ldpc.LDPCCode`."""
+_WAVE_GEOMETRY = ("codewords_per_wave", "waves", "checkpoint_steps", "lds_bytes", "scratch_bytes")
+
+
+def _encode(c_fn: str, code, d_info):
+    """ncw x k message bits through a ``wf_*_encode`` entry point -> ncw x n_tx transmitted bits."""
     if not d_info.is_contiguous() or d_info.numel() % code.k or d_info.numel() == 0:
         raise ValueError(f"messages must be a contiguous whole number of k = {code.k} bits")
     ncw = d_info.numel() // code.k
     out = _hip.empty((ncw, code.n_tx), "uint8")
-    _hip.check(_hip.lib().wf_ldpc_encode(_hip.ctx(), code.handle(), _hip.ptr(d_info), ncw, _hip.ptr(out), _hip.stream()))
+    _hip.check(getattr(_hip.lib(), c_fn)(_hip.ctx(), code.handle(), _hip.ptr(d_info), ncw, _hip.ptr(out), _hip.stream()))
     return out
+
+
+def _codewords(code, d_llr) -> int:
+    """ncw of a decoder's input."""
+    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
+        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
+    return d_llr.numel() // code.n_tx
+
+
+def _ext_stride(code, ext_stride) -> int:
+    stride = code.n_tx if ext_stride is None else int(ext_stride)
+    if stride < code.n_tx:
+        raise ValueError(f"ext_stride {stride} is below n_tx = {code.n_tx}")
+    return stride
+
+
+def _ext_room(code, ext, stride: int, ncw: int) -> None:
+    if ext.dtype != _hip.torch().float32 or not ext.is_contiguous() or ext.numel() < (ncw - 1) * stride + code.n_tx:
+        raise ValueError("ext must be contiguous float32 with room for (ncw - 1) ext_stride + n_tx values")
+
+
+def _ref_counts(code, ref_info, counts, n: int, ncw: int):
+    """The counts a decoder adds to when it has a reference (``counts``, or fresh zeros int64[n]); None without one."""
+    if ref_info is None:
+        return None
+    if ref_info.numel() != ncw * code.k or not ref_info.is_contiguous():
+        raise ValueError("ref_info must hold ncw x k contiguous bits")
+    return _hip.zeros(n, "int64") if counts is None else counts
+
+
+def ldpc_encode(code, d_info):
+    """LDPC encoder (``wf_ldpc_encode``): device messages (ncw x k bits, u8) -> transmitted bits (ncw x n_tx, u8) in
+    transmit order.  ``code``: a :class:`waveforms_amd.encoding.ldpc.LDPCCode`."""
+    return _encode("wf_ldpc_encode", code, d_info)
 
 
 def ldpc_decode(code, d_llr, scale: float = 1.0, alpha: float = 0.75, max_iter: int = 50, ref_info=None, counts=None,
@@ -538,21 +572,14 @@ def ldpc_decode(code, d_llr, scale: float = 1.0, alpha: float = 0.75, max_iter: 
     {"info_bits": u8 ncw x k, "iters": int32 ncw, "post": float32 ncw x n or None, "counts": the int64[4] counts or None}.
     With ``ref_info`` (device ncw x k bits) the decoder ADDS to ``counts`` (fresh zeros if None): information bit errors,
     codewords with an information bit error, codewords not converged, iterations summed."""
-    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
-        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
-    ncw = d_llr.numel() // code.n_tx
+    ncw = _codewords(code, d_llr)
     info = _hip.empty((ncw, code.k), "uint8")
     iters = _hip.empty(ncw, "int32")
     post = _hip.torch().empty((ncw, code.n), dtype=_hip.torch().float32, device="cuda") if want_post else None
-    if ref_info is not None:
-        if ref_info.numel() != ncw * code.k or not ref_info.is_contiguous():
-            raise ValueError("ref_info must hold ncw x k contiguous bits")
-        if counts is None:
-            counts = _hip.zeros(4, "int64")
+    counts = _ref_counts(code, ref_info, counts, 4, ncw)
     _hip.check(_hip.lib().wf_ldpc_decode(_hip.ctx(), code.handle(), _hip.ptr(d_llr), ncw, float(scale), float(alpha), int(max_iter),
-                                         _hip.ptr(info), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ref_info),
-                                         _hip.ptr(counts) if ref_info is not None else None, _hip.stream()))
-    return {"info_bits": info, "iters": iters, "post": post, "counts": counts if ref_info is not None else None}
+                                         _hip.ptr(info), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ref_info), _hip.ptr(counts), _hip.stream()))
+    return {"info_bits": info, "iters": iters, "post": post, "counts": counts}
 
 
 def ldpc_decode_ext(code, d_llr, state, ext, ext_stride: int | None = None, scale: float = 1.0, alpha: float = 0.75, max_iter: int = 5,
@@ -565,16 +592,11 @@ def ldpc_decode_ext(code, d_llr, state, ext, ext_stride: int | None = None, scal
     (u8 ncw x k) and ``iters`` (int32 ncw, INCREASED) are updated in place for the open codewords; fresh zeros when None.
     Returns {"info_bits", "iters", "post" (float32 ncw x n, only open codewords written, or None), "state", "ext"}."""
     torch = _hip.torch()
-    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
-        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
-    ncw = d_llr.numel() // code.n_tx
-    stride = code.n_tx if ext_stride is None else int(ext_stride)
-    if stride < code.n_tx:
-        raise ValueError(f"ext_stride {stride} is below n_tx = {code.n_tx}")
+    ncw = _codewords(code, d_llr)
+    stride = _ext_stride(code, ext_stride)
     if state.dtype != torch.uint8 or state.numel() != ncw or not state.is_contiguous():
         raise ValueError("state must hold ncw contiguous bytes")
-    if ext.dtype != torch.float32 or not ext.is_contiguous() or ext.numel() < (ncw - 1) * stride + code.n_tx:
-        raise ValueError("ext must be contiguous float32 with room for (ncw - 1) ext_stride + n_tx values")
+    _ext_room(code, ext, stride, ncw)
     if info_bits is None:
         info_bits = _hip.zeros((ncw, code.k), "uint8")
     elif info_bits.dtype != torch.uint8 or info_bits.numel() != ncw * code.k or not info_bits.is_contiguous():
@@ -608,20 +630,14 @@ def ldpc_count(code, info_bits, ref_info, state, iters, counts=None):
 
 def ldpc_decode_geometry(code, ncw: int) -> dict:
     """What ``ldpc_decode`` launches for ``ncw`` codewords (``wf_ldpc_decode_geometry``)."""
-    g = (ctypes.c_int64 * 5)()
-    _hip.check(_hip.lib().wf_ldpc_decode_geometry(_hip.ctx(), code.handle(), int(ncw), g))
-    return dict(zip(("state_in_scratch", "codewords_per_workgroup", "workgroups", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
+    return _geometry("wf_ldpc_decode_geometry", ("state_in_scratch", "codewords_per_workgroup", "workgroups", "lds_bytes", "scratch_bytes"),
+                     _hip.ctx(), code.handle(), int(ncw))
 
 
 def conv_encode(code, d_info):
     """Convolutional encoder (``wf_conv_encode``): device messages (ncw x k bits, u8) -> transmitted bits (ncw x n_tx, u8) in
     transmit order.  ``code``: a :class:`waveforms_amd.encoding.conv.ConvCode`."""
-    if not d_info.is_contiguous() or d_info.numel() % code.k or d_info.numel() == 0:
-        raise ValueError(f"messages must be a contiguous whole number of k = {code.k} bits")
-    ncw = d_info.numel() // code.k
-    out = _hip.empty((ncw, code.n_tx), "uint8")
-    _hip.check(_hip.lib().wf_conv_encode(_hip.ctx(), code.handle(), _hip.ptr(d_info), ncw, _hip.ptr(out), _hip.stream()))
-    return out
+    return _encode("wf_conv_encode", code, d_info)
 
 
 def conv_siso(code, d_llr, scale: float = 1.0, prior=None, ext=None, ext_stride: int | None = None, ext_clip: float = float("inf"),
@@ -634,12 +650,8 @@ def conv_siso(code, d_llr, scale: float = 1.0, prior=None, ext=None, ext_stride:
     what was not asked for.  With ``ref_info`` (device ncw x k bits) the decoder ADDS to ``counts`` (int64[2], fresh zeros if
     None): information bit errors, codewords with any."""
     torch = _hip.torch()
-    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
-        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
-    ncw = d_llr.numel() // code.n_tx
-    stride = code.n_tx if ext_stride is None else int(ext_stride)
-    if stride < code.n_tx:
-        raise ValueError(f"ext_stride {stride} is below n_tx = {code.n_tx}")
+    ncw = _codewords(code, d_llr)
+    stride = _ext_stride(code, ext_stride)
     if not float(ext_clip) > 0.0:
         raise ValueError("ext_clip must be positive")
     if prior is not None and (prior.dtype != torch.float32 or not prior.is_contiguous() or prior.numel() != ncw * code.k):
@@ -647,37 +659,25 @@ def conv_siso(code, d_llr, scale: float = 1.0, prior=None, ext=None, ext_stride:
     if ext is None:
         if want_ext:
             ext = torch.zeros((ncw, stride), dtype=torch.float32, device="cuda")
-    elif ext.dtype != torch.float32 or not ext.is_contiguous() or ext.numel() < (ncw - 1) * stride + code.n_tx:
-        raise ValueError("ext must be contiguous float32 with room for (ncw - 1) ext_stride + n_tx values")
-    if ref_info is not None:
-        if ref_info.numel() != ncw * code.k or not ref_info.is_contiguous():
-            raise ValueError("ref_info must hold ncw x k contiguous bits")
-        if counts is None:
-            counts = _hip.zeros(2, "int64")
+    else:
+        _ext_room(code, ext, stride, ncw)
+    counts = _ref_counts(code, ref_info, counts, 2, ncw)
     bits = _hip.empty((ncw, code.k), "uint8") if want_bits else None
     post = torch.empty((ncw, code.k), dtype=torch.float32, device="cuda") if want_post else None
     _hip.check(_hip.lib().wf_conv_siso(_hip.ctx(), code.handle(), _hip.ptr(d_llr), ncw, float(scale), _hip.ptr(prior), _hip.ptr(bits),
-                                       _hip.ptr(post), _hip.ptr(ext), stride, float(ext_clip), _hip.ptr(ref_info),
-                                       _hip.ptr(counts) if ref_info is not None else None, _hip.stream()))
-    return {"info_bits": bits, "info_post": post, "ext": ext, "counts": counts if ref_info is not None else None}
+                                       _hip.ptr(post), _hip.ptr(ext), stride, float(ext_clip), _hip.ptr(ref_info), _hip.ptr(counts), _hip.stream()))
+    return {"info_bits": bits, "info_post": post, "ext": ext, "counts": counts}
 
 
 def conv_siso_geometry(code, ncw: int) -> dict:
     """What ``conv_siso`` launches for ``ncw`` codewords (``wf_conv_siso_geometry``)."""
-    g = (ctypes.c_int64 * 5)()
-    _hip.check(_hip.lib().wf_conv_siso_geometry(_hip.ctx(), code.handle(), int(ncw), g))
-    return dict(zip(("codewords_per_wave", "waves", "checkpoint_steps", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
+    return _geometry("wf_conv_siso_geometry", _WAVE_GEOMETRY, _hip.ctx(), code.handle(), int(ncw))
 
 
 def turbo_encode(code, d_info):
     """Turbo encoder (``wf_turbo_encode``): device messages (ncw x k bits, u8) -> transmitted bits (ncw x n_tx, u8) in transmit
     order.  ``code``: a :class:`waveforms_amd.encoding.turbo.TurboCode`."""
-    if not d_info.is_contiguous() or d_info.numel() % code.k or d_info.numel() == 0:
-        raise ValueError(f"messages must be a contiguous whole number of k = {code.k} bits")
-    ncw = d_info.numel() // code.k
-    out = _hip.empty((ncw, code.n_tx), "uint8")
-    _hip.check(_hip.lib().wf_turbo_encode(_hip.ctx(), code.handle(), _hip.ptr(d_info), ncw, _hip.ptr(out), _hip.stream()))
-    return out
+    return _encode("wf_turbo_encode", code, d_info)
 
 
 def turbo_decode(code, d_llr, half_iters: int = 12, scale: float = 1.0, ext_scale: float = 0.75, early_stop: bool = True, a1=None,
@@ -692,15 +692,11 @@ def turbo_decode(code, d_llr, half_iters: int = 12, scale: float = 1.0, ext_scal
     int32 ncw, "a1", "ext", "counts"}, None for what was not asked for.  With ``ref_info`` (device ncw x k bits) the decoder
     ADDS to ``counts`` (int64[3], fresh zeros if None): information bit errors, codewords with any, half-iterations run."""
     torch = _hip.torch()
-    if not d_llr.is_contiguous() or d_llr.numel() % code.n_tx or d_llr.numel() == 0:
-        raise ValueError(f"LLRs must be a contiguous whole number of n_tx = {code.n_tx} values")
-    ncw = d_llr.numel() // code.n_tx
+    ncw = _codewords(code, d_llr)
     half_iters = int(half_iters)
     if not 1 <= half_iters <= 64:
         raise ValueError("half_iters must be 1 .. 64")
-    stride = code.n_tx if ext_stride is None else int(ext_stride)
-    if stride < code.n_tx:
-        raise ValueError(f"ext_stride {stride} is below n_tx = {code.n_tx}")
+    stride = _ext_stride(code, ext_stride)
     if not float(ext_clip) > 0.0:
         raise ValueError("ext_clip must be positive")
     if (ext is not None or want_ext) and half_iters % 2:
@@ -712,28 +708,21 @@ def turbo_decode(code, d_llr, half_iters: int = 12, scale: float = 1.0, ext_scal
     if ext is None:
         if want_ext:
             ext = torch.zeros((ncw, stride), dtype=torch.float32, device="cuda")
-    elif ext.dtype != torch.float32 or not ext.is_contiguous() or ext.numel() < (ncw - 1) * stride + code.n_tx:
-        raise ValueError("ext must be contiguous float32 with room for (ncw - 1) ext_stride + n_tx values")
-    if ref_info is not None:
-        if ref_info.numel() != ncw * code.k or not ref_info.is_contiguous():
-            raise ValueError("ref_info must hold ncw x k contiguous bits")
-        if counts is None:
-            counts = _hip.zeros(3, "int64")
+    else:
+        _ext_room(code, ext, stride, ncw)
+    counts = _ref_counts(code, ref_info, counts, 3, ncw)
     bits = _hip.empty((ncw, code.k), "uint8") if want_bits else None
     post = torch.empty((ncw, code.k), dtype=torch.float32, device="cuda") if want_post else None
     iters = torch.empty(ncw, dtype=torch.int32, device="cuda") if want_iters else None
     _hip.check(_hip.lib().wf_turbo_decode(_hip.ctx(), code.handle(), _hip.ptr(d_llr), ncw, float(scale), float(ext_scale), half_iters,
                                           1 if early_stop else 0, _hip.ptr(a1), _hip.ptr(bits), _hip.ptr(post), _hip.ptr(iters), _hip.ptr(ext),
-                                          stride, float(ext_clip), _hip.ptr(ref_info), _hip.ptr(counts) if ref_info is not None else None,
-                                          _hip.stream()))
-    return {"info_bits": bits, "info_post": post, "iters": iters, "a1": a1, "ext": ext, "counts": counts if ref_info is not None else None}
+                                          stride, float(ext_clip), _hip.ptr(ref_info), _hip.ptr(counts), _hip.stream()))
+    return {"info_bits": bits, "info_post": post, "iters": iters, "a1": a1, "ext": ext, "counts": counts}
 
 
 def turbo_decode_geometry(code, ncw: int) -> dict:
     """What ``turbo_decode`` launches for ``ncw`` codewords (``wf_turbo_decode_geometry``)."""
-    g = (ctypes.c_int64 * 5)()
-    _hip.check(_hip.lib().wf_turbo_decode_geometry(_hip.ctx(), code.handle(), int(ncw), g))
-    return dict(zip(("codewords_per_wave", "waves", "checkpoint_steps", "lds_bytes", "scratch_bytes"), (int(v) for v in g)))
+    return _geometry("wf_turbo_decode_geometry", _WAVE_GEOMETRY, _hip.ctx(), code.handle(), int(ncw))
 
 
 def _rs_frames(code, x, per: int, bits: bool, what: str) -> int:
@@ -800,9 +789,8 @@ def rs_mark_erasures(code, post, f_max: int, below: float = float("inf")):
 
 def rs_decode_geometry(code, nframes: int) -> dict:
     """What ``rs_decode`` launches for ``nframes`` frames (``wf_rs_decode_geometry``)."""
-    g = (ctypes.c_int64 * 5)()
-    _hip.check(_hip.lib().wf_rs_decode_geometry(_hip.ctx(), code.handle(), int(nframes), g))
-    return dict(zip(("waves_per_workgroup", "workgroups", "launches", "lds_bytes", "threads_per_workgroup"), (int(v) for v in g)))
+    return _geometry("wf_rs_decode_geometry", ("waves_per_workgroup", "workgroups", "launches", "lds_bytes", "threads_per_workgroup"),
+                     _hip.ctx(), code.handle(), int(nframes))
 
 
 def _frame_pn(pn, n_tx: int):

@@ -15,9 +15,9 @@ No tables are needed: ``nasa_k3`` is the (7, 5) code, ``ccsds_k7`` the (171, 133
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
+
+from ._code import DeviceCode, transmit_table
 
 MAX_N = 32768
 
@@ -35,7 +35,7 @@ def qpp_order(N: int, f1: int, f2: int) -> np.ndarray:
     return out
 
 
-class ConvCode:
+class ConvCode(DeviceCode):
     """A terminated feed-forward convolutional code of rate 1 / n_out with its puncturing and transmit order.
 
     Attributes: ``k`` information bits, ``K`` constraint length, ``n_out`` outputs per step, ``T`` = k + K - 1 steps, ``n`` =
@@ -61,30 +61,15 @@ class ConvCode:
         self.n = self.n_out * self.T
         if self.n > MAX_N:
             raise ValueError(f"n = n_out (k + K - 1) = {self.n} exceeds {MAX_N}")
-        if puncture is None:
-            keep = np.arange(self.n, dtype=np.int64)
-        else:
+        sent = np.ones((self.T, self.n_out), dtype=bool)              # T x n_out, variable order
+        if puncture is not None:
             pat = np.asarray(puncture)
             if pat.ndim != 2 or pat.shape[0] != self.n_out or pat.shape[1] < 1 or not np.isin(pat, (0, 1)).all():
                 raise ValueError(f"puncture must be an n_out x P pattern of 0 / 1 (n_out = {self.n_out})")
-            i = np.arange(self.T)
-            sent = pat[:, i % pat.shape[1]].T.astype(bool)            # T x n_out, variable order
-            keep = np.flatnonzero(sent.reshape(-1)).astype(np.int64)
-            if keep.size == 0:
-                raise ValueError("the puncture pattern sends nothing")
-        if tx_order is None:
-            tx = keep
-        else:
-            order = np.asarray(tx_order, dtype=np.int64).ravel()
-            if order.size != keep.size or not np.array_equal(np.sort(order), np.arange(keep.size)):
-                raise ValueError(f"tx_order must be a permutation of the {keep.size} surviving variables' ranks")
-            tx = keep[order]
-        self.tx_var = np.ascontiguousarray(tx, dtype=np.int64)
-        self.n_tx = int(tx.size)
+            sent = pat[:, np.arange(self.T) % pat.shape[1]].T.astype(bool)
+        self.tx_var = transmit_table(sent, tx_order)
+        self.n_tx = int(self.tx_var.size)
         self.rate = self.k / self.n_tx
-        self._handle = None
-        self._handle_dev = None
-        self._lib = None
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -102,9 +87,7 @@ class ConvCode:
     # ------------------------------------------------------------------ host forms
     def codeword_host(self, info: np.ndarray) -> np.ndarray:
         """Codewords by VARIABLE (ncw x n, uint8) from messages (ncw x k): the host statement of the encoder."""
-        u = np.atleast_2d(np.asarray(info, dtype=np.uint8)) & 1
-        if u.shape[1] != self.k:
-            raise ValueError(f"messages must have k = {self.k} bits")
+        u = self._messages(info) & 1
         nu = self.K - 1
         pad = np.zeros((u.shape[0], self.T + nu), dtype=np.uint8)
         pad[:, nu:nu + self.k] = u                                    # pad[:, nu + i] = u_i, zeros in front and behind
@@ -115,50 +98,17 @@ class ConvCode:
                     c[:, :, j] ^= pad[:, nu - d:nu - d + self.T]
         return c.reshape(u.shape[0], self.n)
 
-    def encode_host(self, info: np.ndarray) -> np.ndarray:
-        """Host encoder: messages (ncw x k) -> transmitted bits (ncw x n_tx, uint8) in transmit order."""
-        return np.ascontiguousarray(self.codeword_host(info)[:, self.tx_var])
-
     def c_tables(self) -> dict:
         """The arguments of ``wf_conv_code_create``."""
         return dict(K=self.K, n_out=self.n_out, gen=np.array(self.generators, dtype=np.uint32), k=self.k, n_tx=self.n_tx,
                     tx_var=self.tx_var.astype(np.int32))
 
     # ------------------------------------------------------------------ device
-    def handle(self) -> int:
-        """The ``wf_conv_code *`` of this code on the current device (made on first use)."""
-        from .. import _hip
+    _free, _encode = "wf_conv_code_free", "conv_encode"
 
-        dev = _hip.require_device()
-        if self._handle is not None and self._handle_dev == dev:
-            return self._handle
-        if self._handle is not None:
-            raise RuntimeError(f"this code's tables live on device {self._handle_dev}, not {dev}")
+    def _create(self, lib, ctx, out) -> int:
         t = self.c_tables()
-        out = ctypes.c_void_p()
-        _hip.check(_hip.lib().wf_conv_code_create(_hip.ctx(), t["K"], t["n_out"], t["gen"].ctypes.data, t["k"], t["n_tx"],
-                                                  t["tx_var"].ctypes.data, ctypes.byref(out)))
-        self._handle, self._handle_dev, self._lib = out.value, dev, _hip.lib()
-        return self._handle
-
-    def __del__(self):
-        h, lib = getattr(self, "_handle", None), getattr(self, "_lib", None)
-        if h and lib is not None:
-            try:
-                lib.wf_conv_code_free(h)
-            except Exception:          # noqa: BLE001 - interpreter teardown
-                pass
-            self._handle = None
-
-    def encode(self, info: np.ndarray) -> np.ndarray:
-        """Messages (ncw x k, 0/1) -> transmitted bits (ncw x n_tx, uint8), encoded on the GPU."""
-        from .. import _hip
-        from .. import device as dev
-
-        u = np.ascontiguousarray(np.atleast_2d(np.asarray(info, dtype=np.uint8)))
-        if u.shape[1] != self.k:
-            raise ValueError(f"messages must have k = {self.k} bits")
-        return _hip.to_host(dev.conv_encode(self, _hip.to_device(u)))
+        return lib.wf_conv_code_create(ctx, t["K"], t["n_out"], t["gen"].ctypes.data, t["k"], t["n_tx"], t["tx_var"].ctypes.data, out)
 
     def siso(self, llr: np.ndarray, prior=None, scale: float = 1.0, ext_clip: float = float("inf")) -> dict:
         """λ (ncw x n_tx) and an optional information prior (ncw x k) -> {"info_bits", "info_post", "ext"} as host arrays,

@@ -22,10 +22,11 @@ circulant permutations (each M x M block a permutation that the tables give, not
 """
 from __future__ import annotations
 
-import ctypes
 import functools
 
 import numpy as np
+
+from ._code import DeviceCode
 
 MAX_N = 32768
 MAX_DEG = 32
@@ -165,7 +166,7 @@ def _systematic(H: np.ndarray, punctured: np.ndarray):
     return info, par, A
 
 
-class LDPCCode:
+class LDPCCode(DeviceCode):
     """A binary LDPC code with its decoder layering, transmit order and systematic encoder.
 
     Attributes: ``n`` variables, ``m`` checks, ``k`` information bits, ``n_tx`` transmitted bits, ``info_var`` (the k
@@ -214,9 +215,6 @@ class LDPCCode:
         self.info_var, self.parity_var, self.generator = _systematic(H, self.punctured)
         self.k = int(self.info_var.size)
         self.rate = self.k / self.n_tx
-        self._handle = None
-        self._handle_dev = None
-        self._lib = None
 
     # ------------------------------------------------------------------ construction
     @classmethod
@@ -310,9 +308,7 @@ class LDPCCode:
 
     def codeword_host(self, info: np.ndarray) -> np.ndarray:
         """Systematic codewords by VARIABLE (ncw x n, uint8) from messages (ncw x k): the host statement of the encoder."""
-        u = np.atleast_2d(np.asarray(info, dtype=np.uint8)) & 1
-        if u.shape[1] != self.k:
-            raise ValueError(f"messages must have k = {self.k} bits")
+        u = self._messages(info) & 1
         up = _pack_rows(u)
         A = self.generator
         c = np.zeros((u.shape[0], self.n), dtype=np.uint8)
@@ -328,31 +324,12 @@ class LDPCCode:
         return np.ascontiguousarray(self.codeword_host(info)[:, self.tx_order])
 
     # ------------------------------------------------------------------ device
-    def handle(self) -> int:
-        """The ``wf_ldpc_code *`` of this code on the current device (made on first use)."""
-        from .. import _hip
+    _free, _encode = "wf_ldpc_code_free", "ldpc_encode"
 
-        dev = _hip.require_device()
-        if self._handle is not None and self._handle_dev == dev:
-            return self._handle
-        if self._handle is not None:
-            raise RuntimeError(f"this code's tables live on device {self._handle_dev}, not {dev}")
+    def _create(self, lib, ctx, out) -> int:
         t = self.c_tables()
-        out = ctypes.c_void_p()
-        _hip.check(_hip.lib().wf_ldpc_code_create(
-            _hip.ctx(), t["n"], t["m"], t["check_ptr"].ctypes.data, t["edge_var"].ctypes.data, t["nlayers"], t["layer_ptr"].ctypes.data,
-            t["n_tx"], t["tx_var"].ctypes.data, t["k"], t["info_var"].ctypes.data, t["parity_gen"].ctypes.data, ctypes.byref(out)))
-        self._handle, self._handle_dev, self._lib = out.value, dev, _hip.lib()
-        return self._handle
-
-    def __del__(self):
-        h, lib = getattr(self, "_handle", None), getattr(self, "_lib", None)
-        if h and lib is not None:
-            try:
-                lib.wf_ldpc_code_free(h)
-            except Exception:          # noqa: BLE001 - interpreter teardown
-                pass
-            self._handle = None
+        return lib.wf_ldpc_code_create(ctx, t["n"], t["m"], t["check_ptr"].ctypes.data, t["edge_var"].ctypes.data, t["nlayers"], t["layer_ptr"].ctypes.data,
+                                       t["n_tx"], t["tx_var"].ctypes.data, t["k"], t["info_var"].ctypes.data, t["parity_gen"].ctypes.data, out)
 
     def encode_device(self, d_info):
         """Device messages (ncw x k or flat, u8) -> device transmitted bits (ncw x n_tx, u8)."""
@@ -365,15 +342,6 @@ class LDPCCode:
         from .. import device as dev
 
         return dev.ldpc_decode(self, d_llr, **kw)
-
-    def encode(self, info: np.ndarray) -> np.ndarray:
-        """Messages (ncw x k, 0/1) -> transmitted bits (ncw x n_tx, uint8), encoded on the GPU."""
-        from .. import _hip
-
-        u = np.ascontiguousarray(np.atleast_2d(np.asarray(info, dtype=np.uint8)))
-        if u.shape[1] != self.k:
-            raise ValueError(f"messages must have k = {self.k} bits")
-        return _hip.to_host(self.encode_device(_hip.to_device(u)))
 
     def decode(self, llr: np.ndarray, scale: float = 1.0, alpha: float = 0.75, max_iter: int = 50, want_post: bool = False) -> dict:
         """λ (ncw x n_tx) -> {"info_bits", "iters"[, "post"]} as host arrays, decoded on the GPU."""

@@ -19,10 +19,11 @@ the inner decoder's soft output.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
+
+from ._code import DeviceCode
 
 MAX_T, MAX_DEPTH = 16, 8
 
@@ -50,7 +51,7 @@ def from_bits(bits: np.ndarray) -> np.ndarray:
     return np.packbits(b.reshape(b.shape[:-1] + (b.shape[-1] // 8, 8)), axis=-1).reshape(b.shape[:-1] + (b.shape[-1] // 8,))
 
 
-class RSCode:
+class RSCode(DeviceCode):
     """RS(n, k) over GF(2^8), interleaved to ``depth``.
 
     Attributes: ``n``, ``k``, ``t``, ``prim``, ``fcr``, ``step``, ``depth``, ``rate`` = k / n, ``exp`` / ``log`` (the field's
@@ -89,7 +90,6 @@ class RSCode:
             root = self.beta_pow(self.fcr + i)
             g = np.concatenate(([0], g)) ^ np.concatenate((self.mul(g, root), [0]))
         self.gen = g
-        self._handle = self._handle_dev = self._lib = None
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -292,28 +292,10 @@ class RSCode:
         return out
 
     # ------------------------------------------------------------------ device
-    def handle(self) -> int:
-        """The ``wf_rs_code *`` of this code on the current device (made on first use)."""
-        from .. import _hip
+    _free = "wf_rs_code_free"
 
-        dev = _hip.require_device()
-        if self._handle is not None and self._handle_dev == dev:
-            return self._handle
-        if self._handle is not None:
-            raise RuntimeError(f"this code's tables live on device {self._handle_dev}, not {dev}")
-        out = ctypes.c_void_p()
-        _hip.check(_hip.lib().wf_rs_code_create(_hip.ctx(), self.prim, self.fcr, self.step, self.n, self.k, self.depth, ctypes.byref(out)))
-        self._handle, self._handle_dev, self._lib = out.value, dev, _hip.lib()
-        return self._handle
-
-    def __del__(self):
-        h, lib = getattr(self, "_handle", None), getattr(self, "_lib", None)
-        if h and lib is not None:
-            try:
-                lib.wf_rs_code_free(h)
-            except Exception:          # noqa: BLE001 - interpreter teardown
-                pass
-            self._handle = None
+    def _create(self, lib, ctx, out) -> int:
+        return lib.wf_rs_code_create(ctx, self.prim, self.fcr, self.step, self.n, self.k, self.depth, out)
 
     def encode(self, msg_frames: np.ndarray, bits: bool = False) -> np.ndarray:
         """Message frames (F x k I symbols, or 8 times as many bits) -> frames, encoded on the GPU."""

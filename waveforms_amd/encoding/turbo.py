@@ -19,10 +19,9 @@ polynomial a bijection is accepted; how good the code is depends on the pair).
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
+from ._code import DeviceCode, transmit_table
 from .conv import MAX_N, qpp_order
 
 
@@ -33,7 +32,7 @@ def _parity(x: np.ndarray) -> np.ndarray:
     return (x & 1).astype(np.uint8)
 
 
-class TurboCode:
+class TurboCode(DeviceCode):
     """A parallel concatenation of two identical terminated RSC codes with its interleaver, puncturing and transmit order.
 
     Attributes: ``k`` information bits, ``K`` constraint length, ``n_par`` parity outputs per constituent, ``T`` = k + K - 1
@@ -74,22 +73,9 @@ class TurboCode:
             if pat.ndim != 2 or pat.shape[0] != 2 * m or pat.shape[1] < 1 or not np.isin(pat, (0, 1)).all():
                 raise ValueError(f"puncture must be a 2 m x P pattern of 0 / 1 (2 m = {2 * m})")
             sent &= pat[:, np.arange(self.T) % pat.shape[1]].T.astype(bool)
-        keep = np.flatnonzero(sent.reshape(-1)).astype(np.int64)
-        if keep.size == 0:
-            raise ValueError("the puncture pattern sends nothing")
-        if tx_order is None:
-            tx = keep
-        else:
-            order = np.asarray(tx_order, dtype=np.int64).ravel()
-            if order.size != keep.size or not np.array_equal(np.sort(order), np.arange(keep.size)):
-                raise ValueError(f"tx_order must be a permutation of the {keep.size} surviving variables' ranks")
-            tx = keep[order]
-        self.tx_var = np.ascontiguousarray(tx, dtype=np.int64)
-        self.n_tx = int(tx.size)
+        self.tx_var = transmit_table(sent, tx_order)
+        self.n_tx = int(self.tx_var.size)
         self.rate = self.k / self.n_tx
-        self._handle = None
-        self._handle_dev = None
-        self._lib = None
 
     # ------------------------------------------------------------------ presets
     @classmethod
@@ -120,15 +106,9 @@ class TurboCode:
 
     def codeword_host(self, info: np.ndarray) -> np.ndarray:
         """Codewords by VARIABLE (ncw x n, uint8) from messages (ncw x k): the host statement of the encoder."""
-        u = np.atleast_2d(np.asarray(info, dtype=np.uint8)) & 1
-        if u.shape[1] != self.k:
-            raise ValueError(f"messages must have k = {self.k} bits")
+        u = self._messages(info) & 1
         c = np.concatenate([self._constituent_host(u), self._constituent_host(u[:, self.interleaver])], axis=2)
         return c.reshape(u.shape[0], self.n)
-
-    def encode_host(self, info: np.ndarray) -> np.ndarray:
-        """Host encoder: messages (ncw x k) -> transmitted bits (ncw x n_tx, uint8) in transmit order."""
-        return np.ascontiguousarray(self.codeword_host(info)[:, self.tx_var])
 
     def c_tables(self) -> dict:
         """The arguments of ``wf_turbo_code_create``."""
@@ -136,40 +116,12 @@ class TurboCode:
                     perm=self.interleaver.astype(np.int32), n_tx=self.n_tx, tx_var=self.tx_var.astype(np.int32))
 
     # ------------------------------------------------------------------ device
-    def handle(self) -> int:
-        """The ``wf_turbo_code *`` of this code on the current device (made on first use)."""
-        from .. import _hip
+    _free, _encode = "wf_turbo_code_free", "turbo_encode"
 
-        dev = _hip.require_device()
-        if self._handle is not None and self._handle_dev == dev:
-            return self._handle
-        if self._handle is not None:
-            raise RuntimeError(f"this code's tables live on device {self._handle_dev}, not {dev}")
+    def _create(self, lib, ctx, out) -> int:
         t = self.c_tables()
-        out = ctypes.c_void_p()
-        _hip.check(_hip.lib().wf_turbo_code_create(_hip.ctx(), t["K"], t["n_par"], t["fb"], t["gen"].ctypes.data, t["k"], t["perm"].ctypes.data,
-                                                   t["n_tx"], t["tx_var"].ctypes.data, ctypes.byref(out)))
-        self._handle, self._handle_dev, self._lib = out.value, dev, _hip.lib()
-        return self._handle
-
-    def __del__(self):
-        h, lib = getattr(self, "_handle", None), getattr(self, "_lib", None)
-        if h and lib is not None:
-            try:
-                lib.wf_turbo_code_free(h)
-            except Exception:          # noqa: BLE001 - interpreter teardown
-                pass
-            self._handle = None
-
-    def encode(self, info: np.ndarray) -> np.ndarray:
-        """Messages (ncw x k, 0/1) -> transmitted bits (ncw x n_tx, uint8), encoded on the GPU."""
-        from .. import _hip
-        from .. import device as dev
-
-        u = np.ascontiguousarray(np.atleast_2d(np.asarray(info, dtype=np.uint8)))
-        if u.shape[1] != self.k:
-            raise ValueError(f"messages must have k = {self.k} bits")
-        return _hip.to_host(dev.turbo_encode(self, _hip.to_device(u)))
+        return lib.wf_turbo_code_create(ctx, t["K"], t["n_par"], t["fb"], t["gen"].ctypes.data, t["k"], t["perm"].ctypes.data, t["n_tx"],
+                                        t["tx_var"].ctypes.data, out)
 
     def decode(self, llr: np.ndarray, half_iters: int = 12, scale: float = 1.0, ext_scale: float = 0.75, early_stop: bool = True, a1=None,
                want_ext: bool = False, ext_clip: float = float("inf")) -> dict:
