@@ -852,6 +852,42 @@ def test_gpu_detect_samples_carries_its_state(oracle, ctx_options):
 
 
 @pytest.mark.gpu
+def test_gpu_detect_samples_puts_its_carry_back_when_a_chunk_is_left_unproven(oracle, ctx_options):
+    """A ``detect_samples`` launch that leaves chunks unproven (repairs switched off, 4 calls of warm-up) raises and leaves the
+    detector where it was before the launch, as ``detect`` does: the same second half again with the repairs back on
+    completes the burst with the sequential detector's decisions.  ``samples_form`` after every launch: the fallback through
+    ``detect()`` must not be what passes this."""
+    from waveforms_amd import _hip
+    from waveforms_amd.viterbi.cpm import ARTM_16, CPMTrellisDetector, matched_filter_templates
+
+    pulse = oracle.freq_pulse_multih_irig(SPS)
+    sym, res = _noisy_rows(oracle, oracle.ARTM_16, pulse, 40_000, 3.0, 21)
+    geo = res["geometry"]
+    assert geo["start0"] == 0
+    T = matched_filter_templates(pulse, SPS, ARTM_16)
+    k0 = 20_000                                  # (even: the second half's calls take the template columns of their places in the burst)
+    tail = res["received"][SPS * k0:]
+    with ctx_options(WF_OPT_CPM_SAMPLES_MIN_CALLS=4096):
+        det = CPMTrellisDetector(ARTM_16)
+        first = det.detect_samples(res["received"], T, 0, SPS, k0)
+        assert det.samples_form
+        # (the detector's own context exists since its first launch, and a default reaches only the contexts made after it and
+        #  the device's shared ones: the option is set on that context as well)
+        _hip.set_default_option(_hip.WF_OPT_DET_REPAIR, 1)
+        _hip.set_option(det._ctx, _hip.WF_OPT_DET_REPAIR, 1)
+        try:
+            with pytest.raises(RuntimeError, match="unproven"):
+                det.detect_samples(tail, T, 0, SPS, geo["ncalls"] - k0, warmup=4)
+            assert det.samples_form
+        finally:
+            _hip.set_default_option(_hip.WF_OPT_DET_REPAIR, 0)
+            _hip.set_option(det._ctx, _hip.WF_OPT_DET_REPAIR, 0)
+        second = det.detect_samples(tail, T, 0, SPS, geo["ncalls"] - k0, warmup=4)
+        assert det.samples_form
+    assert np.array_equal(np.concatenate([first, second]), res["decisions"])
+
+
+@pytest.mark.gpu
 def test_gpu_samples_form_of_the_256_state_link_equals_rows_form(ctx_options):
     """The full ARTM trellis (256 states, 64 matched filters: a row is 1 KB per symbol) with fuse bit 7: the front end stores the
     noisy samples and every detector workgroup forms the filter outputs of a batch itself (quad form, the k-ascending chain of

@@ -107,11 +107,8 @@ def gpu_block_runner(plan: SweepPlan, streams: int | None = None, fuse: int | No
     lanes of sequential links (0.165 - 0.169 s; one pipelined lane 0.168 - 0.172), PCM/FM — since the lane detector and the
     3 dB floor of its operating-point warm-up — one pipelined lane (0.089 - 0.092 s; three sequential lanes 0.093 - 0.100;
     round 3, row-form detector: 0.107): profiles/r04_sweep_lanes.log."""
-    import ctypes
-
     from waveforms_amd import _hip, device as dev
-    from waveforms_amd.link import CPMLink, SOQPSKLink, sigma_for_ebn0
-    from waveforms_amd.viterbi.cpm import sigma_for_ebn0 as cpm_sigma
+    from waveforms_amd.link import CPMLink, SOQPSKLink
 
     torch = _hip.torch()
     cpm = plan.waveform != "soqpsk"
@@ -131,7 +128,6 @@ def gpu_block_runner(plan: SweepPlan, streams: int | None = None, fuse: int | No
         links = [CPMLink(plan.nsym, plan.sps, waveform=plan.waveform, spec=big, pn_degree=plan.pn_degree, private_ctx=n > 1,
                          warmup=plan.warmup, fuse=((42 if n == 1 and one_pipelined else 10) | (128 if plan.waveform == "multih" else 0)) if fuse is None else fuse)
                  for _ in range(n)]
-        run_fn = _hip.lib().wf_cpm_link_run
     else:
         # (several lanes: sequential links with fuse bit 4 — the link's one-launch PRBS + precoder kernel is few, long
         #  workgroups, the right trade for ONE block at a time; with three blocks in flight the generic kernels fill the
@@ -139,7 +135,6 @@ def gpu_block_runner(plan: SweepPlan, streams: int | None = None, fuse: int | No
         links = [SOQPSKLink(plan.nsym, plan.sps, detector=plan.detector, pn_degree=plan.pn_degree, private_ctx=n > 1, warmup=plan.warmup,
                             fuse=(31 if n > 1 else 47) if fuse is None else fuse)
                  for _ in range(n)]
-        run_fn = _hip.lib().wf_link_run
     lanes = [torch.cuda.Stream() for _ in range(n)] if n > 1 else [torch.cuda.current_stream()]
     npts = len(plan.ebn0_db)
     # Counters of a lane accumulate on the device.  Every launch of the chunk-parallel detectors proves on the device
@@ -160,20 +155,10 @@ def gpu_block_runner(plan: SweepPlan, streams: int | None = None, fuse: int | No
                     else soqpsk_warmup_param(operating_point_warmup("soqpsk", float(e))) for e in plan.ebn0_db]
 
     def launch(k: int, point: int, block: int, warmup: int) -> int:
-        link, c = links[k], links[k].cfg
-        c.sigma = (cpm_sigma(plan.ebn0_db[point], plan.sps, plan.bits_per_symbol) if cpm
-                   else sigma_for_ebn0(plan.ebn0_db[point], plan.sps))
-        c.seed = plan.seed
-        c.stream_id, c.skip, c.event_slot = plan.stream_id(point, block), plan.skip_bits(block), -1
-        keep, c.warmup = c.warmup, warmup
-        m = ctypes.c_int64(0)
-        try:
-            with torch.cuda.stream(lanes[k]):
-                _hip.check(run_fn(link._ctx, ctypes.byref(c), link.workspace.data_ptr(), link.workspace_bytes,
-                                  tables[k].data_ptr() + 16 * point, ctypes.byref(m), _hip.stream()))
-        finally:
-            c.warmup = keep
-        return m.value
+        """One block of the link's own (``launch``), counted into this point's row of the lane's table."""
+        with torch.cuda.stream(lanes[k]):
+            return links[k].launch(tables[k].data_ptr() + 16 * point, plan.ebn0_db[point], plan.seed, plan.stream_id(point, block),
+                                   plan.skip_bits(block), warmup=warmup)
 
     def run(point: int, block: int) -> None:
         k = issued[0] % n
@@ -184,10 +169,7 @@ def gpu_block_runner(plan: SweepPlan, streams: int | None = None, fuse: int | No
         out = np.zeros((npts, 3), dtype=np.int64)
         for k in range(n):
             with torch.cuda.stream(lanes[k]):
-                _hip.check(_hip.lib().wf_ctx_check(links[k]._ctx, _hip.stream()))
-                unproven = dev.viterbi_unmerged(reset=True, ctx=links[k]._ctx)
-                if unproven:
-                    raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+                dev.require_proven(links[k]._ctx, check=True)
                 stats["repaired_chunks"] += dev.viterbi_repaired(reset=True, ctx=links[k]._ctx)
                 stats["cascaded_chunks"] += dev.viterbi_cascaded(reset=True, ctx=links[k]._ctx)
                 out[:, :2] += tables[k].cpu().numpy()

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "wf_cpm_detect.h"
+#include "wf_link.h"
 
 #define CPM_THREADS 256
 #define CPM_WAVES (CPM_THREADS / WF_WAVE)
@@ -1171,8 +1172,6 @@ struct cpm_link_layout {
     size_t off_bits, off_syms, off_sig, off_rows, off_dec, total;
 };
 
-static inline int64_t cpm_round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 static bool cpm_make_layout(const wf_cpm_link_config *cfg, cpm_link_layout &L)
 {
     if (!cfg || cfg->nsym < 1 || cfg->sps < 2 || cfg->sps > 256 || cfg->ntaps < 1) return false;
@@ -1197,11 +1196,11 @@ static bool cpm_make_layout(const wf_cpm_link_config *cfg, cpm_link_layout &L)
     L.nfilt = 1;
     for (int i = 0; i < d.Lp; ++i) L.nfilt *= d.M;
     size_t o_ = 0;
-    L.off_bits = o_; o_ += (size_t)cpm_round_up(L.nbits + 16, 256);
-    L.off_syms = o_; o_ += (size_t)cpm_round_up(L.nsym + 16, 256);
-    L.off_sig = o_;  o_ += (size_t)cpm_round_up(L.npts * 16, 256);
-    L.off_rows = o_; o_ += (size_t)cpm_round_up(L.ncalls * L.nfilt * 16, 256);
-    L.off_dec = o_;  o_ += (size_t)cpm_round_up(L.ncalls + 16, 256);
+    L.off_bits = o_; o_ += (size_t)round_up(L.nbits + 16, 256);
+    L.off_syms = o_; o_ += (size_t)round_up(L.nsym + 16, 256);
+    L.off_sig = o_;  o_ += (size_t)round_up(L.npts * 16, 256);
+    L.off_rows = o_; o_ += (size_t)round_up(L.ncalls * L.nfilt * 16, 256);
+    L.off_dec = o_;  o_ += (size_t)round_up(L.ncalls + 16, 256);
     L.total = o_;
     return true;
 }
@@ -1210,7 +1209,7 @@ extern "C" int64_t wf_cpm_link_workspace_bytes(const wf_cpm_link_config *cfg)
 {
     cpm_link_layout L;
     if (!cpm_make_layout(cfg, L)) return -1;
-    const int64_t one = ((int64_t)L.total + 255) / 256 * 256;
+    const int64_t one = round_up((int64_t)L.total, 256);
     return (cfg->fuse & 32) ? 2 * one : (int64_t)L.total;      // fuse bit 5: two sets of intermediates (see wf_cpm_link_run)
 }
 
@@ -1281,61 +1280,35 @@ extern "C" int wf_cpm_link_run(wf_ctx *ctx, const wf_cpm_link_config *cfg, void 
     //  the quad detector — 8 workgroups per CU, LDS-bound — slows it by more than it hides: 11.67 ms per block against 13.49 pipelined,
     //  profiles/r06_bench_multih256_forms.log)
     const bool piped = (cfg->fuse & 32) != 0 && L.ncalls > 0 && !cpm_link_samples_form_quad(cfg, L);
+    int rc;
     if (piped) {
-        const int64_t set_bytes = ((int64_t)L.total + 255) / 256 * 256;
-        WF_REQUIRE(2 * set_bytes <= workspace_bytes, "wf_cpm_link_run: fuse bit 5 needs two sets of intermediates (%lld bytes)", (long long)(2 * set_bytes));
-        WF_HIP(hipSetDevice(ctx->device));
-#ifndef WF_CPM_PIPE_PRIO
-#define WF_CPM_PIPE_PRIO 0      // (A/B aid: priority of the side streams, 0 = default; -1 = high: profiles/r06_ab_side_stream_priority.log)
-#endif
-        if (!ctx->pipe_stream) {
-            hipStream_t ps;
-            WF_HIP(hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, WF_CPM_PIPE_PRIO));
-            ctx->pipe_stream = ps;
-            WF_HIP(hipEventCreateWithFlags(&ctx->pipe_front, hipEventDisableTiming));
-            for (int k = 0; k < 2; ++k) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_done[k], hipEventDisableTiming));
-        }
-        if (!ctx->pipe_stream2) {
-            hipStream_t ps;
-            WF_HIP(hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, WF_CPM_PIPE_PRIO));
-            ctx->pipe_stream2 = ps;
-        }
-        w += (int64_t)ctx->pipe_set * set_bytes;
-        if (ctx->pipe_done_valid[ctx->pipe_set]) WF_HIP(hipStreamWaitEvent(wf_stream(stream), ctx->pipe_done[ctx->pipe_set], 0));
-    } else {
-        const int rj = wf_link_join_internal(ctx, stream);
-        if (rj) return rj;
+        // (side streams of the default priority: a high one was measured and not kept, profiles/r06_ab_side_stream_priority.log)
+        const int64_t set_bytes = round_up((int64_t)L.total, 256);
+        if ((rc = link_pipe_open(ctx, "wf_cpm_link_run", set_bytes, workspace_bytes, true)) || (rc = link_pipe_select(ctx, set_bytes, w, stream))) return rc;
+    } else if ((rc = wf_link_join_internal(ctx, stream))) {
+        return rc;
     }
     uint8_t *bits = reinterpret_cast<uint8_t *>(w + L.off_bits);
     int8_t *syms = reinterpret_cast<int8_t *>(w + L.off_syms);
     double *sig = reinterpret_cast<double *>(w + L.off_sig);
     double *rows = reinterpret_cast<double *>(w + L.off_rows);
     uint8_t *dec = reinterpret_cast<uint8_t *>(w + L.off_dec);
-    hipEvent_t *ev = nullptr;
-    if (cfg->event_slot >= 0) {
-        WF_REQUIRE(cfg->event_slot < WF_LINK_EVENT_SLOTS, "wf_cpm_link_run: event_slot %d", cfg->event_slot);
-        if (!ctx->events) {
-            ctx->events = new hipEvent_t[WF_LINK_EVENT_SLOTS * (WF_LINK_STAGES + 1)];
-            for (int k = 0; k < WF_LINK_EVENT_SLOTS * (WF_LINK_STAGES + 1); ++k) WF_HIP(hipEventCreate(&ctx->events[k]));
-        }
-        ev = ctx->events + cfg->event_slot * (WF_LINK_STAGES + 1);
-    }
-#define MARK(k) do { if (ev) WF_HIP(hipEventRecord(ev[k], wf_stream(stream))); } while (0)
-    int rc;
-    MARK(0);
+    hipEvent_t *ev;
+    if ((rc = link_stage_events(ctx, "wf_cpm_link_run", cfg->event_slot, ev))) return rc;
+    if ((rc = mark(ev, 0, stream))) return rc;
     // PRBS and mapper in one launch (the mappers are memoryless: the PRBS kernel applies them to the bits it holds in LDS);
     // fuse bit 4 (16), as in wf_link_config: the two generic kernels instead (same bits and symbols)
     rc = (cfg->fuse & 16) ? 1 : wf_lfsr_generate_map(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, bits, L.nbits, cfg->mapper_kind, syms, stream);
     if (rc < 0) return rc;
     if (rc == 1) {
         if ((rc = wf_lfsr_generate(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, bits, L.nbits, nullptr, stream))) return rc;
-        MARK(1);
+        if ((rc = mark(ev, 1, stream))) return rc;
         // MultiHSymbolMapper on an even number of bits leaves its parity at 0 (precoder.py:22)
         if ((rc = wf_symbol_map(ctx, cfg->mapper_kind, bits, L.nbits, 0, 0, 0, syms, stream))) return rc;
     } else {
-        MARK(1);
+        if ((rc = mark(ev, 1, stream))) return rc;
     }
-    MARK(2);
+    if ((rc = mark(ev, 2, stream))) return rc;
     // fuse bit 3 (with bit 1): modulator + channel + matched-filter rows in one kernel
     // (mod_chan_bank_kernel, wf_modulate.hip) — the baseband samples never reach HBM
     bool fused_all = false, samples_form = false;
@@ -1364,17 +1337,16 @@ extern "C" int wf_cpm_link_run(wf_ctx *ctx, const wf_cpm_link_config *cfg, void 
         WF_REQUIRE(rc == 0, "wf_cpm_link_run: burst / pulse outside the fused modulator (%lld symbols, %d taps)",
                    (long long)cfg->nsym, cfg->ntaps);
     }
-    MARK(3);
-    MARK(4);
+    if ((rc = mark(ev, 3, stream)) || (rc = mark(ev, 4, stream))) return rc;
     if (fused_all) {
-        MARK(5);
+        if ((rc = mark(ev, 5, stream))) return rc;
     } else if (cfg->fuse & 2) {     // channel inside the matched-filter kernel: the noisy samples never exist in HBM
-        MARK(5);
+        if ((rc = mark(ev, 5, stream))) return rc;
         if ((rc = wf_cpm_awgn_mf_rows_c128(ctx, sig, L.npts, cos(-M_PI / 4), sin(-M_PI / 4), cfg->sigma, cfg->seed, cfg->stream_id, 0,
                                            cfg->d_templates, cfg->det.nh, L.nfilt, L.ntm, L.start0, cfg->sps, L.ncalls, rows, stream))) return rc;
     } else {
         if ((rc = wf_awgn_c128(ctx, sig, L.npts, cos(-M_PI / 4), sin(-M_PI / 4), cfg->sigma, cfg->seed, cfg->stream_id, 0, sig, stream))) return rc;
-        MARK(5);
+        if ((rc = mark(ev, 5, stream))) return rc;
         if ((rc = wf_cpm_mf_rows_c128(ctx, sig, L.npts, cfg->d_templates, cfg->det.nh, L.nfilt, L.ntm, L.start0, cfg->sps, L.ncalls,
                                       rows, stream))) return rc;
     }
@@ -1390,8 +1362,7 @@ extern "C" int wf_cpm_link_run(wf_ctx *ctx, const wf_cpm_link_config *cfg, void 
         WF_HIP(hipEventRecord(ctx->pipe_front, wf_stream(stream)));
         WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_front, 0));
     }
-#define MARKB(k) do { if (ev) WF_HIP(hipEventRecord(ev[k], wf_stream(back))); } while (0)
-    MARKB(6);
+    if ((rc = mark(ev, 6, back))) return rc;
     // (rows sit inside the block's set of intermediates: what lies before them — symbols, the sample region — and behind
     //  them — the decisions, up to the end of the set — may be read by the lane form's row fetch, so no wave of it clamps)
     if (samples_form && samples_quad) {
@@ -1406,21 +1377,15 @@ extern "C" int wf_cpm_link_run(wf_ctx *ctx, const wf_cpm_link_config *cfg, void 
     } else if ((rc = wf_cpm_viterbi_detect_in(ctx, &cfg->det, cfg->d_rot_cs, rows, L.ncalls, cfg->warmup, dec, nullptr, back, (int64_t)L.off_rows,
                                               (int64_t)(L.total - L.off_rows) - L.ncalls * L.nfilt * 16, piped, nullptr, edge_slot)))
         return rc;
-    MARKB(7);
+    if ((rc = mark(ev, 7, back))) return rc;
     // decision of call k is symbol k - D + 1; symbols [skip_head, ncalls - D] are compared
     const int64_t skip = cfg->skip_head > 0 ? cfg->skip_head : 0;
     int64_t m = L.ncalls - cfg->det.D + 1 - skip;
     if (m < 0) m = 0;
     if (m > 0)
         if ((rc = wf_cpm_count_errors(ctx, dec + skip + cfg->det.D - 1, syms + skip, cfg->det.M, m, d_counts, back))) return rc;
-    MARKB(8);
-#undef MARKB
-    if (piped) {
-        WF_HIP(hipEventRecord(ctx->pipe_done[ctx->pipe_set], wf_stream(back)));
-        ctx->pipe_done_valid[ctx->pipe_set] = true;
-        ctx->pipe_set ^= 1;
-    }
-#undef MARK
+    if ((rc = mark(ev, 8, back))) return rc;
+    if (piped && (rc = link_pipe_close(ctx, back))) return rc;
     if (h_compared) *h_compared = m;
     return WF_OK;
 }
@@ -1435,9 +1400,8 @@ extern "C" int wf_cpm_link_run(wf_ctx *ctx, const wf_cpm_link_config *cfg, void 
 // indices, decision registers) and the 62-bit fixed-point phase carry of the next chunk's first tile.
 // Decisions and counts equal the one-shot wf_cpm_link_run over the whole stream, bit for bit.  Runs the
 // one-kernel front end (fuse bits 1 + 3; sps 8, 4 or 16 filters): other configurations are refused.
-struct cpm_stream_layout {
+struct cpm_stream_layout : link_chunk_window {
     int64_t N, B, tile_len, spt, ntiles_total, halo, ncalls_total, m_total;
-    int64_t k_lo, ncols, ws, nloc, tile_lo, ntiles, q_out_tile;
     size_t off_bits, off_syms, off_rows, off_dec, total;
     cpm_link_layout L;
     bool ok;
@@ -1450,7 +1414,7 @@ static cpm_stream_layout cpm_make_stream_layout(const wf_cpm_link_config *cfg, i
     S.N = cfg->nsym; S.B = B;
     S.ok = wf_mod_tile_geometry(cfg->sps, cfg->ntaps, cfg->nsym, &S.tile_len, &S.spt, &S.ntiles_total) == 0;
     if (!S.ok || S.spt <= 0) { S.ok = false; return S; }
-    S.halo = cpm_round_up(S.spt + 48 + cfg->det.D, 16);
+    S.halo = round_up(S.spt + 48 + cfg->det.D, 16);
     S.ncalls_total = S.L.ncalls;
     const int64_t skip = cfg->skip_head > 0 ? cfg->skip_head : 0;
     S.m_total = S.ncalls_total - cfg->det.D + 1 - skip;
@@ -1458,24 +1422,13 @@ static cpm_stream_layout cpm_make_stream_layout(const wf_cpm_link_config *cfg, i
     S.ok = B % S.spt == 0 && B % 128 == 0 && B >= 4 * S.halo &&
            ((cfg->fuse & 8) && (cfg->fuse & 2) &&
             wf_mod_chan_cpm_rows_applies(cfg->nsym, cfg->det.nh, cfg->ntaps, cfg->sps, S.L.nfilt, S.L.ntm, S.L.start0));
-    S.k_lo = c * B;
-    const int64_t k_hi = S.k_lo + B < S.ncalls_total ? S.k_lo + B : S.ncalls_total;
-    S.ncols = k_hi > S.k_lo ? k_hi - S.k_lo : 0;
-    S.ws = c * B - S.halo > 0 ? c * B - S.halo : 0;
-    const int64_t we = (c + 1) * B + S.halo < S.N ? (c + 1) * B + S.halo : S.N;
-    S.nloc = we > S.ws ? we - S.ws : 0;
-    S.tile_lo = c * B / S.spt - 1 > 0 ? c * B / S.spt - 1 : 0;          // the tile before the chunk too: its last column is the chunk's first
-    int64_t tile_hi = (c + 1) * B / S.spt + 1;
-    if (tile_hi > S.ntiles_total) tile_hi = S.ntiles_total;
-    S.ntiles = tile_hi > S.tile_lo ? tile_hi - S.tile_lo : 0;
-    const int64_t next_tile_lo = (c + 1) * B / S.spt - 1;
-    S.q_out_tile = (next_tile_lo >= S.tile_lo && next_tile_lo < tile_hi) ? next_tile_lo - S.tile_lo : -1;
+    static_cast<link_chunk_window &>(S) = link_chunk_window_of(B, c, S.halo, S.N, S.ncalls_total, S.spt, S.ntiles_total);
     size_t o = 0;
     const int64_t win = B + 2 * S.halo + 32;
-    S.off_bits = o; o += (size_t)cpm_round_up(win * S.L.bps, 256);
-    S.off_syms = o; o += (size_t)cpm_round_up(win, 256);
-    S.off_rows = o; o += (size_t)cpm_round_up(B * S.L.nfilt * 16, 256);
-    S.off_dec = o;  o += (size_t)cpm_round_up(B + 16, 256);
+    S.off_bits = o; o += (size_t)round_up(win * S.L.bps, 256);
+    S.off_syms = o; o += (size_t)round_up(win, 256);
+    S.off_rows = o; o += (size_t)round_up(B * S.L.nfilt * 16, 256);
+    S.off_dec = o;  o += (size_t)round_up(B + 16, 256);
     S.total = o;
     return S;
 }

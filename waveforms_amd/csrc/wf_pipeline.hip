@@ -6,7 +6,7 @@
 // kernels of this library on one stream; nothing is allocated and nothing comes back to
 // the host except the caller's own counters, so the call is graph-capturable and one
 // "Monte-Carlo trial block" of the BER sweep / one bench step.
-#include "wf_common.h"
+#include "wf_link.h"
 
 // ---------------------------------------------------------------- time axis (a5)
 // np.linspace(0, N+1, (N+1)*sps, endpoint=False) (reference waveforms/cpm/modulate.py:81-88)
@@ -31,8 +31,6 @@ extern "C" int wf_time_axis_f64(wf_ctx *ctx, int64_t n, double step, double *d_o
 }
 
 // ---------------------------------------------------------------- link
-static inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 struct link_layout {
     int64_t nsym, npts, ncols, first;
     size_t off_bits, off_syms, off_freq, off_sig, off_mf, off_dbits, off_dsyms, total;
@@ -169,19 +167,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
     const bool piped = link_pipelined(cfg) && L.ncols > 0;
     void *s_pro = stream, *s_main = stream;       // where the prologue / the front-end kernel go (a pipelined link: library streams)
     bool ahead = false;
-    int slot = -1;
+    int slot = -1, rc;
     if (piped) {
         const int64_t set_bytes = round_up((int64_t)L.total, 256);
-        WF_REQUIRE(2 * set_bytes <= workspace_bytes, "wf_link_run: fuse bit 5 needs two sets of intermediates (%lld bytes)", (long long)(2 * set_bytes));
-        WF_HIP(hipSetDevice(ctx->device));
-        if (!ctx->pipe_stream) {
-            hipStream_t ps;
-            WF_HIP(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
-            ctx->pipe_stream = ps;
-            WF_HIP(hipEventCreateWithFlags(&ctx->pipe_front, hipEventDisableTiming));
-            for (int k = 0; k < 2; ++k) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_done[k], hipEventDisableTiming));
-        }
-        w += (int64_t)ctx->pipe_set * set_bytes;
+        if ((rc = link_pipe_open(ctx, "wf_link_run", set_bytes, workspace_bytes, false))) return rc;
         // Round 6: three library streams per pipelined link.  A block's PROLOGUE (PRBS + precoder, tile sums, tile scan: ~60 us of
         // small kernels that used to sit between two front ends on the caller's stream) goes to pipe_pro and depends only on its
         // set of intermediates being free — the host queues block k + 1 while block k's front end runs, so it runs BESIDE that front
@@ -211,14 +200,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
                 WF_HIP(hipEventRecord(ctx->pipe_call, wf_stream(stream)));
                 WF_HIP(hipStreamWaitEvent(wf_stream(s_pro), ctx->pipe_call, 0));
             }
-            if (ctx->pipe_done_valid[ctx->pipe_set]) WF_HIP(hipStreamWaitEvent(wf_stream(s_pro), ctx->pipe_done[ctx->pipe_set], 0));
-        } else if (ctx->pipe_done_valid[ctx->pipe_set]) {
-            // the set was last used two blocks ago: that block's detector and counter must be done with it
-            WF_HIP(hipStreamWaitEvent(wf_stream(stream), ctx->pipe_done[ctx->pipe_set], 0));
         }
-    } else {
-        const int rj = wf_link_join_internal(ctx, stream);      // (a context that ran pipelined blocks before: ordinary stream order from here on)
-        if (rj) return rj;
+        if ((rc = link_pipe_select(ctx, set_bytes, w, s_pro))) return rc;     // (s_pro: the caller's stream unless the prologue runs ahead)
+    } else if ((rc = wf_link_join_internal(ctx, stream))) {     // (a context that ran pipelined blocks before: ordinary stream order from here on)
+        return rc;
     }
     uint8_t *bits = reinterpret_cast<uint8_t *>(w + L.off_bits);
     int8_t *syms = reinterpret_cast<int8_t *>(w + L.off_syms);
@@ -228,43 +213,20 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
     uint8_t *dbits = reinterpret_cast<uint8_t *>(w + L.off_dbits);
     int8_t *dsyms = reinterpret_cast<int8_t *>(w + L.off_dsyms);
 
-    // SOQPSKTrellis4x2 / 4x2DiffEncoded as dense [column][state][input] tables
-    // (reference waveforms/cpm/trellis/model.py:205-258).
-    uint8_t next[2][4][2];
-    int8_t outp[2][4][2];
-    static const int8_t kOut[2][8] = {{0, 2, 0, -2, -2, 0, 2, 0}, {0, -2, 2, 0, 0, 2, -2, 0}};
-    for (int c = 0; c < 2; ++c)
-        for (int b = 0; b < 8; ++b) {
-            const int s = b >> 1;
-            const int e = c == 0 ? (s & 1) + 2 * (b & 1) : (s & 2) + (b & 1);
-            const int flip = cfg->differential ? (c == 0 ? (s >> 1) : (s & 1)) : 0;
-            const int inp = (b & 1) ^ flip;
-            next[c][s][inp] = (uint8_t)e;
-            outp[c][s][inp] = kOut[c][b];
-        }
-    hipEvent_t *ev = nullptr;
-    if (cfg->event_slot >= 0) {
-        WF_REQUIRE(cfg->event_slot < WF_LINK_EVENT_SLOTS, "wf_link_run: event_slot %d", cfg->event_slot);
-        if (!ctx->events) {
-            ctx->events = new hipEvent_t[WF_LINK_EVENT_SLOTS * (WF_LINK_STAGES + 1)];
-            for (int k = 0; k < WF_LINK_EVENT_SLOTS * (WF_LINK_STAGES + 1); ++k) WF_HIP(hipEventCreate(&ctx->events[k]));
-        }
-        ev = ctx->events + cfg->event_slot * (WF_LINK_STAGES + 1);
-    }
-#define MARKS(k, s) do { if (ev) WF_HIP(hipEventRecord(ev[k], wf_stream(s))); } while (0)
-#define MARK(k) MARKS(k, stream)
-    int rc;
-    MARKS(0, s_pro);
+    const soqpsk_trellis_tables T = soqpsk_trellis(cfg->differential);
+    hipEvent_t *ev;
+    if ((rc = link_stage_events(ctx, "wf_link_run", cfg->event_slot, ev))) return rc;
+    if ((rc = mark(ev, 0, s_pro))) return rc;
     // PRBS + precoder: two launches when the burst fits the scan-free form (wf_soqpsk_prbs_encode), else the generic four
-    rc = (cfg->fuse & 16) ? 1 : wf_soqpsk_prbs_encode(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, &next[0][0][0], &outp[0][0][0], bits,
+    rc = (cfg->fuse & 16) ? 1 : wf_soqpsk_prbs_encode(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, &T.next[0][0][0], &T.outp[0][0][0], bits,
                                                        cfg->nsym, syms, s_pro, ev ? (void *)ev[1] : nullptr);
     if (rc < 0) return rc;
     if (rc == 1) {
         if ((rc = wf_lfsr_generate(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, bits, cfg->nsym, nullptr, s_pro))) return rc;
-        MARKS(1, s_pro);
-        if ((rc = wf_fsm_encode(ctx, &next[0][0][0], &outp[0][0][0], 2, 4, 1, bits, cfg->nsym, 0, 0, syms, nullptr, s_pro))) return rc;
+        if ((rc = mark(ev, 1, s_pro))) return rc;
+        if ((rc = wf_fsm_encode(ctx, &T.next[0][0][0], &T.outp[0][0][0], 2, 4, 1, bits, cfg->nsym, 0, 0, syms, nullptr, s_pro))) return rc;
     }
-    if (!ahead) MARKS(2, s_pro);
+    if (!ahead && (rc = mark(ev, 2, s_pro))) return rc;
     // fuse bit 3 (with bits 1 and 2 in effect): modulator, channel and bank in ONE kernel — the clean
     // baseband samples never exist in HBM.  Outside that kernel's envelope the bits below apply.
     bool fused_all = false;
@@ -278,10 +240,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
             if (ahead && stage == 2) {
                 // stage events of such a block: "encode" = precoder + the two carry kernels (the prologue's tail), "fir" = the wait
                 // between the prologue's end and the main kernel's start (no kernel), "phase" = the main kernel
-                MARKS(2, s_pro);
+                if ((rc = mark(ev, 2, s_pro))) return rc;
                 WF_HIP(hipEventRecord(ctx->pipe_pro_done, wf_stream(s_pro)));
                 WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_pro_done, 0));
-                MARKS(3, s_main);
+                if ((rc = mark(ev, 3, s_main))) return rc;
             }
             rc = wf_mod_chan_bank_packed(ctx, syms, cfg->nsym, cfg->d_h, 1, cfg->d_pulse, cfg->ntaps, cfg->sps, M_PI / 4, cfg->d_mf_taps,
                                          cos(-M_PI / 4), sin(-M_PI / 4), cfg->sigma, cfg->seed, cfg->stream_id, 0, L.first, L.ncols, 0,
@@ -292,30 +254,24 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
         fused_all = true;
     }
     if (fused_all) {
-        if (!ahead) MARKS(3, s_main);                                    // the "fir" slot times the whole fused kernel (the "phase" slot when the prologue runs ahead: above)
-        MARKS(4, s_main); MARKS(5, s_main);
+        if (!ahead && (rc = mark(ev, 3, s_main))) return rc;   // the "fir" slot times the whole fused kernel (the "phase" slot when the prologue runs ahead: above)
+        if ((rc = mark(ev, 4, s_main)) || (rc = mark(ev, 5, s_main))) return rc;
         void *back = stream;                  // the stream the detector and the counter run on
         if (piped) {
             back = ctx->pipe_stream;
             WF_HIP(hipEventRecord(ctx->pipe_front, wf_stream(s_main)));
             WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_front, 0));
         }
-#define MARKB(k) do { if (ev) WF_HIP(hipEventRecord(ev[k], wf_stream(back))); } while (0)
-        MARKB(6);
+        if ((rc = mark(ev, 6, back))) return rc;
         rc = wf_viterbi4_detect_packed(ctx, mf, L.ncols, cfg->differential, link_warmup(cfg), dbits, dsyms, nullptr, back);
         if (rc) return rc;
-        MARKB(7);
+        if ((rc = mark(ev, 7, back))) return rc;
         int64_t m_ = L.ncols - length;
         if (m_ > cfg->nsym) m_ = cfg->nsym;
         if (m_ < 0) m_ = 0;
         if ((rc = wf_count_errors(ctx, dsyms + length, syms, dbits + length, bits, m_, d_counts, back))) return rc;
-        MARKB(8);
-#undef MARKB
-        if (piped) {
-            WF_HIP(hipEventRecord(ctx->pipe_done[ctx->pipe_set], wf_stream(back)));
-            ctx->pipe_done_valid[ctx->pipe_set] = true;
-            ctx->pipe_set ^= 1;
-        }
+        if ((rc = mark(ev, 8, back))) return rc;
+        if (piped && (rc = link_pipe_close(ctx, back))) return rc;
         if (h_compared) *h_compared = m_;
         return WF_OK;
     }
@@ -326,25 +282,24 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
         fused_mod = rc == 0;
     }
     if (fused_mod) {
-        MARK(3);   // the "fir" slot times the fused modulator, the "phase" slot is empty
+        if ((rc = mark(ev, 3, stream))) return rc;   // the "fir" slot times the fused modulator, the "phase" slot is empty
     } else {
         if ((rc = wf_upsample_fir_f64(ctx, syms, cfg->nsym, cfg->d_h, 1, cfg->d_pulse, cfg->ntaps, cfg->sps, freq, stream))) return rc;
-        MARK(3);
+        if ((rc = mark(ev, 3, stream))) return rc;
         if ((rc = wf_phase_cexp_f64(ctx, freq, L.npts, cfg->sps, M_PI / 4, 0.0, sig, nullptr, stream))) return rc;
     }
-    MARK(4);
+    if ((rc = mark(ev, 4, stream))) return rc;
     const double rot_re = cos(-M_PI / 4), rot_im = sin(-M_PI / 4);
     const bool fused_chan = (cfg->fuse & 2) && L.ncols > 0;
     // modulated *= exp(-j pi/4); received = modulated + noise   (in place, or inside the bank)
     if (!fused_chan)
         if ((rc = wf_awgn_c128(ctx, sig, L.npts, rot_re, rot_im, cfg->sigma, cfg->seed, cfg->stream_id, 0, sig, stream))) return rc;
-    MARK(5);
+    if ((rc = mark(ev, 5, stream))) return rc;
     // drop the first `length` detector outputs, compare min_size elements
     // (reference examples/soqpsk_detection.py:201-209)
     int64_t m = L.ncols - length;
     if (m > cfg->nsym) m = cfg->nsym;
     if (m < 0) m = 0;
-    const bool fused_count = false;
     const bool packed = fused_chan && link_packed_rows8(cfg);
     if (L.ncols > 0) {
         if (packed)   // detector-packed rows: 4 doubles per call (call index of column 0 is 0: even)
@@ -357,23 +312,19 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
             rc = wf_mf_bank_c128(ctx, sig, L.npts, cfg->d_mf_taps, cfg->mf_nfilt, cfg->mf_ntaps, L.first, cfg->sps,
                                  L.ncols, mf, stream);
         if (rc) return rc;
-        MARK(6);
-        if (fused_count)
-            rc = wf_viterbi4_detect_count(ctx, mf, L.ncols, cfg->differential, link_warmup(cfg), dbits, dsyms, bits, syms,
-                                          length, m, d_counts, stream);
-        else if (packed)
+        if ((rc = mark(ev, 6, stream))) return rc;
+        if (packed)
             rc = wf_viterbi4_detect_packed(ctx, mf, L.ncols, cfg->differential, link_warmup(cfg), dbits, dsyms, nullptr, stream);
         else
             rc = wf_viterbi4_detect(ctx, mf, L.ncols, cfg->differential, link_warmup(cfg), dbits, dsyms, nullptr, stream);
         if (rc) return rc;
     } else {
-        MARK(6);
+        if ((rc = mark(ev, 6, stream))) return rc;
     }
-    MARK(7);
-    if (m > 0 && !fused_count)
+    if ((rc = mark(ev, 7, stream))) return rc;
+    if (m > 0)
         if ((rc = wf_count_errors(ctx, dsyms + length, syms, dbits + length, bits, m, d_counts, stream))) return rc;
-    MARK(8);
-#undef MARK
+    if ((rc = mark(ev, 8, stream))) return rc;
     if (h_compared) *h_compared = m;
     return WF_OK;
 }
@@ -408,9 +359,9 @@ extern "C" int wf_link_layout(const wf_link_config *cfg, int64_t *info8)
 // (32 doubles), encoder state at the next window start, modulator phase carry (62-bit
 // fixed point) of the next window's first tile.  Decisions and counts equal the one-shot
 // wf_link_run over the whole stream.
-struct stream_layout {
+struct stream_layout : link_chunk_window {
     int64_t N, B, c, tile_len, spt, ntiles_total, halo, npts, ncols_total, first, m_total;
-    int64_t k_lo, ncols, ws, nloc, tile_lo, ntiles, out_origin, local_len, ws_next, q_out_tile;
+    int64_t out_origin, local_len, ws_next;
     size_t off_bits, off_syms, off_sig, off_mf, off_dbits, off_dsyms, total;
     bool ok;
 };
@@ -436,22 +387,11 @@ static stream_layout make_stream_layout(const wf_link_config *cfg, int64_t B, in
     if (S.m_total < 0) S.m_total = 0;
     S.ok = S.ok && B > 0 && B % S.spt == 0 && B % 128 == 0 && B >= 4 * S.halo &&
            S.tile_len >= cfg->mf_ntaps + 2 * cfg->sps;
-    S.k_lo = c * B;
-    const int64_t k_hi = S.k_lo + B < S.ncols_total ? S.k_lo + B : S.ncols_total;
-    S.ncols = k_hi > S.k_lo ? k_hi - S.k_lo : 0;
-    S.ws = c * B - S.halo > 0 ? c * B - S.halo : 0;
-    const int64_t we = (c + 1) * B + S.halo < S.N ? (c + 1) * B + S.halo : S.N;
-    S.nloc = we > S.ws ? we - S.ws : 0;
-    S.tile_lo = S.spt > 0 && c * B / S.spt - 1 > 0 ? c * B / S.spt - 1 : 0;
-    int64_t tile_hi = S.spt > 0 ? (c + 1) * B / S.spt + 1 : 0;
-    if (tile_hi > S.ntiles_total) tile_hi = S.ntiles_total;
-    S.ntiles = tile_hi > S.tile_lo ? tile_hi - S.tile_lo : 0;
+    static_cast<link_chunk_window &>(S) = link_chunk_window_of(B, c, S.halo, S.N, S.ncols_total, S.spt, S.ntiles_total);
     S.out_origin = S.tile_lo * S.tile_len;
-    const int64_t hi = tile_hi * S.tile_len < S.npts ? tile_hi * S.tile_len : S.npts;
+    const int64_t hi = S.tile_hi * S.tile_len < S.npts ? S.tile_hi * S.tile_len : S.npts;
     S.local_len = hi > S.out_origin ? hi - S.out_origin : 0;
     S.ws_next = (c + 1) * B - S.halo > 0 ? (c + 1) * B - S.halo : 0;
-    const int64_t next_tile_lo = S.spt > 0 ? (c + 1) * B / S.spt - 1 : 0;
-    S.q_out_tile = (next_tile_lo >= S.tile_lo && next_tile_lo < tile_hi) ? next_tile_lo - S.tile_lo : -1;
     size_t o = 0;
     const int64_t win = B + 2 * S.halo + 32;
     S.off_bits = o;  o += (size_t)round_up(win, 256);
@@ -584,17 +524,7 @@ static int stream_chunk_impl(wf_ctx *ctx, const wf_link_config *cfg, int64_t chu
     if (steady)
         WF_REQUIRE(wf_link_stream_interior(cfg, chunk_symbols, 1), "wf_link_stream_steady: the stream has no interior chunk of this size");
 
-    uint8_t next[2][4][2];
-    int8_t outp[2][4][2];
-    static const int8_t kOut[2][8] = {{0, 2, 0, -2, -2, 0, 2, 0}, {0, -2, 2, 0, 0, 2, -2, 0}};
-    for (int c = 0; c < 2; ++c)
-        for (int b = 0; b < 8; ++b) {
-            const int s = b >> 1;
-            const int e = c == 0 ? (s & 1) + 2 * (b & 1) : (s & 2) + (b & 1);
-            const int flip = cfg->differential ? (c == 0 ? (s >> 1) : (s & 1)) : 0;
-            next[c][s][(b & 1) ^ flip] = (uint8_t)e;
-            outp[c][s][(b & 1) ^ flip] = kOut[c][b];
-        }
+    const soqpsk_trellis_tables T = soqpsk_trellis(cfg->differential);
     int rc = WF_OK;
     const bool packed = link_packed_rows8(cfg);     // (the stream's one-kernel windows are an sps-8 path)
     const double rot_re = cos(-M_PI / 4), rot_im = sin(-M_PI / 4);
@@ -603,7 +533,7 @@ static int stream_chunk_impl(wf_ctx *ctx, const wf_link_config *cfg, int64_t chu
         if ((rc = wf_lfsr_generate_dyn(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip + (uint64_t)S.ws, steady ? dyn : nullptr,
                                        bits, S.nloc, nullptr, stream))) return rc;
         const int64_t at = S.ws_next - S.ws;
-        if ((rc = wf_fsm_encode_core(ctx, &next[0][0][0], &outp[0][0][0], 2, 4, 1, bits, S.nloc, S.ws, 0, enc_state, syms, nullptr,
+        if ((rc = wf_fsm_encode_core(ctx, &T.next[0][0][0], &T.outp[0][0][0], 2, 4, 1, bits, S.nloc, S.ws, 0, enc_state, syms, nullptr,
                                      at <= S.nloc ? enc_state : nullptr, at, stream))) return rc;
         if (steady) {   // the PRBS position of the next chunk's part 1 (each part advances ITS word: parts of different chunks overlap)
             hipLaunchKernelGGL(stream_advance_kernel, dim3(1), dim3(64), 0, wf_stream(stream), dyn, (uint64_t)chunk_symbols);

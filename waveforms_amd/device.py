@@ -6,6 +6,7 @@ stream.  The reference-shaped host API (``waveforms_amd.cpm`` ...) is built on t
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 
@@ -462,6 +463,35 @@ def viterbi_unmerged(reset: bool = True, ctx=None) -> int:
     n = ctypes.c_int64(0)
     _hip.check(_hip.lib().wf_viterbi4_unmerged(_ctx(ctx), ctypes.byref(n), int(reset), _hip.stream()))
     return int(n.value)
+
+
+def require_proven(ctx=None, check: bool = False, also=None) -> None:
+    """Raise RuntimeError if the chunk-parallel detectors left a chunk unproven on ``ctx`` since the last reset — which only
+    a context with the repairs switched off (WF_OPT_DET_REPAIR, tests of the proof itself) can do.  Reads with reset
+    (``viterbi_unmerged``; synchronises); ``check``: ``wf_ctx_check`` first (joins a pipelined link's side streams and reads
+    the fault word); ``also``: a second context whose count is reset too before raising (the other lane of a stream)."""
+    if check:
+        _hip.check(_hip.lib().wf_ctx_check(_ctx(ctx), _hip.stream()))
+    unproven = viterbi_unmerged(reset=True, ctx=ctx)
+    if unproven:
+        if also is not None:
+            viterbi_unmerged(reset=True, ctx=also)
+        raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+
+
+@contextlib.contextmanager
+def proven_carry(carry, ctx):
+    """Around a detector launch that advances the device-resident ``carry``: ``require_proven`` behind it, and where that
+    raises the carry is what it was before the launch (cloned only on a context that has the repairs switched off: nothing
+    else can raise behind a launch), so the caller can run the same rows again."""
+    keep = carry.clone() if _hip.get_option(ctx, _hip.WF_OPT_DET_REPAIR) else None
+    yield
+    try:
+        require_proven(ctx)
+    except RuntimeError:
+        if keep is not None:
+            carry.copy_(keep)
+        raise
 
 
 def viterbi_repaired(reset: bool = True, ctx=None) -> int:

@@ -4,6 +4,10 @@ error count in one C-ABI call (``wf_link_run``), all intermediates in one HBM wo
 This is the unit of work of the benchmark (one step = one block) and of the Monte-Carlo
 BER sweep (one trial block per (Eb/N0 point, block index)).  It restates the
 per-waveform body of reference examples/soqpsk_detection.py:45-216.
+
+Four classes, each a base plus a waveform side: ``SOQPSKLink`` / ``CPMLink`` (``_Link``: one block per call) and
+``SOQPSKStream`` / ``CPMStream`` (``_Stream``: a long stream in chunks), with ``_SOQPSK`` / ``_CPM`` holding the tables,
+``cfg`` and the entry-point names of their waveform.
 """
 from __future__ import annotations
 
@@ -49,24 +53,58 @@ def soqpsk_warmup_param(rows: int) -> int:
     return max(int(rows) - 1, 0)
 
 
-class SOQPSKLink:
-    def __init__(self, nsym: int, sps: int = 8, **kw) -> None:
-        self._configure(nsym, sps, **kw)
-        self.workspace_bytes = _hip.lib().wf_link_workspace_bytes(ctypes.byref(self.cfg))
-        if self.workspace_bytes < 0:
-            raise ValueError("invalid link configuration")
-        self.workspace = _hip.empty(self.workspace_bytes, "uint8")
+class _Session:
+    """What the links and the streams share: the library context, the error counters and the proven result."""
+
+    def _open(self, private_ctx: bool) -> None:
+        # a link that runs on its own stream next to other links needs its own scratch
+        self._ctx = _hip.new_ctx() if private_ctx else _hip.ctx()
+        _hip.check(_hip.lib().wf_ctx_forget_promises(self._ctx))    # (this link's tables may sit where a dead link's did: every promise is checked afresh)
+        self._owns_ctx = bool(private_ctx)
+
+    def _close(self) -> None:
+        if getattr(self, "_owns_ctx", False):
+            _hip.free_ctx(self._ctx)
+            self._owns_ctx = False
+
+    def _allocate(self, nbytes: int) -> None:
+        self.workspace_bytes = nbytes
+        self.workspace = _hip.empty(nbytes, "uint8")
         self.counts = _hip.zeros(2, "int64")
         self.compared = 0
+
+    def _words(self, c_fn: str, keys, *args) -> dict:
+        """The eight int64 words a layout entry point writes for ``self.cfg``, by name."""
+        info = (ctypes.c_int64 * 8)()
+        _hip.check(getattr(_hip.lib(), c_fn)(ctypes.byref(self.cfg), *args, info))
+        return dict(zip(keys, (int(v) for v in info)))
+
+    def result(self) -> tuple[int, int, int]:
+        """(symbol errors, bit errors, symbols compared) — synchronises.  The detector's chunks are proven (and, where
+        a warm-up fell short, repaired) on the device, so this never depends on ``warmup`` or Eb/N0; it raises only
+        if a chunk was left unproven because the context's WF_OPT_DET_REPAIR option switched the repairs off."""
+        from waveforms_amd import device as dev
+
+        dev.require_proven(self._ctx, check=True)
+        se, be = (int(v) for v in self.counts.cpu().tolist())
+        return se, be, self.compared
+
+
+class _SOQPSK:
+    """The SOQPSK side of a link or a stream: tables, ``cfg`` and the names of its entry points."""
+
+    WORKSPACE_BYTES, LAYOUT, RUN = "wf_link_workspace_bytes", "wf_link_layout", "wf_link_run"
+    STREAM_WORKSPACE_BYTES, STREAM_LAYOUT = "wf_link_stream_workspace_bytes", "wf_link_stream_layout"
+    STREAM_CHUNK, STREAM_CHUNK_PHASE = "wf_link_stream_chunk", "wf_link_stream_chunk_phase"
+    LAYOUT_KEYS = ("calls", "one_kernel_front_end", "off_bits", "off_syms", "off_signal", "row_bytes", "signal_len", "off_mf")
+    CHUNK_KEYS = ("calls", "first_call", "off_bits", "off_syms", "off_signal", "signal_origin", "signal_len", "off_mf")
+    STAGES = ("prbs", "encode", "fir", "phase", "awgn", "mfbank", "viterbi", "count")
 
     def _configure(self, nsym: int, sps: int = 8, pulse=None, mod_index: float = 0.25, detector: str = "PT",
                    pn_degree: int = 23, differential: bool = True, timing_offset: int | None = None,
                    warmup: int = 0, fuse: int = 15, private_ctx: bool = False, factor_bank: bool = True) -> None:
         self.nsym, self.sps = int(nsym), int(sps)
-        # a link that runs on its own stream next to other links needs its own scratch
-        self._ctx = _hip.new_ctx() if private_ctx else _hip.ctx()
-        _hip.check(_hip.lib().wf_ctx_forget_promises(self._ctx))    # (this link's tables may sit where a dead link's did: every promise is checked afresh)
-        self._owns_ctx = bool(private_ctx)
+        self._open(private_ctx)
         pulse = freq_pulse_soqpsk_tg(sps) if pulse is None else np.asarray(pulse, dtype=np.float64)
         factors = None
         if detector == "PT":
@@ -102,6 +140,75 @@ class SOQPSKLink:
         cfg.d_mf_factor = self._d_factor.data_ptr() if self._d_factor is not None else None
         self.cfg = cfg
 
+    def _sigma(self, ebn0_db: float) -> float:
+        return sigma_for_ebn0(ebn0_db, self.sps)
+
+
+class _CPM:
+    """The side of the waveforms served by the generic CPM trellis detector: ``waveform`` "multih" (ARTM multi-h CPM,
+    BASELINE configs[2]) or "pcmfm"."""
+
+    WORKSPACE_BYTES, LAYOUT, RUN = "wf_cpm_link_workspace_bytes", "wf_cpm_link_layout", "wf_cpm_link_run"
+    STREAM_WORKSPACE_BYTES, STREAM_LAYOUT = "wf_cpm_link_stream_workspace_bytes", "wf_cpm_link_stream_layout"
+    STREAM_CHUNK, STREAM_CHUNK_PHASE = "wf_cpm_link_stream_chunk", "wf_cpm_link_stream_chunk_phase"
+    LAYOUT_KEYS = ("calls", "start0", "off_decisions", "off_syms", "off_signal", "one_kernel_front_end", "signal_len", "off_rows")
+    CHUNK_KEYS = ("calls", "first_call", "off_decisions", "off_syms", "syms_origin", "stream_calls", "sym_per_tile", "off_rows")
+    STAGES = ("prbs", "map", "modulate", "-", "awgn", "mfbank", "viterbi", "count")
+
+    def _configure(self, nsym: int, sps: int = 8, waveform: str = "multih", spec=None, pn_degree: int = 23, warmup: int = 0,
+                   skip_head: int = 64, private_ctx: bool = False, fuse: int = 10, paired_templates: bool = True) -> None:
+        from .viterbi import cpm
+
+        if waveform == "multih":
+            from .cpm.multih import freq_pulse_multih_irig
+
+            pulse, kind, spec = freq_pulse_multih_irig(sps), 1, spec or cpm.ARTM_16
+        elif waveform == "pcmfm":
+            from .cpm.pcmfm import freq_pulse_pcmfm
+
+            pulse, kind, spec = freq_pulse_pcmfm(sps), 2, spec or cpm.PCMFM_10
+        else:
+            raise ValueError(f"unknown waveform {waveform!r}")
+        self.nsym, self.sps, self.spec, self.waveform = int(nsym), int(sps), spec, waveform
+        self._open(private_ctx)
+        self._d_h = _hip.to_device(spec.mod_index)
+        self._d_pulse = _hip.to_device(np.asarray(pulse, dtype=np.float64))
+        templates = cpm.matched_filter_templates(pulse, sps, spec)
+        self._d_templates = _hip.to_device(templates)
+        # A symmetric alphabet makes the templates of a symbol pattern and of its negation exact conjugates (filter f and
+        # nfilt - 1 - f): the one-kernel front end then forms each pair of filters from four real sums (wf_cpm_link_config.fuse
+        # bit 6, which vouches for exactly this identity — checked here, bit for bit)
+        self.paired_templates = bool(paired_templates and templates.shape[1] in (4, 16) and np.array_equal(templates[:, ::-1, :], np.conj(templates)))
+        if self.paired_templates:
+            fuse = int(fuse) | 64
+        self._d_rot = _hip.to_device(cpm.rotation_table(spec))
+        cfg = _hip.CPMLinkConfig()
+        cfg.nsym, cfg.sps = self.nsym, self.sps
+        cfg.degree, cfg.mask, cfg.state, cfg.skip = pn_degree, generate_mask(pn_degree), (1 << pn_degree) - 1, 0
+        cfg.mapper_kind, cfg.det = kind, spec.c_config()
+        cfg.d_h, cfg.d_pulse, cfg.ntaps = self._d_h.data_ptr(), self._d_pulse.data_ptr(), int(np.asarray(pulse).size)
+        cfg.d_templates, cfg.d_rot_cs = self._d_templates.data_ptr(), self._d_rot.data_ptr()
+        cfg.sigma, cfg.seed, cfg.stream_id = 0.0, 1, 0
+        cfg.warmup, cfg.skip_head, cfg.event_slot, cfg.fuse = warmup, skip_head, -1, int(fuse)
+        self.cfg = cfg
+
+    def _sigma(self, ebn0_db: float | None) -> float:
+        """``ebn0_db=None`` = no noise."""
+        from .viterbi.cpm import sigma_for_ebn0 as cpm_sigma
+
+        return 0.0 if ebn0_db is None else cpm_sigma(ebn0_db, self.sps, self.spec.bits_per_symbol)
+
+
+class _Link(_Session):
+    """One trial block per C-ABI call (``RUN``), all intermediates in one HBM workspace."""
+
+    def __init__(self, nsym: int, sps: int = 8, *args, **kw) -> None:
+        self._configure(nsym, sps, *args, **kw)
+        nbytes = getattr(_hip.lib(), self.WORKSPACE_BYTES)(ctypes.byref(self.cfg))
+        if nbytes < 0:
+            raise ValueError("invalid link configuration")
+        self._allocate(nbytes)
+
     def __del__(self):
         try:
             if getattr(self, "cfg", None) is not None and (self.cfg.fuse & 32) and getattr(self, "workspace", None) is not None:
@@ -110,9 +217,49 @@ class SOQPSKLink:
                 _hip.torch().cuda.current_stream().synchronize()
         except Exception:          # noqa: BLE001 — interpreter teardown
             pass
-        if getattr(self, "_owns_ctx", False):
-            _hip.free_ctx(self._ctx)
-            self._owns_ctx = False
+        self._close()
+
+    def layout(self) -> dict:
+        """Byte offsets of the intermediates inside ``self.workspace`` (and what else the library says of ``self.cfg``)."""
+        return self._words(self.LAYOUT, self.LAYOUT_KEYS)
+
+    def reset_counts(self) -> None:
+        # (fuse bit 5: earlier blocks' counters may still be running on the context's side stream)
+        _hip.check(_hip.lib().wf_link_join(self._ctx, _hip.stream()))
+        self.counts.zero_()
+        self.compared = 0
+
+    def stage_ms(self, event_slot: int) -> dict[str, float]:
+        """Per-stage HIP-event times (ms) of the last run that used ``event_slot``."""
+        buf = (ctypes.c_float * len(self.STAGES))()
+        _hip.check(_hip.lib().wf_link_stage_ms(self._ctx, event_slot, buf))
+        return {k: float(v) for k, v in zip(self.STAGES, buf) if k != "-"}
+
+    def launch(self, counts_ptr: int, ebn0_db: float | None, seed: int, stream_id: int, skip_bits: int, event_slot: int = -1,
+               warmup: int | None = None) -> int:
+        """Queue one trial block on the current stream with its error counts added to the two int64 words at ``counts_ptr``
+        (``warmup``: for this block only); returns the number of symbols it compares."""
+        c = self.cfg
+        c.sigma, c.seed, c.stream_id, c.skip, c.event_slot = self._sigma(ebn0_db), seed, stream_id, skip_bits, event_slot
+        keep = c.warmup
+        if warmup is not None:
+            c.warmup = warmup
+        m = ctypes.c_int64(0)
+        try:
+            _hip.check(getattr(_hip.lib(), self.RUN)(self._ctx, ctypes.byref(c), self.workspace.data_ptr(), self.workspace_bytes,
+                                                     counts_ptr, ctypes.byref(m), _hip.stream()))
+        finally:
+            c.warmup = keep
+        return m.value
+
+    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0, skip_bits: int = 0, event_slot: int = -1) -> None:
+        """Queue one trial block on the current stream; error counts accumulate on the
+        device (``self.counts``), the compared-symbol count on the host."""
+        self.compared += self.launch(self.counts.data_ptr(), ebn0_db, seed, stream_id, skip_bits, event_slot)
+
+
+class SOQPSKLink(_SOQPSK, _Link):
+    """PRBS -> precoder -> modulator -> AWGN -> matched-filter bank -> 4-state detector -> error count (``wf_link_run``)."""
 
     @property
     def row_bytes(self) -> int:
@@ -121,26 +268,8 @@ class SOQPSKLink:
         front end at 8 / 10 / 20)."""
         return self.layout()["row_bytes"]            # the library's own rule (wf_link_layout)
 
-    def layout(self) -> dict:
-        """Byte offsets of the intermediates inside ``self.workspace``."""
-        info = (ctypes.c_int64 * 8)()
-        _hip.check(_hip.lib().wf_link_layout(ctypes.byref(self.cfg), info))
-        keys = ("calls", "one_kernel_front_end", "off_bits", "off_syms", "off_signal", "row_bytes", "signal_len", "off_mf")
-        return dict(zip(keys, (int(v) for v in info)))
-
-    def reset_counts(self) -> None:
-        # (fuse bit 5: earlier blocks' counters may still be running on the context's side stream)
-        _hip.check(_hip.lib().wf_link_join(self._ctx, _hip.stream()))
-        self.counts.zero_()
-        self.compared = 0
-
-    STAGES = ("prbs", "encode", "fir", "phase", "awgn", "mfbank", "viterbi", "count")
-
     def stage_ms(self, event_slot: int) -> dict[str, float]:
-        """Per-stage HIP-event times (ms) of the last run that used ``event_slot``."""
-        buf = (ctypes.c_float * len(self.STAGES))()
-        _hip.check(_hip.lib().wf_link_stage_ms(self._ctx, event_slot, buf))
-        d = dict(zip(self.STAGES, (float(v) for v in buf)))
+        d = super().stage_ms(event_slot)
         if self.prologue_ahead:
             # (wf_link_run, round 6: the prologue of such a block runs on its own stream beside the previous front end; the event
             #  pair of the "fir" slot then brackets the WAIT between the prologue's end and the main kernel's start, and the main
@@ -154,39 +283,120 @@ class SOQPSKLink:
         own stream (``WF_OPT_PIPE_RESERVE_CUS`` other than 0: a measured alternative, not the default)."""
         return bool(self.cfg.fuse & 32) and bool(self.layout()["one_kernel_front_end"]) and _hip.get_option(self._ctx, _hip.WF_OPT_PIPE_RESERVE_CUS) != 0
 
-    def run_block(self, ebn0_db: float, seed: int = 1, stream_id: int = 0, skip_bits: int = 0,
-                  event_slot: int = -1) -> None:
-        """Queue one trial block on the current stream; error counts accumulate on the
-        device (``self.counts``), the compared-symbol count on the host."""
-        c = self.cfg
-        c.sigma, c.seed, c.stream_id, c.skip = sigma_for_ebn0(ebn0_db, self.sps), seed, stream_id, skip_bits
-        c.event_slot = event_slot
+
+class CPMLink(_CPM, _Link):
+    """Device-resident link for the waveforms served by the generic CPM trellis detector
+    (``wf_cpm_link_run``): PRBS -> mapper -> cpm_modulate -> AWGN -> matched-filter rows ->
+    detector -> error count."""
+
+
+class _Stream(_Session):
+    """The chain of a link over a continuous stream of ``total_symbols`` symbols, processed in chunks of ``chunk_symbols``
+    detector calls: HBM use of one chunk, what a chunk needs of its neighbours re-generated as a halo or carried in a small
+    device block (``self.state``).  Decisions and error counts equal the one-shot link over the whole stream."""
+
+    WAITS = ()              # the parts of a chunk (1, 4, 2: ``STREAM_CHUNK_PHASE``) that take a carry from the same part of the chunk before
+    _ctx2 = None            # the second lane of the pipelined forms: context, workspace (_ws2) and the two HIP streams (_lanes)
+
+    def __init__(self, total_symbols: int, chunk_symbols: int, sps: int = 8, **kw) -> None:
+        self._configure(int(total_symbols), sps, **kw)
+        self.total_symbols, self.chunk_symbols = int(total_symbols), int(chunk_symbols)
+        lib = _hip.lib()
+        nbytes = getattr(lib, self.STREAM_WORKSPACE_BYTES)(ctypes.byref(self.cfg), self.chunk_symbols)
+        if nbytes < 0:
+            tl, spt, nt = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+            lib.wf_mod_tile_geometry(self.sps, self.cfg.ntaps, self.total_symbols, ctypes.byref(tl), ctypes.byref(spt), ctypes.byref(nt))
+            raise ValueError(self._chunk_rule(spt.value))
+        self._allocate(nbytes)
+        self.state = self._carry()
+        self.total_calls = self._total_calls()
+        self.nchunks = -(-self.total_calls // self.chunk_symbols)
+
+    def __del__(self):
+        if self._ctx2:
+            _hip.free_ctx(self._ctx2)
+            self._ctx2 = None
+        self._close()
+
+    def reset(self) -> None:
+        self.state.zero_()
+        self.counts.zero_()
+        self.compared = 0
+
+    def chunk_info(self, c: int) -> dict:
+        return self._words(self.STREAM_LAYOUT, self.CHUNK_KEYS, self.chunk_symbols, c)
+
+    def _point(self, ebn0_db: float | None, seed: int, stream_id: int):
+        cfg = self.cfg
+        cfg.sigma, cfg.seed, cfg.stream_id, cfg.event_slot = self._sigma(ebn0_db), seed, stream_id, -1
+        return cfg
+
+    def run_chunk(self, c: int, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
         m = ctypes.c_int64(0)
-        _hip.check(_hip.lib().wf_link_run(self._ctx, ctypes.byref(c), self.workspace.data_ptr(),
-                                          self.workspace_bytes, self.counts.data_ptr(), ctypes.byref(m),
-                                          _hip.stream()))
+        _hip.check(getattr(_hip.lib(), self.STREAM_CHUNK)(self._ctx, ctypes.byref(self._point(ebn0_db, seed, stream_id)), self.chunk_symbols, c,
+                                                          self.state.data_ptr(), self.workspace.data_ptr(), self.workspace_bytes,
+                                                          self.counts.data_ptr(), ctypes.byref(m), _hip.stream()))
         self.compared += m.value
 
-    def result(self) -> tuple[int, int, int]:
-        """(symbol errors, bit errors, symbols compared) — synchronises.  The detector's chunks are proven (and, where
-        a warm-up fell short, repaired) on the device, so this never depends on ``warmup`` or Eb/N0; it raises only
-        if a chunk was left unproven because the context's WF_OPT_DET_REPAIR option switched the repairs off."""
-        _hip.check(_hip.lib().wf_ctx_check(self._ctx, _hip.stream()))
+    def run(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> tuple[int, int, int]:
+        """All chunks in order; returns (symbol errors, bit errors, symbols compared)."""
+        self.reset()
+        for c in range(self.nchunks):
+            self.run_chunk(c, ebn0_db, seed, stream_id)
+        return self.result()
+
+    def _second_lane(self) -> None:
+        if self._ctx2 is None:
+            torch = _hip.torch()
+            self._ws2 = _hip.empty(self.workspace_bytes, "uint8")
+            self._ctx2 = _hip.new_ctx()
+            self._lanes = [torch.cuda.Stream(), torch.cuda.Stream()]
+
+    def _late_result(self) -> tuple[int, int, int]:
+        """:meth:`result` behind the proof check of the second lane's context (the first context's count is read by result())."""
         from waveforms_amd import device as dev
 
-        unmerged = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-        if unmerged:
-            raise RuntimeError(f"{unmerged} detector chunk(s) were left unproven (the repairs are switched off on this context)")
-        se, be = (int(v) for v in self.counts.cpu().tolist())
-        return se, be, self.compared
+        dev.require_proven(self._ctx2, check=True, also=self._ctx)
+        return self.result()
+
+    def run_pipelined(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> tuple[int, int, int]:
+        """Like :meth:`run` with consecutive chunks alternating between two HIP streams, each with its own workspace and
+        library context.  A chunk is issued as three parts (``STREAM_CHUNK_PHASE``: 1 = PRBS and what follows it up to the
+        modulator's carries, 4 = modulator + channel + filters, 2 = detector + error count), and a part in ``WAITS`` waits
+        for the same part of the previous chunk, which is where its carry comes from — so the small serial kernels of chunk
+        c + 1 and the detector of chunk c run beside a main kernel instead of between two.  Same decisions and counts as
+        :meth:`run`."""
+        torch = _hip.torch()
+        self.reset()
+        cfg = self._point(ebn0_db, seed, stream_id)
+        self._second_lane()
+        main = torch.cuda.current_stream()
+        for lane in self._lanes:
+            lane.wait_stream(main)                       # the carry block / counters were zeroed on the caller's stream
+        fn, m = getattr(_hip.lib(), self.STREAM_CHUNK_PHASE), ctypes.c_int64(0)
+        done = dict.fromkeys(self.WAITS)
+        for c in range(self.nchunks):
+            lane, ws, ctx = self._lanes[c & 1], (self.workspace, self._ws2)[c & 1], (self._ctx, self._ctx2)[c & 1]
+            with torch.cuda.stream(lane):
+                for part in (1, 4, 2):
+                    if done.get(part) is not None:
+                        lane.wait_event(done[part])
+                    _hip.check(fn(ctx, ctypes.byref(cfg), self.chunk_symbols, c, self.state.data_ptr(), ws.data_ptr(), self.workspace_bytes,
+                                  self.counts.data_ptr(), ctypes.byref(m), part, lane.cuda_stream))
+                    if part in done:
+                        done[part] = torch.cuda.Event()
+                        done[part].record(lane)
+                self.compared += m.value
+        for lane in self._lanes:
+            main.wait_stream(lane)
+        return self._late_result()
 
 
-class SOQPSKStream:
-    """The same chain over a continuous stream of ``total_symbols`` symbols, processed in
-    chunks of ``chunk_symbols`` detector calls (``wf_link_stream_chunk``; BASELINE config 5).
-    Neighbouring context is re-generated as a halo or carried in a 512-byte device block;
-    decisions and error counts equal a one-shot :class:`SOQPSKLink` over the whole stream,
-    while HBM use is that of one chunk."""
+class SOQPSKStream(_SOQPSK, _Stream):
+    """The SOQPSK chain as a stream (``wf_link_stream_chunk``; BASELINE config 5): the carry is a 512-byte device block
+    (detector state, encoder state, modulator phase), and all three parts of a chunk take one from the chunk before."""
+
+    WAITS = (1, 4, 2)
 
     @property
     def row_bytes(self) -> int:
@@ -195,105 +405,14 @@ class SOQPSKStream:
         c = self.cfg
         return 32 if (c.fuse & 4) and (c.fuse & 2) and c.sps == 8 and c.mf_nfilt == 3 else 16 * c.mf_nfilt
 
-    def __init__(self, total_symbols: int, chunk_symbols: int, sps: int = 8, **kw) -> None:
-        # reuse the link's configuration (taps, pulse, PRBS ...) without its one-shot workspace
-        self._proto = SOQPSKLink.__new__(SOQPSKLink)
-        SOQPSKLink._configure(self._proto, int(total_symbols), sps, **kw)
-        self.cfg, self._ctx, self.sps = self._proto.cfg, self._proto._ctx, int(sps)
-        self.total_symbols, self.chunk_symbols = int(total_symbols), int(chunk_symbols)
-        lib = _hip.lib()
-        nbytes = lib.wf_link_stream_workspace_bytes(ctypes.byref(self.cfg), self.chunk_symbols)
-        if nbytes < 0:
-            tl, spt, nt = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-            lib.wf_mod_tile_geometry(self.sps, self.cfg.ntaps, self.total_symbols, ctypes.byref(tl), ctypes.byref(spt),
-                                     ctypes.byref(nt))
-            raise ValueError(f"chunk_symbols must be a multiple of {spt.value} (one modulator tile) and of 128, and at "
-                             f"least {4 * (spt.value + 48)}")
-        self.workspace_bytes = nbytes
-        self.workspace = _hip.empty(nbytes, "uint8")
-        self.state = _hip.zeros(64, "float64")          # WF_LINK_STREAM_STATE_BYTES = 512
-        self.counts = _hip.zeros(2, "int64")
-        self.compared = 0
-        info = (ctypes.c_int64 * 8)()
-        _hip.check(lib.wf_link_layout(ctypes.byref(self.cfg), info))
-        self.total_calls = int(info[0])
-        self.nchunks = -(-self.total_calls // self.chunk_symbols)
+    def _chunk_rule(self, spt: int) -> str:
+        return f"chunk_symbols must be a multiple of {spt} (one modulator tile) and of 128, and at least {4 * (spt + 48)}"
 
-    def reset(self) -> None:
-        self.state.zero_()
-        self.counts.zero_()
-        self.compared = 0
+    def _carry(self):
+        return _hip.zeros(64, "float64")          # WF_LINK_STREAM_STATE_BYTES = 512
 
-    def chunk_info(self, c: int) -> dict:
-        info = (ctypes.c_int64 * 8)()
-        _hip.check(_hip.lib().wf_link_stream_layout(ctypes.byref(self.cfg), self.chunk_symbols, c, info))
-        keys = ("calls", "first_call", "off_bits", "off_syms", "off_signal", "signal_origin", "signal_len", "off_mf")
-        return dict(zip(keys, (int(v) for v in info)))
-
-    def run_chunk(self, c: int, ebn0_db: float, seed: int = 1, stream_id: int = 0) -> None:
-        cfg = self.cfg
-        cfg.sigma, cfg.seed, cfg.stream_id, cfg.event_slot = sigma_for_ebn0(ebn0_db, self.sps), seed, stream_id, -1
-        m = ctypes.c_int64(0)
-        _hip.check(_hip.lib().wf_link_stream_chunk(self._ctx, ctypes.byref(cfg), self.chunk_symbols, c,
-                                                   self.state.data_ptr(), self.workspace.data_ptr(), self.workspace_bytes,
-                                                   self.counts.data_ptr(), ctypes.byref(m), _hip.stream()))
-        self.compared += m.value
-
-    def run(self, ebn0_db: float, seed: int = 1, stream_id: int = 0) -> tuple[int, int, int]:
-        """All chunks in order; returns (symbol errors, bit errors, symbols compared)."""
-        self.reset()
-        for c in range(self.nchunks):
-            self.run_chunk(c, ebn0_db, seed, stream_id)
-        return self.result()
-
-    def run_pipelined(self, ebn0_db: float, seed: int = 1, stream_id: int = 0) -> tuple[int, int, int]:
-        """Like :meth:`run` with consecutive chunks alternating between two HIP streams, each with its own
-        workspace and library context.  A chunk is issued as three parts (``wf_link_stream_chunk_phase``)
-        and each part waits only for the same part of the previous chunk, which is where its carry comes
-        from: PRBS / encoder / modulator carries (encoder state, modulator phase), the modulator + channel
-        + bank kernel, detector + error count (detector state).  So the small serial kernels of chunk c + 1
-        and the detector of chunk c run beside a main kernel instead of between two.  Same decisions and
-        counts as :meth:`run`."""
-        torch = _hip.torch()
-        self.reset()
-        cfg = self.cfg
-        cfg.sigma, cfg.seed, cfg.stream_id, cfg.event_slot = sigma_for_ebn0(ebn0_db, self.sps), seed, stream_id, -1
-        if getattr(self, "_ws2", None) is None:
-            self._ws2 = _hip.empty(self.workspace_bytes, "uint8")
-            self._ctx2 = _hip.new_ctx()
-            self._lanes = [torch.cuda.Stream(), torch.cuda.Stream()]
-        main = torch.cuda.current_stream()
-        for lane in self._lanes:
-            lane.wait_stream(main)                       # the carry block / counters were zeroed on the caller's stream
-        lib, m = _hip.lib(), ctypes.c_int64(0)
-        done = {1: None, 4: None, 2: None}
-        for c in range(self.nchunks):
-            lane, ws, ctx = self._lanes[c & 1], (self.workspace, self._ws2)[c & 1], (self._ctx, self._ctx2)[c & 1]
-            with torch.cuda.stream(lane):
-                for part in (1, 4, 2):
-                    if done[part] is not None:
-                        lane.wait_event(done[part])
-                    _hip.check(lib.wf_link_stream_chunk_phase(ctx, ctypes.byref(cfg), self.chunk_symbols, c, self.state.data_ptr(),
-                                                              ws.data_ptr(), self.workspace_bytes, self.counts.data_ptr(),
-                                                              ctypes.byref(m), part, lane.cuda_stream))
-                    done[part] = torch.cuda.Event()
-                    done[part].record(lane)
-                self.compared += m.value
-        for lane in self._lanes:
-            main.wait_stream(lane)
-        from waveforms_amd import device as dev
-
-        _hip.check(lib.wf_ctx_check(self._ctx2, _hip.stream()))
-        late = dev.viterbi_unmerged(reset=True, ctx=self._ctx2)     # the first context's count is read by result()
-        if late:
-            dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-            raise RuntimeError(f"{late} detector chunk(s) were left unproven (the repairs are switched off on this context)")
-        return self.result()
-
-    def __del__(self):
-        if getattr(self, "_ctx2", None):
-            _hip.free_ctx(self._ctx2)
-            self._ctx2 = None
+    def _total_calls(self) -> int:
+        return self._words(self.LAYOUT, self.LAYOUT_KEYS)["calls"]
 
     def interior_chunks(self) -> int:
         """Number of consecutive chunks 1, 2, ... that issue exactly the launches of chunk 1."""
@@ -307,8 +426,7 @@ class SOQPSKStream:
         chunk (the PRBS position and the noise counter live in the device carry block)."""
         torch = _hip.torch()
         self.reset()
-        cfg = self.cfg
-        cfg.sigma, cfg.seed, cfg.stream_id, cfg.event_slot = sigma_for_ebn0(ebn0_db, self.sps), seed, stream_id, -1
+        cfg = self._point(ebn0_db, seed, stream_id)
         self.run_chunk(0, ebn0_db, seed, stream_id)
         n_int = self.interior_chunks()
         if n_int:
@@ -339,12 +457,8 @@ class SOQPSKStream:
         (``wf_link_stream_steady_phase``: each part advances its own position word on the device)."""
         torch = _hip.torch()
         self.reset()
-        cfg = self.cfg
-        cfg.sigma, cfg.seed, cfg.stream_id, cfg.event_slot = sigma_for_ebn0(ebn0_db, self.sps), seed, stream_id, -1
-        if not hasattr(self, "_ws2"):
-            self._ws2 = _hip.empty(self.workspace_bytes, "uint8")
-            self._ctx2 = _hip.new_ctx()
-            self._lanes = [torch.cuda.Stream(), torch.cuda.Stream()]
+        cfg = self._point(ebn0_db, seed, stream_id)
+        self._second_lane()
         lib, m = _hip.lib(), ctypes.c_int64(0)
         K = max(2, int(chunks_per_graph) // 2 * 2)
         n_int = self.interior_chunks()
@@ -397,226 +511,21 @@ class SOQPSKStream:
                 self.compared += m.value
             else:
                 self.run_chunk(c, ebn0_db, seed, stream_id)
-        from waveforms_amd import device as dev
-
-        _hip.check(lib.wf_ctx_check(self._ctx2, _hip.stream()))
-        late = dev.viterbi_unmerged(reset=True, ctx=self._ctx2)
-        if late:
-            dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-            raise RuntimeError(f"{late} detector chunk(s) were left unproven (the repairs are switched off on this context)")
-        return self.result()
-
-    def result(self) -> tuple[int, int, int]:
-        """Like :meth:`SOQPSKLink.result`."""
-        return SOQPSKLink.result(self)
+        return self._late_result()
 
 
-class CPMLink:
-    """Device-resident link for the waveforms served by the generic CPM trellis detector
-    (``wf_cpm_link_run``): PRBS -> mapper -> cpm_modulate -> AWGN -> matched-filter rows ->
-    detector -> error count.  ``waveform``: "multih" (ARTM multi-h CPM, BASELINE configs[2]) or
-    "pcmfm"."""
+class CPMStream(_CPM, _Stream):
+    """The CPM chain as a stream (``wf_cpm_link_stream_chunk``): the detector state and the modulator phase are carried on
+    the device; PRBS + mapper depend on nothing, so only the front end and the detector of a chunk wait for the chunk before."""
 
-    STAGES = ("prbs", "map", "modulate", "-", "awgn", "mfbank", "viterbi", "count")
+    WAITS = (4, 2)
 
-    def __init__(self, nsym: int, sps: int = 8, waveform: str = "multih", spec=None, pn_degree: int = 23, warmup: int = 0,
-                 skip_head: int = 64, private_ctx: bool = False, fuse: int = 10, _no_workspace: bool = False,
-                 paired_templates: bool = True) -> None:
-        from .viterbi import cpm
+    def _chunk_rule(self, spt: int) -> str:
+        return (f"chunk_symbols must be a multiple of {spt} (one modulator tile) and of 128 and at least "
+                f"{4 * (spt + 48 + self.spec.D)}, with a configuration the one-kernel front end takes")
 
-        if waveform == "multih":
-            from .cpm.multih import freq_pulse_multih_irig
+    def _carry(self):
+        return _hip.zeros(_hip.WF_CPM_STREAM_STATE_BYTES // 8, "int64")
 
-            pulse, kind, spec = freq_pulse_multih_irig(sps), 1, spec or cpm.ARTM_16
-        elif waveform == "pcmfm":
-            from .cpm.pcmfm import freq_pulse_pcmfm
-
-            pulse, kind, spec = freq_pulse_pcmfm(sps), 2, spec or cpm.PCMFM_10
-        else:
-            raise ValueError(f"unknown waveform {waveform!r}")
-        self.nsym, self.sps, self.spec, self.waveform = int(nsym), int(sps), spec, waveform
-        self._ctx = _hip.new_ctx() if private_ctx else _hip.ctx()
-        _hip.check(_hip.lib().wf_ctx_forget_promises(self._ctx))    # (this link's tables may sit where a dead link's did: every promise is checked afresh)
-        self._owns_ctx = bool(private_ctx)
-        self._d_h = _hip.to_device(spec.mod_index)
-        self._d_pulse = _hip.to_device(np.asarray(pulse, dtype=np.float64))
-        templates = cpm.matched_filter_templates(pulse, sps, spec)
-        self._d_templates = _hip.to_device(templates)
-        # A symmetric alphabet makes the templates of a symbol pattern and of its negation exact conjugates (filter f and
-        # nfilt - 1 - f): the one-kernel front end then forms each pair of filters from four real sums (wf_cpm_link_config.fuse
-        # bit 6, which vouches for exactly this identity — checked here, bit for bit)
-        self.paired_templates = bool(paired_templates and templates.shape[1] in (4, 16) and np.array_equal(templates[:, ::-1, :], np.conj(templates)))
-        if self.paired_templates:
-            fuse = int(fuse) | 64
-        self._d_rot = _hip.to_device(cpm.rotation_table(spec))
-        cfg = _hip.CPMLinkConfig()
-        cfg.nsym, cfg.sps = self.nsym, self.sps
-        cfg.degree, cfg.mask, cfg.state, cfg.skip = pn_degree, generate_mask(pn_degree), (1 << pn_degree) - 1, 0
-        cfg.mapper_kind, cfg.det = kind, spec.c_config()
-        cfg.d_h, cfg.d_pulse, cfg.ntaps = self._d_h.data_ptr(), self._d_pulse.data_ptr(), int(np.asarray(pulse).size)
-        cfg.d_templates, cfg.d_rot_cs = self._d_templates.data_ptr(), self._d_rot.data_ptr()
-        cfg.sigma, cfg.seed, cfg.stream_id = 0.0, 1, 0
-        cfg.warmup, cfg.skip_head, cfg.event_slot, cfg.fuse = warmup, skip_head, -1, int(fuse)
-        self.cfg = cfg
-        if _no_workspace:        # (CPMStream: the one-shot workspace of a long stream is exactly what it avoids)
-            return
-        self.workspace_bytes = _hip.lib().wf_cpm_link_workspace_bytes(ctypes.byref(cfg))
-        if self.workspace_bytes < 0:
-            raise ValueError("invalid link configuration")
-        self.workspace = _hip.empty(self.workspace_bytes, "uint8")
-        self.counts = _hip.zeros(2, "int64")
-        self.compared = 0
-
-    def __del__(self):
-        try:
-            if getattr(self, "cfg", None) is not None and (self.cfg.fuse & 32) and getattr(self, "workspace", None) is not None:
-                _hip.lib().wf_link_join(self._ctx, _hip.stream())
-                _hip.torch().cuda.current_stream().synchronize()
-        except Exception:          # noqa: BLE001 — interpreter teardown
-            pass
-        if getattr(self, "_owns_ctx", False):
-            _hip.free_ctx(self._ctx)
-            self._owns_ctx = False
-
-    def layout(self) -> dict:
-        info = (ctypes.c_int64 * 8)()
-        _hip.check(_hip.lib().wf_cpm_link_layout(ctypes.byref(self.cfg), info))
-        keys = ("calls", "start0", "off_decisions", "off_syms", "off_signal", "one_kernel_front_end", "signal_len", "off_rows")
-        return dict(zip(keys, (int(v) for v in info)))
-
-    def reset_counts(self) -> None:
-        _hip.check(_hip.lib().wf_link_join(self._ctx, _hip.stream()))   # (fuse bit 5: counters of earlier blocks on the side stream)
-        self.counts.zero_()
-        self.compared = 0
-
-    def stage_ms(self, event_slot: int) -> dict[str, float]:
-        buf = (ctypes.c_float * len(self.STAGES))()
-        _hip.check(_hip.lib().wf_link_stage_ms(self._ctx, event_slot, buf))
-        return {k: float(v) for k, v in zip(self.STAGES, buf) if k != "-"}
-
-    def run_block(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0, skip_bits: int = 0, event_slot: int = -1) -> None:
-        """Queue one trial block; ``ebn0_db=None`` = no noise."""
-        from .viterbi.cpm import sigma_for_ebn0 as cpm_sigma
-
-        c = self.cfg
-        c.sigma = 0.0 if ebn0_db is None else cpm_sigma(ebn0_db, self.sps, self.spec.bits_per_symbol)
-        c.seed, c.stream_id, c.skip, c.event_slot = seed, stream_id, skip_bits, event_slot
-        m = ctypes.c_int64(0)
-        _hip.check(_hip.lib().wf_cpm_link_run(self._ctx, ctypes.byref(c), self.workspace.data_ptr(), self.workspace_bytes,
-                                              self.counts.data_ptr(), ctypes.byref(m), _hip.stream()))
-        self.compared += m.value
-
-    def result(self) -> tuple[int, int, int]:
-        """(symbol errors, bit errors, symbols compared), like :meth:`SOQPSKLink.result`."""
-        return SOQPSKLink.result(self)
-
-
-class CPMStream:
-    """The CPM link (:class:`CPMLink`) over a continuous stream of ``total_symbols`` symbols in chunks of
-    ``chunk_symbols`` detector calls (``wf_cpm_link_stream_chunk``): HBM use of one chunk, the detector state
-    and the modulator phase carried on the device, everything else re-generated as a halo.  Decisions and
-    error counts equal a one-shot :class:`CPMLink` over the whole stream."""
-
-    def __init__(self, total_symbols: int, chunk_symbols: int, sps: int = 8, **kw) -> None:
-        self._proto = CPMLink.__new__(CPMLink)
-        CPMLink.__init__(self._proto, int(total_symbols), sps, _no_workspace=True, **kw)
-        self.cfg, self._ctx, self.sps, self.spec = self._proto.cfg, self._proto._ctx, int(sps), self._proto.spec
-        self.total_symbols, self.chunk_symbols = int(total_symbols), int(chunk_symbols)
-        lib = _hip.lib()
-        nbytes = lib.wf_cpm_link_stream_workspace_bytes(ctypes.byref(self.cfg), self.chunk_symbols)
-        if nbytes < 0:
-            tl, spt, nt = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-            lib.wf_mod_tile_geometry(self.sps, self.cfg.ntaps, self.total_symbols, ctypes.byref(tl), ctypes.byref(spt), ctypes.byref(nt))
-            raise ValueError(f"chunk_symbols must be a multiple of {spt.value} (one modulator tile) and of 128 and at least "
-                             f"{4 * (spt.value + 48 + self.spec.D)}, with a configuration the one-kernel front end takes")
-        self.workspace_bytes = nbytes
-        self.workspace = _hip.empty(nbytes, "uint8")
-        self.state = _hip.zeros(_hip.WF_CPM_STREAM_STATE_BYTES // 8, "int64")
-        self.counts = _hip.zeros(2, "int64")
-        self.compared = 0
-        self.total_calls = self.chunk_info(0)["stream_calls"]
-        self.nchunks = -(-self.total_calls // self.chunk_symbols)
-
-    def reset(self) -> None:
-        self.state.zero_()
-        self.counts.zero_()
-        self.compared = 0
-
-    def chunk_info(self, c: int) -> dict:
-        info = (ctypes.c_int64 * 8)()
-        _hip.check(_hip.lib().wf_cpm_link_stream_layout(ctypes.byref(self.cfg), self.chunk_symbols, c, info))
-        keys = ("calls", "first_call", "off_decisions", "off_syms", "syms_origin", "stream_calls", "sym_per_tile", "off_rows")
-        return dict(zip(keys, (int(v) for v in info)))
-
-    def run_chunk(self, c: int, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> None:
-        from .viterbi.cpm import sigma_for_ebn0 as cpm_sigma
-
-        cfg = self.cfg
-        cfg.sigma = 0.0 if ebn0_db is None else cpm_sigma(ebn0_db, self.sps, self.spec.bits_per_symbol)
-        cfg.seed, cfg.stream_id, cfg.event_slot = seed, stream_id, -1
-        m = ctypes.c_int64(0)
-        _hip.check(_hip.lib().wf_cpm_link_stream_chunk(self._ctx, ctypes.byref(cfg), self.chunk_symbols, c, self.state.data_ptr(),
-                                                       self.workspace.data_ptr(), self.workspace_bytes, self.counts.data_ptr(),
-                                                       ctypes.byref(m), _hip.stream()))
-        self.compared += m.value
-
-    def run(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> tuple[int, int, int]:
-        self.reset()
-        for c in range(self.nchunks):
-            self.run_chunk(c, ebn0_db, seed, stream_id)
-        return self.result()
-
-    def run_pipelined(self, ebn0_db: float | None, seed: int = 1, stream_id: int = 0) -> tuple[int, int, int]:
-        """Like :meth:`run` with consecutive chunks alternating between two HIP streams, each with its own workspace and
-        library context (``wf_cpm_link_stream_chunk_phase``, as :meth:`SOQPSKStream.run_pipelined` does it): PRBS + mapper
-        depend on nothing, a chunk's front end waits for the previous chunk's front end (phase carry), its detector for
-        the previous chunk's detector (detector carry) — so the detector of chunk c runs beside the front end of chunk
-        c + 1.  Same decisions and counts as :meth:`run`."""
-        from .viterbi.cpm import sigma_for_ebn0 as cpm_sigma
-
-        torch = _hip.torch()
-        self.reset()
-        cfg = self.cfg
-        cfg.sigma = 0.0 if ebn0_db is None else cpm_sigma(ebn0_db, self.sps, self.spec.bits_per_symbol)
-        cfg.seed, cfg.stream_id, cfg.event_slot = seed, stream_id, -1
-        if getattr(self, "_ws2", None) is None:
-            self._ws2 = _hip.empty(self.workspace_bytes, "uint8")
-            self._ctx2 = _hip.new_ctx()
-            self._lanes = [torch.cuda.Stream(), torch.cuda.Stream()]
-        main = torch.cuda.current_stream()
-        for lane in self._lanes:
-            lane.wait_stream(main)                       # the carry block / counters were zeroed on the caller's stream
-        lib, m = _hip.lib(), ctypes.c_int64(0)
-        done = {4: None, 2: None}
-        for c in range(self.nchunks):
-            lane, ws, ctx = self._lanes[c & 1], (self.workspace, self._ws2)[c & 1], (self._ctx, self._ctx2)[c & 1]
-            with torch.cuda.stream(lane):
-                for part in (1, 4, 2):
-                    if part != 1 and done[part] is not None:
-                        lane.wait_event(done[part])
-                    _hip.check(lib.wf_cpm_link_stream_chunk_phase(ctx, ctypes.byref(cfg), self.chunk_symbols, c, self.state.data_ptr(),
-                                                                  ws.data_ptr(), self.workspace_bytes, self.counts.data_ptr(),
-                                                                  ctypes.byref(m), part, lane.cuda_stream))
-                    if part != 1:
-                        done[part] = torch.cuda.Event()
-                        done[part].record(lane)
-                self.compared += m.value
-        for lane in self._lanes:
-            main.wait_stream(lane)
-        from waveforms_amd import device as dev
-
-        _hip.check(lib.wf_ctx_check(self._ctx2, _hip.stream()))
-        late = dev.viterbi_unmerged(reset=True, ctx=self._ctx2)     # the first context's count is read by result()
-        if late:
-            dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-            raise RuntimeError(f"{late} detector chunk(s) were left unproven (the repairs are switched off on this context)")
-        return self.result()
-
-    def __del__(self):
-        if getattr(self, "_ctx2", None):
-            _hip.free_ctx(self._ctx2)
-            self._ctx2 = None
-
-    def result(self) -> tuple[int, int, int]:
-        """(symbol errors, bit errors, symbols compared), like :meth:`SOQPSKLink.result`."""
-        return SOQPSKLink.result(self)
+    def _total_calls(self) -> int:
+        return self.chunk_info(0)["stream_calls"]

@@ -60,6 +60,14 @@ class SOQPSKTrellisDetector:
             _hip.free_ctx(self._ctx)
             self._ctx = None
 
+    def _open(self) -> None:
+        """The batch forms' private context (the proof counter lives in the wf_ctx: with its own, the detector's
+        read-with-reset cannot disturb a SOQPSKLink or a BER sweep on the default one)."""
+        if self._ctx is None:
+            from waveforms_amd import _hip
+
+            self._ctx = _hip.new_ctx()
+
     # ------------------------------------------------------------------ the reference's public state arrays
     # algorithm.py:25-42 gives every instance ``bi_history`` float64[branches_per_column, length], ``metrics``
     # float64[states, length] and ``path`` uint8[states, length]; iteration() (:57-88) rewrites them on every call.  Here the
@@ -186,24 +194,17 @@ class SOQPSKTrellisDetector:
         # The kernel is chunk-parallel; every launch proves on the device that each chunk started from bitwise the
         # state its predecessor ended with and runs the chunks that did not again from the true state, cascading
         # where needed (csrc/wf_viterbi.hip: viterbi_fixup_kernel) — the output is the sequential detector's
-        # (algorithm.py:44-101) whatever `warmup` is.  The proof counter lives in the wf_ctx: the detector owns a
-        # private context so that its read-with-reset cannot disturb a SOQPSKLink or a BER sweep on the default one.
-        if self._ctx is None:
-            self._ctx = _hip.new_ctx()
+        # (algorithm.py:44-101) whatever `warmup` is.  (Repairs switched off — tests of the proof — is the one way this
+        # call can raise behind a launch: the carry is put back then, dev.proven_carry.)
+        self._open()
         n = int(mf_rows.shape[0])
         # the trellis as it stands NOW (iteration() follows a swap of det.fsm the same way; algorithm.py:62 reads self.fsm per call)
         if self.fsm.trellis is not SOQPSKTrellis4x2DiffEncoded and self.fsm.trellis is not SOQPSKTrellis4x2:
             raise ValueError("SOQPSKTrellisDetector serves the two 4-state, 2-column SOQPSK trellises (state_exp_term has four entries)")
         self.differential = self.fsm.trellis is SOQPSKTrellis4x2DiffEncoded
-        # (repairs switched off — tests of the proof — is the one way this call can raise behind a launch: the carry is put back then)
-        keep = self._d_carry.clone() if _hip.get_option(self._ctx, _hip.WF_OPT_DET_REPAIR) else None
-        out = (dev.viterbi_detect(mf_rows, self.differential, warmup, self._d_carry, ctx=self._ctx) if L == 2 else
-               dev.viterbi_detect_window(mf_rows, L, self.differential, warmup, self._d_carry, ctx=self._ctx))
-        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-        if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
-            if keep is not None:
-                self._d_carry.copy_(keep)
-            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+        with dev.proven_carry(self._d_carry, self._ctx):
+            out = (dev.viterbi_detect(mf_rows, self.differential, warmup, self._d_carry, ctx=self._ctx) if L == 2 else
+                   dev.viterbi_detect_window(mf_rows, L, self.differential, warmup, self._d_carry, ctx=self._ctx))
         self.i += n                         # like iteration(): one call per row, state carried
         return out
 
@@ -218,17 +219,13 @@ class SOQPSKTrellisDetector:
         reference's metric, not those of ``detect`` (length 2): they can have MORE bit errors; the LLRs are for an
         FEC decoder.  Each call is a fresh burst (free start, free end): ``self.i``, the batch carry and the
         per-symbol state are left untouched, and it can be mixed with either API."""
-        from waveforms_amd import _hip
         from waveforms_amd import device as dev
 
         if self.fsm.trellis is not SOQPSKTrellis4x2DiffEncoded and self.fsm.trellis is not SOQPSKTrellis4x2:
             raise ValueError("SOQPSKTrellisDetector serves the two 4-state, 2-column SOQPSK trellises (state_exp_term has four entries)")
-        if self._ctx is None:
-            self._ctx = _hip.new_ctx()
+        self._open()
         out = dev.viterbi_soft(mf_rows, self.fsm.trellis is SOQPSKTrellis4x2DiffEncoded, warmup, 48, ctx=self._ctx)
-        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-        if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
-            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+        dev.require_proven(self._ctx)
         return out
 
     def detect_soft(self, mf_rows: NDArray[np.complex128], warmup: int = 0):

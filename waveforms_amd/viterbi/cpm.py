@@ -190,15 +190,21 @@ class CPMTrellisDetector:
             _hip.free_ctx(self._ctx)
             self._ctx = None
 
+    def _open(self) -> None:
+        """The detector's private context (own proof counter, like SOQPSKTrellisDetector), rotation table and carry."""
+        if self._ctx is None:
+            from waveforms_amd import _hip
+
+            self._ctx = _hip.new_ctx()
+            self._d_rot = _hip.to_device(rotation_table(self.spec))
+            self._d_state = _hip.zeros(_hip.WF_CPM_STATE_BYTES // 8, "int64")
+
     def detect_device(self, rows, warmup: int = 0):
         """``rows``: float64[n, nfilt, 2] device tensor -> uint8[n] device tensor (entry k = the
         decision of call k; entries of calls before the D-th of the burst are 0)."""
         from waveforms_amd import _hip, device as dev
 
-        if self._ctx is None:
-            self._ctx = _hip.new_ctx()          # private proof counter, like SOQPSKTrellisDetector
-            self._d_rot = _hip.to_device(rotation_table(self.spec))
-            self._d_state = _hip.zeros(_hip.WF_CPM_STATE_BYTES // 8, "int64")
+        self._open()
         n = int(rows.shape[0])
         if tuple(rows.shape[1:]) != (self.spec.nfilt, 2):
             raise ValueError(f"rows must be [n, {self.spec.nfilt}, 2] float64")
@@ -206,14 +212,9 @@ class CPMTrellisDetector:
         # (chunk-parallel; chunks that miss their warm-up are repaired on the device, cascading where needed: the
         #  decisions are the sequential detector's whatever `warmup` is — it only sets how many chunks get repaired)
         # (repairs switched off — tests of the proof — is the one way this call can raise behind a launch: the carry is put back then)
-        keep = self._d_state.clone() if _hip.get_option(self._ctx, _hip.WF_OPT_DET_REPAIR) else None
-        _hip.check(_hip.lib().wf_cpm_viterbi_detect(self._ctx, ctypes.byref(self._cfg), _hip.ptr(self._d_rot), _hip.ptr(rows), n, int(warmup),
-                                                    _hip.ptr(out), _hip.ptr(self._d_state), _hip.stream()))
-        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-        if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
-            if keep is not None:
-                self._d_state.copy_(keep)
-            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+        with dev.proven_carry(self._d_state, self._ctx):
+            _hip.check(_hip.lib().wf_cpm_viterbi_detect(self._ctx, ctypes.byref(self._cfg), _hip.ptr(self._d_rot), _hip.ptr(rows), n, int(warmup),
+                                                        _hip.ptr(out), _hip.ptr(self._d_state), _hip.stream()))
         return out[:n]
 
     def detect_soft_device(self, rows, first_call: int = 0, warmup: int = 0, apriori=None, apriori_scale: float = 1.0):
@@ -234,17 +235,12 @@ class CPMTrellisDetector:
             raise ValueError(f"the full-phase trellis of {self.spec} has {spec.nstates} states: the soft output serves up to 64")
         if tuple(rows.shape[1:]) != (self.spec.nfilt, 2):
             raise ValueError(f"rows must be [n, {self.spec.nfilt}, 2] float64")
-        if self._ctx is None:
-            self._ctx = _hip.new_ctx()
-            self._d_rot = _hip.to_device(rotation_table(self.spec))
-            self._d_state = _hip.zeros(_hip.WF_CPM_STATE_BYTES // 8, "int64")
+        self._open()
         if apriori is None:
             out = dev.cpm_soft(rows, spec, first_call, warmup, ctx=self._ctx, d_rot=self._d_rot)
         else:
             out = dev.cpm_soft_apriori(rows, spec, apriori, apriori_scale, first_call, warmup, ctx=self._ctx, d_rot=self._d_rot)
-        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-        if unproven:        # only with the context's WF_OPT_DET_REPAIR option switched off (tests of the proof itself)
-            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
+        dev.require_proven(self._ctx)
         return out
 
     def detect_soft(self, rows, first_call: int = 0, warmup: int = 0, apriori=None, apriori_scale: float = 1.0):
@@ -277,22 +273,18 @@ class CPMTrellisDetector:
 
         r = np.ascontiguousarray(received, dtype=np.complex128).ravel()
         t = np.ascontiguousarray(templates, dtype=np.complex128)
-        if self._ctx is None:
-            self._ctx = _hip.new_ctx()
-            self._d_rot = _hip.to_device(rotation_table(self.spec))
-            self._d_state = _hip.zeros(_hip.WF_CPM_STATE_BYTES // 8, "int64")
+        self._open()
         d_r, d_t = _hip.to_device(r), _hip.to_device(t)
         out = _hip.zeros(int(ncalls) + 16, "uint8")
-        rc = _hip.lib().wf_cpm_viterbi_detect_samples(self._ctx, ctypes.byref(self._cfg), _hip.ptr(self._d_rot), _hip.ptr(d_t), int(t.shape[0]),
-                                                      int(t.shape[1]), int(t.shape[2]), _hip.ptr(d_r), int(r.size), int(start0), int(sps),
-                                                      int(ncalls), int(warmup), _hip.ptr(out), _hip.ptr(self._d_state), _hip.stream())
-        self.samples_form = rc == 0
+        with dev.proven_carry(self._d_state, self._ctx):   # (a declined launch, rc 1, queued nothing: the check behind it finds nothing)
+            rc = _hip.lib().wf_cpm_viterbi_detect_samples(self._ctx, ctypes.byref(self._cfg), _hip.ptr(self._d_rot), _hip.ptr(d_t), int(t.shape[0]),
+                                                          int(t.shape[1]), int(t.shape[2]), _hip.ptr(d_r), int(r.size), int(start0), int(sps),
+                                                          int(ncalls), int(warmup), _hip.ptr(out), _hip.ptr(self._d_state), _hip.stream())
+            self.samples_form = rc == 0
+            if rc != 1:
+                _hip.check(rc)
         if rc == 1:         # not this launch's configuration: rows, then the detector over them
             return self.detect(_hip.to_host(dev.cpm_mf_rows(d_r, d_t, int(start0), int(sps), int(ncalls)), complex_pairs=True), warmup)
-        _hip.check(rc)
-        unproven = dev.viterbi_unmerged(reset=True, ctx=self._ctx)
-        if unproven:
-            raise RuntimeError(f"{unproven} detector chunk(s) were left unproven (the repairs are switched off on this context)")
         dec = _hip.to_host(out[:int(ncalls)])
         lo = max(self.spec.D - 1 - self.i, 0)
         self.i += int(ncalls)
