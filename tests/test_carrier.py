@@ -259,22 +259,23 @@ def _counters(dev, handle):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ebn0", [0.0, 10.0])
-def test_soft_branch_bitwise_on_oracle_rows(oracle, ctx, ebn0):
+@pytest.mark.parametrize("ebn0,differential", [pytest.param(0.0, True, id="0.0"), pytest.param(10.0, True, id="10.0"),
+                                               pytest.param(0.0, False, id="0.0-coherent"), pytest.param(10.0, False, id="10.0-coherent")])
+def test_soft_branch_bitwise_on_oracle_rows(oracle, ctx, ebn0, differential):
     """20 001 rows in chunks of 64 (313 chunks): λ and bits bitwise wf_viterbi4_soft's, the branch exactly the host statement's,
-    with the default warm-up and through the repairs of a 2-row warm-up."""
+    with the default warm-up and through the repairs of a 2-row warm-up, on both trellises."""
     from waveforms_amd import _hip
     from waveforms_amd import device as dev
 
     rows = _pt_rows(oracle, 20_002, ebn0)[:20_001]
-    want_llr, want_bits, want_branch = C.map_branch_host(rows)
+    want_llr, want_bits, want_branch = C.map_branch_host(rows, differential)
     _hip.set_option(ctx, _hip.WF_OPT_SOFT_CHUNK_CALLS, 64)
     d_rows = _hip.to_device(rows)
     _counters(dev, ctx)
     for warmup in (0, 2):
-        ref_llr, ref_bits = dev.viterbi_soft(d_rows, True, warmup, 48, ctx=ctx)
+        ref_llr, ref_bits = dev.viterbi_soft(d_rows, differential, warmup, 48, ctx=ctx)
         _counters(dev, ctx)
-        llr, bits, branch = dev.viterbi_soft_branch(d_rows, True, warmup, ctx=ctx)
+        llr, bits, branch = dev.viterbi_soft_branch(d_rows, differential, warmup, ctx=ctx)
         unproven, repaired = _counters(dev, ctx)
         assert unproven == 0
         assert np.array_equal(_hip.to_host(llr).view(np.uint64), _hip.to_host(ref_llr).view(np.uint64))
@@ -306,13 +307,14 @@ def test_soft_branch_short_bursts_and_exact_ties(ctx, differential):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("window", [64, 256])
+@pytest.mark.parametrize("window", [64, 256, 1024, 8192])
 def test_carrier_stat_bitwise(ctx, window):
+    """The wide windows take 16 and 128 trips of the lane loop (8192 is the widest the header allows)."""
     from waveforms_amd import _hip
     from waveforms_amd import device as dev
 
     rng = np.random.default_rng(window)
-    for n in (1, window - 1, window, 5 * window + 77, 2000):
+    for n in (1, window - 1, window, 5 * window + 77, 2000) if window <= 256 else (1, window - 1, window + 1, 2 * window + 77):
         rows = rng.standard_normal((n, 3)) + 1j * rng.standard_normal((n, 3))
         rows[0] = 0.0                                     # signed zeros among the terms
         branch = rng.integers(0, 8, n).astype(np.uint8)
@@ -327,13 +329,16 @@ def test_carrier_stat_bitwise(ctx, window):
 @pytest.mark.parametrize("H", [1, 8])
 def test_carrier_track_on_the_devices_own_statistics(oracle, ctx, H, span):
     """choice exact wherever the two best X differ; phase within 8 * 2^-52 * max(1, |phase|) * nwin of the host statement: each of
-    the nwin accumulated terms carries a few ulp of atan2 and of the wrap, and the sums add one rounding each."""
+    the nwin accumulated terms carries a few ulp of atan2 and of the wrap, and the sums add one rounding each.  66 000 rows in
+    windows of 64 are 1032 windows: the tracker's 1024 threads then own up to two windows each (tests/test_carrier_edges.py)."""
     from waveforms_amd import _hip
     from waveforms_amd import device as dev
 
     rows = _rot(_pt_rows(oracle, 4097, 8.0), 65.0, 0.03)
-    for n, window in ((rows.shape[0], 64), (rows.shape[0], 256), (200, 256)):       # the last one: nwin = 1
-        d_rows = _hip.to_device(rows[:n])
+    long_rows = _rot(_pt_rows(oracle, 66_001, 8.0), 65.0, 0.03)
+    assert long_rows.shape[0] == 66_000
+    for z, n, window in ((rows, rows.shape[0], 64), (rows, rows.shape[0], 256), (rows, 200, 256), (long_rows, 66_000, 64)):       # the third one: nwin = 1
+        d_rows = _hip.to_device(z[:n])
         nwin = -(-n // window)
         stat = _hip.empty((H, nwin, 2), "float64")
         for h in range(H):
@@ -346,7 +351,14 @@ def test_carrier_track_on_the_devices_own_statistics(oracle, ctx, H, span):
         clear = np.ones(nwin, dtype=bool) if H == 1 else xs[0] != xs[1]
         assert clear.all() and np.array_equal(choice, want_choice)
         bound = 8.0 * EPS * np.maximum(1.0, np.abs(want_phase)) * nwin
+        print(f"H {H}, span {span}, {n} rows, W {window}: max |device - host| / bound = {(np.abs(phase - want_phase) / bound).max():.3g}")
         assert (np.abs(phase - want_phase) <= bound).all(), (np.abs(phase - want_phase).max(), bound.min())
+        if nwin > 1024:
+            # no wrapped step of the host's ψ comes within 0.25 rad of ±π/2, where an ulp of atan2 could turn it the other way
+            # (span 1: the phases are the u_w, whose steps are the wrapped steps; 1.17 rad at H = 1 and 1.24 at H = 8 on these rows)
+            margin = math.pi / 2.0 - np.abs(np.diff(C.carrier_track_host(st, 1)[0])).max()
+            print(f"   wrap margin {margin:.3f} rad")
+            assert margin >= 0.25, margin
         if H == 8 and window == 256 and n > 256:
             assert np.abs(_wrap_deg(np.degrees(want_phase[2:-2]) - 65.0 - 0.03 * 360.0 * (np.arange(nwin)[2:-2] + 0.5))).max() < 8.0
 
@@ -369,11 +381,23 @@ def test_rows_derotate_against_numpy(ctx):
     rows = 3.0 * (rng.standard_normal((n, 3)) + 1j * rng.standard_normal((n, 3)))
     phase = np.cumsum(rng.uniform(-0.4, 0.4, nwin)) + 50.0
     d_rows = _hip.to_device(rows)
-    for ph, phase0, w in ((phase, 0.0, window), (phase, -1.25, window), (None, 2.5, 64), (phase[:1], 0.3, 1024), (phase[:4], 0.0, 256)):
+    for ph, phase0, w in ((phase, 0.0, window), (phase, -1.25, window), (None, 2.5, 64), (phase[:1], 0.3, 1024), (phase[:4], 0.0, 256),
+                          (phase[:3], 0.0, 64)):
         want = C.derotate_host(rows, w, ph, phase0)
         ang = phase0 + (0.0 if ph is None else C.interpolate_phase_host(n, w, ph)) + np.zeros(n)
         got = _hip.to_host(dev.rows_derotate(d_rows, w, None if ph is None else _hip.to_device(ph), phase0, ctx=ctx), True)
         assert (np.abs(got - want) <= _rot_bound(rows, ang[:, None])).all(), np.abs(got - want).max()
+    # fewer phases than the rows have windows (3 of 16; `got` is that case): the trajectory is held flat behind the last centre,
+    # 2 * 64 + 31.5, so the rows from 160 on turn by phase[2] itself
+    assert (ang[160:] == phase[2]).all() and ang[159] != phase[2]
+    flat = rows[160:] * (math.cos(-phase[2]) + 1j * math.sin(-phase[2]))
+    assert (np.abs(got[160:] - flat) <= _rot_bound(rows[160:], phase[2])).all()
+    # the widest window, two phases over one window and 100 rows: flat to 4095.5, then the line towards the second centre
+    wide = 3.0 * (rng.standard_normal((8192 + 100, 3)) + 1j * rng.standard_normal((8192 + 100, 3)))
+    ang = C.interpolate_phase_host(wide.shape[0], 8192, phase[:2])
+    assert (ang[:4096] == phase[0]).all() and ang[-1] == phase[0] + ((8291 - 4095.5) / 8192) * (phase[1] - phase[0])
+    got = _hip.to_host(dev.rows_derotate(_hip.to_device(wide), 8192, _hip.to_device(phase[:2]), 0.0, ctx=ctx), True)
+    assert (np.abs(got - C.derotate_host(wide, 8192, phase[:2])) <= _rot_bound(wide, ang[:, None])).all()
     # flat ends: the rows in front of the first centre and behind the last one turn by phase[0] and phase[-1]
     ang = C.interpolate_phase_host(n, window, phase)
     assert (ang[:32] == phase[0]).all() and (ang[(nwin - 1) * window + 32:] == phase[-1]).all()
