@@ -62,7 +62,7 @@ int wf_ctx_check(wf_ctx *ctx, void *stream);
 /* Per-context options: everything that tunes or instruments the library is a field of the context set through
  * this call — the library reads no environment variable and keeps no process-wide switch (the reference's objects
  * carry their own configuration the same way: SOQPSKTrellisDetector(length, differantial_encoding),
- * waveforms/viterbi/algorithm.py:19-42).  Values are int64; 0 is every option's default.  Unknown key or a value
+ * waveforms/viterbi/algorithm.py:19-42).  Values are int64; 0 is every option's default but WF_OPT_PIPE_RESERVE_CUS's.  Unknown key or a value
  * outside the option's range: WF_ERR_VALUE.  Takes effect for calls issued afterwards on this context. */
 typedef enum {
     WF_OPT_CPM_FORM = 0,          /* generic CPM detector: 0 choose by estimated time, 1 row form, 2 lane form (where compiled in) */
@@ -73,12 +73,15 @@ typedef enum {
                                    * differs in wf_viterbi4_unmerged (an internal-consistency check; always 0) */
     WF_OPT_ITERATION_SERVER = 4,  /* wf_viterbi4_iteration_host: 0 persistent server, 1 one launch + synchronise per call */
     WF_OPT_MCB_TAIL_PERMILLE = 5, /* one-kernel front end: resident-slot-fulls of tail tiles x 1000; 0 = default, -1 = none */
-    WF_OPT_PIPE_RESERVE_CUS = 6,  /* pipelined SOQPSK link (wf_link_config.fuse bit 5), a measured alternative that is NOT the default
-                                   * (profiles/r06_ab_prologue_ahead_cu_mask.log: 0.457 ms per block as shipped, 0.474 with -1, 0.50 with 8):
-                                   * N >= 1: each block's prologue (PRBS + precoder, carry kernels) on a stream of its own beside the
-                                   * previous block's front end, the front-end kernel on a stream whose CU mask leaves N compute units
-                                   * free; -1: the same without a mask; 0: front end and prologue on the caller's stream.  Set before
-                                   * the context's first pipelined block. */
+    WF_OPT_PIPE_RESERVE_CUS = 6,  /* pipelined SOQPSK link (wf_link_config.fuse bit 5): the order of a block's kernels.  A context starts with -1.
+                                   * N >= 1: each block's prologue (PRBS + precoder, carry kernels) beside the previous block's front end
+                                   * (on the caller's stream; on a stream of the library's for a caller on the NULL stream), the front-end
+                                   * kernel on a stream whose CU mask leaves N compute units free, launched behind the previous block's
+                                   * detector; -1: the same without a mask for the forms it was measured faster for — the short
+                                   * (pulse-truncation) bank: 0.435 against 0.459 ms per block at 8 samples per symbol, 0.564 against 0.591
+                                   * at 10 — and the order of 0 for the long (PAM) bank (0.72 against 0.654 ms: profiles/order_ab_headline.log,
+                                   * order_ab_others.log); 0: front end and prologue on the caller's stream, the prologue between two
+                                   * front ends.  Set before the context's first pipelined block. */
     WF_OPT_CPM_SAMPLES_MIN_CALLS = 7, /* wf_cpm_viterbi_detect_samples / wf_cpm_link_config.fuse bit 7, 16-state lane form: shortest burst (calls) that
                                    * takes the samples form; 0 = the library's 6e6 (below it rows + the row form are faster: one lane per chunk leaves
                                    * most of a short burst's chunks to warm-up), otherwise >= 4096 — tests run the form on bursts an oracle can follow */

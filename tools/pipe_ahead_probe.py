@@ -24,7 +24,7 @@ def main():
     wu = soqpsk_warmup_param(operating_point_warmup("soqpsk", 10.0))
     for own_stream in (False, True):
         for rsv in [int(v) for v in a.reserve.split(",")]:
-            _hip.set_default_option(_hip.WF_OPT_PIPE_RESERVE_CUS, rsv)
+            _hip.set_default_option(_hip.WF_OPT_PIPE_RESERVE_CUS, rsv, literal=True)
             ctxm = torch.cuda.stream(torch.cuda.Stream()) if own_stream else torch.cuda.stream(torch.cuda.current_stream())
             with ctxm:
                 link = SOQPSKLink(a.nsym, a.sps, detector=a.detector, fuse=47, private_ctx=True, warmup=wu)

@@ -231,6 +231,9 @@ def check(rc: int) -> None:
 # Options (wf_option) every context this module creates starts with, and the per-device default contexts are switched
 # to: the library itself has no process-wide switch (include/wfhip.h: wf_ctx_set_option), so a caller that wants one
 # behaviour everywhere — the tests' "run this module in the lane form" fixture — says so here.
+# LIBRARY_DEFAULT_OPTIONS: what wf_ctx_create itself sets — everything 0 but the order of the pipelined SOQPSK link's kernels;
+# default_options holds what differs from it.
+LIBRARY_DEFAULT_OPTIONS = {WF_OPT_PIPE_RESERVE_CUS: -1}
 default_options: dict[int, int] = {}
 
 
@@ -244,10 +247,14 @@ def get_option(handle, key: int) -> int:
     return int(v.value)
 
 
-def set_default_option(key: int, value: int) -> None:
-    """Record ``key = value`` for every context created from now on and apply it to the live default contexts."""
+def set_default_option(key: int, value: int, literal: bool = False) -> None:
+    """Record ``key = value`` for every context created from now on and apply it to the live default contexts.  ``value`` 0 puts
+    the option back to what the library starts a context with (LIBRARY_DEFAULT_OPTIONS: not 0 for every key) — the way scopes
+    of options undo themselves; ``literal``: 0 means the value 0 (the --opt flags of bench.py and the tools)."""
     with _lock:
-        if int(value) == 0:
+        if int(value) == 0 and not literal:
+            value = LIBRARY_DEFAULT_OPTIONS.get(int(key), 0)
+        if int(value) == LIBRARY_DEFAULT_OPTIONS.get(int(key), 0):
             default_options.pop(int(key), None)
         else:
             default_options[int(key)] = int(value)
@@ -259,7 +266,7 @@ def apply_option_args(pairs) -> None:
     """``["cpm_form=1", "cpm_chunk_calls=320"]`` (the --opt flags of bench.py and the tools) -> set_default_option."""
     for kv in pairs or []:
         key, _, val = str(kv).partition("=")
-        set_default_option(globals()["WF_OPT_" + key.strip().upper()], int(val))
+        set_default_option(globals()["WF_OPT_" + key.strip().upper()], int(val), literal=True)
 
 
 def ctx() -> int:

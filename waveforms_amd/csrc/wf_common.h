@@ -50,7 +50,7 @@ struct wf_lfsr_tables {
 struct wf_ctx {
     int device = 0;
     int cus = 256;                       // compute units of the device (hipDeviceAttributeMultiprocessorCount at creation)
-    int64_t opt[WF_OPT_COUNT] = {0};     // wf_ctx_set_option: 0 = default for every key
+    int64_t opt[WF_OPT_COUNT] = {0};     // wf_ctx_set_option: 0 = default for every key but WF_OPT_PIPE_RESERVE_CUS (wf_ctx_create: -1)
     // chained-scan scratch: [0] ticket counter (as u64), [1..] tile descriptors
     uint64_t *d_scan = nullptr;
     size_t scan_words = 0;
@@ -78,10 +78,16 @@ struct wf_ctx {
     // of the last block that used set s; wf_link_join / wf_ctx_check make the caller's stream wait for both.
     void *pipe_stream = nullptr;
     void *pipe_stream2 = nullptr;        // the CPM links alternate consecutive blocks' back ends between two side streams (wf_cpm_link_run)
-    // the pipelined SOQPSK link (wf_link_run): the NEXT block's prologue (PRBS + precoder, tile sums, tile scan) on pipe_pro while
-    // this block's front end runs on pipe_main, whose CU mask keeps a few compute units free for those small kernels
+    // the pipelined SOQPSK link (wf_link_run): the NEXT block's prologue (PRBS + precoder, tile sums, tile scan) on the caller's
+    // stream (pipe_pro for a caller on the NULL stream) while this block's front end runs on pipe_main (CU-masked on request)
     void *pipe_pro = nullptr, *pipe_main = nullptr;
-    hipEvent_t pipe_call = nullptr, pipe_pro_done = nullptr;
+    hipEvent_t pipe_pro_done = nullptr;
+    // ... and the order of two queues: recorded on the back stream between its wait for a block's front end and that block's detector
+    // launch; the NEXT block's front end waits for it, so the detector's launch packet is always the older one (wf_link_run)
+    hipEvent_t pipe_back_go = nullptr;
+    bool pipe_back_go_valid = false;
+    bool pipe_front_recorded = false;    // a pipelined block has been queued: pipe_front stands behind its front end ...
+    bool pipe_front_on_main = false;     // ... on pipe_main: link_pipe_select orders a block of the other kind behind it
     hipEvent_t pipe_front = nullptr, pipe_done[2] = {nullptr, nullptr};
     bool pipe_done_valid[2] = {false, false};
     int pipe_set = 0;

@@ -28,6 +28,7 @@ extern "C" int wf_ctx_create(int device, wf_ctx **out)
     c->device = device;
     (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device);
     if (c->cus < 1) c->cus = 256;
+    c->opt[WF_OPT_PIPE_RESERVE_CUS] = -1;      // the one option that does not start at 0 (include/wfhip.h)
     WF_HIP(hipMalloc(&c->d_fault, 64));
     WF_HIP(hipMemset(c->d_fault, 0, 64));
     WF_HIP(hipHostMalloc(&c->h_fault, 64, hipHostMallocDefault));
@@ -63,8 +64,8 @@ extern "C" int wf_ctx_destroy(wf_ctx *c)
     if (c->pipe_stream2) (void)hipStreamDestroy(static_cast<hipStream_t>(c->pipe_stream2));
     if (c->pipe_pro) (void)hipStreamDestroy(static_cast<hipStream_t>(c->pipe_pro));
     if (c->pipe_main) (void)hipStreamDestroy(static_cast<hipStream_t>(c->pipe_main));
-    if (c->pipe_call) (void)hipEventDestroy(c->pipe_call);
     if (c->pipe_pro_done) (void)hipEventDestroy(c->pipe_pro_done);
+    if (c->pipe_back_go) (void)hipEventDestroy(c->pipe_back_go);
     if (c->d_scan) (void)hipFree(c->d_scan);
     if (c->d_fsm_scratch) (void)hipFree(c->d_fsm_scratch);
     if (c->d_mod_scratch) (void)hipFree(c->d_mod_scratch);

@@ -27,8 +27,15 @@ static inline int link_pipe_open(wf_ctx *ctx, const char *fn, int64_t set_bytes,
 }
 
 // Step 2: this block's set; `waiter`, the stream the block starts on, waits for the back end of the block that used it two blocks ago.
-static inline int link_pipe_select(wf_ctx *ctx, int64_t set_bytes, char *&w, void *waiter)
+// `on_main`: this block's front end goes to the context's pipe_main (wf_link_run with the prologue ahead) and its carries to scratch
+// slot pipe_set; every other pipelined block runs its front end on the caller's stream with the one set of carries, which is slot 0's
+// words.  One context may serve both kinds in turn (links of different forms share the per-device context), and the two streams
+// do not order themselves: where the kind changes, `waiter` also waits for the previous block's front end (pipe_front).
+static inline int link_pipe_select(wf_ctx *ctx, int64_t set_bytes, char *&w, void *waiter, bool on_main = false)
 {
+    if (ctx->pipe_front_on_main != on_main && ctx->pipe_front_recorded) WF_HIP(hipStreamWaitEvent(wf_stream(waiter), ctx->pipe_front, 0));
+    ctx->pipe_front_on_main = on_main;
+    ctx->pipe_front_recorded = true;      // (every pipelined block records it behind its front end, further down the same call)
     w += (int64_t)ctx->pipe_set * set_bytes;
     if (ctx->pipe_done_valid[ctx->pipe_set]) WF_HIP(hipStreamWaitEvent(wf_stream(waiter), ctx->pipe_done[ctx->pipe_set], 0));
     return WF_OK;

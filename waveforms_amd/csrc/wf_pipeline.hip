@@ -171,37 +171,42 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
     if (piped) {
         const int64_t set_bytes = round_up((int64_t)L.total, 256);
         if ((rc = link_pipe_open(ctx, "wf_link_run", set_bytes, workspace_bytes, false))) return rc;
-        // Round 6: three library streams per pipelined link.  A block's PROLOGUE (PRBS + precoder, tile sums, tile scan: ~60 us of
-        // small kernels that used to sit between two front ends on the caller's stream) goes to pipe_pro and depends only on its
-        // set of intermediates being free — the host queues block k + 1 while block k's front end runs, so it runs BESIDE that front
-        // end; the front-end kernel goes to pipe_main (CU-masked: see link_masked_stream) behind its own prologue and the previous
-        // front end; detector + count to pipe_stream as before.  The carries live in one of two scratch sets (slot = the set).
-        // MEASURED AND NOT KEPT as the default (option WF_OPT_PIPE_RESERVE_CUS, 0 = off): the front ends then follow each other
-        // with 12 us between them, but each runs 404 - 475 us instead of 380 — what the detector and the prologue kernels take from
-        // it when they run beside it is what they cost between two front ends (the chip's work is conserved: the front end fills
-        // every SIMD's registers and every CU's LDS, nothing co-resides with it) — 0.457 ms per block as shipped, 0.474 without a
-        // mask, 0.50 with 8 CUs masked (profiles/r06_ab_prologue_ahead_cu_mask.log, r06_timeline_soqpsk_prologue_ahead.txt).
+        // The prologue-ahead order.  A block's PROLOGUE (PRBS + precoder, tile sums, tile scan: ~60 us of small kernels that otherwise
+        // sit between two front ends) depends only on its set of intermediates being free: the host queues block k + 1 while block
+        // k's front end runs, so it runs BESIDE that front end — on the caller's stream, or on pipe_pro for a caller on the NULL
+        // stream (which would wait for the front end in flight).  The front-end kernel goes to pipe_main (CU-masked for N >= 1: see
+        // link_masked_stream) behind its own prologue, the previous front end and the previous block's pipe_back_go (below);
+        // detector + count to pipe_stream as in the other order.  The carries live in one of two scratch sets (slot = the set).
+        // Without pipe_back_go the dispatcher served whichever of two queues got there first: a detector placed after the next front
+        // end had filled every SIMD waited for two front-end workgroups to leave a CU at once and ran 461 us instead of 109 (0.474 ms
+        // per block against 0.457 in the other order: profiles/r06_ab_prologue_ahead_cu_mask.log, r06_timeline_soqpsk_prologue_ahead.txt).
+        // With it the detector starts at least 7 us (median 17) before the next front end in every period (profiles/order_timeline_soqpsk.txt).
+        // WF_OPT_PIPE_RESERVE_CUS: 0 = the other order (prologue between two front ends on the caller's stream), N >= 1 = this one
+        // with N CUs masked, -1 (what a context starts with) = this one without a mask WHERE IT WAS MEASURED FASTER: the short
+        // (pulse-truncation) bank — 0.435 against 0.459 ms per block at 8 samples per symbol, 0.564 against 0.591 at 10 — and the
+        // other order for the long (PAM) bank, whose front end leaves the small kernels less (0.72 against 0.654 and 0.905 against
+        // 0.851: profiles/order_ab_headline.log, order_ab_others.log).
         const int64_t rsv = ctx->opt[WF_OPT_PIPE_RESERVE_CUS];
-        ahead = rsv != 0;
+        ahead = rsv > 0 || (rsv < 0 && cfg->mf_ntaps == cfg->sps + 1);
         if (ahead) {
             if (!ctx->pipe_pro) {
                 hipStream_t sp;
                 WF_HIP(hipStreamCreateWithFlags(&sp, hipStreamDefault));       // (default flags: ordered behind what the caller queued on the NULL stream)
                 ctx->pipe_pro = sp;
+            }
+            if (!ctx->pipe_main) {
                 ctx->pipe_main = link_masked_stream(ctx, rsv < 0 ? 0 : (int)rsv);
                 WF_REQUIRE(ctx->pipe_main != nullptr, "wf_link_run: could not create the front end's stream");
-                WF_HIP(hipEventCreateWithFlags(&ctx->pipe_call, hipEventDisableTiming));
-                WF_HIP(hipEventCreateWithFlags(&ctx->pipe_pro_done, hipEventDisableTiming));
             }
-            s_pro = ctx->pipe_pro;
+            if (!ctx->pipe_pro_done) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_pro_done, hipEventDisableTiming));
+            if (!ctx->pipe_back_go) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_back_go, hipEventDisableTiming));
+            // (a caller's own stream carries the prologue itself: one stream fewer — with more streams than hardware queues, 4 by
+            //  default, two of them share a queue and the kernels that were to run side by side run one after the other)
+            s_pro = stream ? stream : ctx->pipe_pro;
             s_main = ctx->pipe_main;
             slot = ctx->pipe_set;
-            if (stream) {          // a caller's own stream: what it queued there comes first (the NULL stream orders itself, and recording on it would wait for the front end in flight)
-                WF_HIP(hipEventRecord(ctx->pipe_call, wf_stream(stream)));
-                WF_HIP(hipStreamWaitEvent(wf_stream(s_pro), ctx->pipe_call, 0));
-            }
         }
-        if ((rc = link_pipe_select(ctx, set_bytes, w, s_pro))) return rc;     // (s_pro: the caller's stream unless the prologue runs ahead)
+        if ((rc = link_pipe_select(ctx, set_bytes, w, s_pro, ahead))) return rc;     // (s_pro: the caller's stream unless a NULL-stream caller's prologue runs ahead)
     } else if ((rc = wf_link_join_internal(ctx, stream))) {     // (a context that ran pipelined blocks before: ordinary stream order from here on)
         return rc;
     }
@@ -243,6 +248,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
                 if ((rc = mark(ev, 2, s_pro))) return rc;
                 WF_HIP(hipEventRecord(ctx->pipe_pro_done, wf_stream(s_pro)));
                 WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_pro_done, 0));
+                // ... and behind the previous block's pipe_back_go: the back stream has then seen that block's front end finish and the
+                // detector's launch packet is the next one in its queue, so the detector's workgroups are placed BEFORE this front end
+                // fills every SIMD (placed after it, the detector waits for two front-end workgroups to leave a CU at once)
+                if (ctx->pipe_back_go_valid) WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_back_go, 0));
                 if ((rc = mark(ev, 3, s_main))) return rc;
             }
             rc = wf_mod_chan_bank_packed(ctx, syms, cfg->nsym, cfg->d_h, 1, cfg->d_pulse, cfg->ntaps, cfg->sps, M_PI / 4, cfg->d_mf_taps,
@@ -261,6 +270,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
             back = ctx->pipe_stream;
             WF_HIP(hipEventRecord(ctx->pipe_front, wf_stream(s_main)));
             WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_front, 0));
+            if (ahead) {           // the next block's front end starts behind this point of the back stream (above)
+                WF_HIP(hipEventRecord(ctx->pipe_back_go, wf_stream(back)));
+                ctx->pipe_back_go_valid = true;
+            }
         }
         if ((rc = mark(ev, 6, back))) return rc;
         rc = wf_viterbi4_detect_packed(ctx, mf, L.ncols, cfg->differential, link_warmup(cfg), dbits, dsyms, nullptr, back);

@@ -149,6 +149,40 @@ __device__ __forceinline__ void vit_step(vit_lane &L, const double2 *__restrict_
     }
 }
 
+__device__ __forceinline__ void vit_save_start(vit_lane &L)
+{
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) L.ms[s4] = L.m0[s4];
+}
+
+// ... of an INTERIOR wave of the batch kernel (every row of every lane of the wave lies inside the burst): step j of the walk is
+// the same kind of step for all 64 lanes, so what vit_step decides per lane from 64-bit call indices is decided here once per
+// wave from j (scalar compares and branches, scalar shift counts): j = 0 the priming row, 1 .. warmup the warm-up (decisions
+// dropped), warmup + 1 .. the lane's own calls, packed at position (j - warmup - 1) & 15 and parked once per 16.  A chunk is a
+// multiple of 16 calls, so no group is left open.  Same vit_step_core, same order: same metrics, same decisions.
+template <int COL, bool PACKED>
+__device__ __forceinline__ void vit_step_interior(vit_lane &L, const double2 *__restrict__ zrow, int diff, int j, int warmup, int nsteps,
+                                                  uint64_t *__restrict__ dec)
+{
+    if (j >= nsteps) return;             // (the last batch's spare rows)
+    if (j == 0) {
+        L.prev = vit_components<COL, PACKED>(zrow);
+        return;
+    }
+    if (j == warmup + 1) vit_save_start(L);
+    bool bit, cd0, cd1;
+    vit_step_core<COL, PACKED>(L, zrow, diff, bit, cd0, cd1);
+    if (j > warmup) {
+        const int o = j - warmup - 1, c = o & 15;
+        L.wb |= (bit ? 1u : 0u) << c;
+        L.ws |= ((cd0 ? 1u : 0u) << (2 * c)) | ((cd1 ? 2u : 0u) << (2 * c));
+        if (c == 15) {
+            dec[o >> 4] = (uint64_t)L.wb | ((uint64_t)L.ws << 32);
+            L.wb = L.ws = 0;
+        }
+    }
+}
+
 // Expand the packed decisions of one lane (calls [a, a + n)) and store them: 16 B per group of 16.
 __device__ __forceinline__ uint64_t vit_spread_bits8(uint32_t x)    // 8 bits -> 8 bytes of 0 / 1, LSB first
 {
@@ -185,12 +219,6 @@ __device__ __forceinline__ void vit_flush(const uint64_t *__restrict__ dec, int 
             }
         }
     }
-}
-
-__device__ __forceinline__ void vit_save_start(vit_lane &L)
-{
-#pragma unroll
-    for (int s4 = 0; s4 < 4; ++s4) L.ms[s4] = L.m0[s4];
 }
 
 // Carry block <-> lane state.  The block keeps the reference's shape (8 branch increments of
@@ -330,13 +358,25 @@ __device__ __forceinline__ void viterbi_batch_body(const double *__restrict__ mf
     fetch(min(2, last_b), pend2);
 #endif
     const int64_t kbase = a - warmup - 1;
+    // An interior wave: its first lane's priming row is a row of the burst and its last lane's chunk ends inside the burst (all but
+    // the first and last few waves of a launch).  Wave-uniform.
+    const bool interior = g0u * CH - warmup - 1 >= 0 && (g0u + WF_WAVE) * CH <= ncalls;
     auto round = [&](int b, double2 (&pd)[NP]) __attribute__((always_inline)) {
         stash(pd);                                           // waits for batch b only (loads return in order)
         fetch(min(b + VIT_DEPTH, last_b), pd);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (live) {
+        if (interior) {
+            // every lane of the wave takes the same kind of step: per-wave bookkeeping (vit_step_interior)
+#pragma unroll 1
+            for (int jj = 0; jj < VIT_S; jj += 2) {
+                const int j = b * VIT_S + jj;
+                const double2 *zr = tile + lane * LS + RW * jj;
+                vit_step_interior<PAR0, PACKED>(L, zr, diff, j, warmup, nsteps, dec);
+                vit_step_interior<PAR0 ^ 1, PACKED>(L, zr + RW, diff, j + 1, warmup, nsteps, dec);
+            }
+        } else if (live) {
 #pragma unroll 1
             for (int jj = 0; jj < VIT_S; jj += 2) {
                 const int j = b * VIT_S + jj;

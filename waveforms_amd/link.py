@@ -279,9 +279,12 @@ class SOQPSKLink(_SOQPSK, _Link):
 
     @property
     def prologue_ahead(self) -> bool:
-        """A pipelined link (``fuse`` bit 5 with the one-kernel front end) whose context runs each block's prologue ahead on its
-        own stream (``WF_OPT_PIPE_RESERVE_CUS`` other than 0: a measured alternative, not the default)."""
-        return bool(self.cfg.fuse & 32) and bool(self.layout()["one_kernel_front_end"]) and _hip.get_option(self._ctx, _hip.WF_OPT_PIPE_RESERVE_CUS) != 0
+        """A pipelined link (``fuse`` bit 5 with the one-kernel front end) whose context runs each block's prologue ahead, beside
+        the previous block's front end (``WF_OPT_PIPE_RESERVE_CUS``, wf_link_run's own rule: N >= 1 always, -1 — what a context
+        starts with — for the short bank only, 0 never)."""
+        rsv = _hip.get_option(self._ctx, _hip.WF_OPT_PIPE_RESERVE_CUS)
+        ahead = rsv > 0 or (rsv < 0 and self.cfg.mf_ntaps == self.cfg.sps + 1)
+        return bool(self.cfg.fuse & 32) and bool(self.layout()["one_kernel_front_end"]) and ahead
 
 
 class CPMLink(_CPM, _Link):
