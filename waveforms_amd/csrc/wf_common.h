@@ -86,8 +86,16 @@ struct wf_ctx {
     // launch; the NEXT block's front end waits for it, so the detector's launch packet is always the older one (wf_link_run)
     hipEvent_t pipe_back_go = nullptr;
     bool pipe_back_go_valid = false;
+    // the same link without a CU mask (what a context starts with): block k's WHOLE chain — prologue, front end, detector, fix-up,
+    // count — on pipe_chain[set of block k], two non-blocking streams taken in turn; the edges between them: wf_link_run
+    void *pipe_chain[2] = {nullptr, nullptr};
+    hipEvent_t pipe_call = nullptr;      // recorded on the caller's stream at each such call: the chain starts behind it
+    hipEvent_t pipe_chain_pro = nullptr; // behind the last such block's prologue: the next one's starts behind it (context-owned scratch)
+    bool pipe_chain_pro_valid = false;
+    void *pipe_back_last = nullptr;      // the stream the last pipelined block's back end went to (link_pipe_close)
     bool pipe_front_recorded = false;    // a pipelined block has been queued: pipe_front stands behind its front end ...
-    bool pipe_front_on_main = false;     // ... on pipe_main: link_pipe_select orders a block of the other kind behind it
+    int pipe_front_kind = 0;             // ... on the caller's stream (0), pipe_main (1) or a chain (2): link_pipe_select orders a block of another kind behind it
+    uint64_t pipe_carries = 0;           // ... with carries of this size (0: the one set): a block with others waits for that front end too
     hipEvent_t pipe_front = nullptr, pipe_done[2] = {nullptr, nullptr};
     bool pipe_done_valid[2] = {false, false};
     int pipe_set = 0;

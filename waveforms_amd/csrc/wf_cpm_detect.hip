@@ -1361,6 +1361,7 @@ extern "C" int wf_cpm_link_run(wf_ctx *ctx, const wf_cpm_link_config *cfg, void 
         back = two_back && ctx->pipe_set ? ctx->pipe_stream2 : ctx->pipe_stream;
         WF_HIP(hipEventRecord(ctx->pipe_front, wf_stream(stream)));
         WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_front, 0));
+        if ((rc = link_pipe_back_order(ctx, back))) return rc;     // (behind a SOQPSK block's back end on a chain stream of the same context)
     }
     if ((rc = mark(ev, 6, back))) return rc;
     // (rows sit inside the block's set of intermediates: what lies before them — symbols, the sample region — and behind

@@ -66,6 +66,10 @@ extern "C" int wf_ctx_destroy(wf_ctx *c)
     if (c->pipe_main) (void)hipStreamDestroy(static_cast<hipStream_t>(c->pipe_main));
     if (c->pipe_pro_done) (void)hipEventDestroy(c->pipe_pro_done);
     if (c->pipe_back_go) (void)hipEventDestroy(c->pipe_back_go);
+    for (int k = 0; k < 2; ++k)
+        if (c->pipe_chain[k]) (void)hipStreamDestroy(static_cast<hipStream_t>(c->pipe_chain[k]));
+    if (c->pipe_call) (void)hipEventDestroy(c->pipe_call);
+    if (c->pipe_chain_pro) (void)hipEventDestroy(c->pipe_chain_pro);
     if (c->d_scan) (void)hipFree(c->d_scan);
     if (c->d_fsm_scratch) (void)hipFree(c->d_fsm_scratch);
     if (c->d_mod_scratch) (void)hipFree(c->d_mod_scratch);
@@ -96,6 +100,8 @@ extern "C" int wf_ctx_retire(wf_ctx *c)
     if (c->pipe_stream2) (void)hipStreamSynchronize(static_cast<hipStream_t>(c->pipe_stream2));
     if (c->pipe_pro) (void)hipStreamSynchronize(static_cast<hipStream_t>(c->pipe_pro));
     if (c->pipe_main) (void)hipStreamSynchronize(static_cast<hipStream_t>(c->pipe_main));
+    for (int k = 0; k < 2; ++k)
+        if (c->pipe_chain[k]) (void)hipStreamSynchronize(static_cast<hipStream_t>(c->pipe_chain[k]));
     return WF_OK;
 }
 

@@ -7,17 +7,19 @@ static inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * 
 
 // ---- fuse bit 5: the detector and the error count of a block run on a side stream of the context, beside the front end of the
 // NEXT run on the same context; the workspace then holds two sets of intermediates of `set_bytes` each, used alternately.
-// Step 1: both sets fit, and the side stream(s) and their events exist (`second`: the CPM links' second side stream).
-static inline int link_pipe_open(wf_ctx *ctx, const char *fn, int64_t set_bytes, int64_t workspace_bytes, bool second)
+// Step 1: both sets fit, and the events and the side stream(s) exist (`second`: the CPM links' second side stream; `side` false:
+// a block whose back end runs on its own chain stream and needs no side stream — wf_link_run).
+static inline int link_pipe_open(wf_ctx *ctx, const char *fn, int64_t set_bytes, int64_t workspace_bytes, bool second, bool side = true)
 {
     WF_REQUIRE(2 * set_bytes <= workspace_bytes, "%s: fuse bit 5 needs two sets of intermediates (%lld bytes)", fn, (long long)(2 * set_bytes));
     WF_HIP(hipSetDevice(ctx->device));
     hipStream_t ps;
-    if (!ctx->pipe_stream) {
+    if (!ctx->pipe_front) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_front, hipEventDisableTiming));
+    for (int k = 0; k < 2; ++k)
+        if (!ctx->pipe_done[k]) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_done[k], hipEventDisableTiming));
+    if (side && !ctx->pipe_stream) {
         WF_HIP(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
         ctx->pipe_stream = ps;
-        WF_HIP(hipEventCreateWithFlags(&ctx->pipe_front, hipEventDisableTiming));
-        for (int k = 0; k < 2; ++k) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_done[k], hipEventDisableTiming));
     }
     if (second && !ctx->pipe_stream2) {
         WF_HIP(hipStreamCreateWithFlags(&ps, hipStreamNonBlocking));
@@ -27,17 +29,35 @@ static inline int link_pipe_open(wf_ctx *ctx, const char *fn, int64_t set_bytes,
 }
 
 // Step 2: this block's set; `waiter`, the stream the block starts on, waits for the back end of the block that used it two blocks ago.
-// `on_main`: this block's front end goes to the context's pipe_main (wf_link_run with the prologue ahead) and its carries to scratch
-// slot pipe_set; every other pipelined block runs its front end on the caller's stream with the one set of carries, which is slot 0's
-// words.  One context may serve both kinds in turn (links of different forms share the per-device context), and the two streams
-// do not order themselves: where the kind changes, `waiter` also waits for the previous block's front end (pipe_front).
-static inline int link_pipe_select(wf_ctx *ctx, int64_t set_bytes, char *&w, void *waiter, bool on_main = false)
+// `kind`: where this block's front end goes — 0: the caller's stream, with the one set of carries, which is slot 0's words; 1: the
+// context's pipe_main, 2: the chain stream of its set (wf_link_run with the prologue ahead; carries in scratch slot pipe_set).  One
+// context may serve all kinds in turn (links of different forms share the per-device context), and their streams do not order
+// themselves: where the kind changes, `waiter` also waits for the previous block's front end (pipe_front).
+// `carries` (kinds 1 and 2): a word that differs where the carries' size does.  Slot 1 lies behind slot 0 AS THIS BLOCK SIZES IT, so
+// the slots of two links of different burst lengths overlap: there too `waiter`, which carries the prologue, waits for the previous
+// front end — it may still be reading what this block's carry kernels write.
+static inline int link_pipe_select(wf_ctx *ctx, int64_t set_bytes, char *&w, void *waiter, int kind = 0, uint64_t carries = 0)
 {
-    if (ctx->pipe_front_on_main != on_main && ctx->pipe_front_recorded) WF_HIP(hipStreamWaitEvent(wf_stream(waiter), ctx->pipe_front, 0));
-    ctx->pipe_front_on_main = on_main;
+    if ((ctx->pipe_front_kind != kind || ctx->pipe_carries != carries) && ctx->pipe_front_recorded)
+        WF_HIP(hipStreamWaitEvent(wf_stream(waiter), ctx->pipe_front, 0));
+    ctx->pipe_front_kind = kind;
+    ctx->pipe_carries = carries;
     ctx->pipe_front_recorded = true;      // (every pipelined block records it behind its front end, further down the same call)
     w += (int64_t)ctx->pipe_set * set_bytes;
     if (ctx->pipe_done_valid[ctx->pipe_set]) WF_HIP(hipStreamWaitEvent(wf_stream(waiter), ctx->pipe_done[ctx->pipe_set], 0));
+    return WF_OK;
+}
+
+// Step 2b, in front of the back end on `back`: every back end works in the context's ONE set of detector scratch (proof records and
+// repair lists: the fix-up of a block reads what its detector wrote).  Back ends on one side stream follow each other; where the
+// previous block's ran on another stream and either of the two is a chain stream, `back` waits for that back end (pipe_done of the
+// other set).  In steady state the wait is long satisfied: a back end is a quarter of a front end.
+static inline int link_pipe_back_order(wf_ctx *ctx, void *back)
+{
+    const void *last = ctx->pipe_back_last;
+    const bool chains = back == ctx->pipe_chain[0] || back == ctx->pipe_chain[1] || last == ctx->pipe_chain[0] || last == ctx->pipe_chain[1];
+    if (last && last != back && chains && ctx->pipe_done_valid[ctx->pipe_set ^ 1])
+        WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_done[ctx->pipe_set ^ 1], 0));
     return WF_OK;
 }
 
@@ -46,6 +66,7 @@ static inline int link_pipe_close(wf_ctx *ctx, void *back)
 {
     WF_HIP(hipEventRecord(ctx->pipe_done[ctx->pipe_set], wf_stream(back)));
     ctx->pipe_done_valid[ctx->pipe_set] = true;
+    ctx->pipe_back_last = back;
     ctx->pipe_set ^= 1;
     return WF_OK;
 }

@@ -166,29 +166,75 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
     char *w = static_cast<char *>(d_workspace);
     const bool piped = link_pipelined(cfg) && L.ncols > 0;
     void *s_pro = stream, *s_main = stream;       // where the prologue / the front-end kernel go (a pipelined link: library streams)
-    bool ahead = false;
+    bool ahead = false, chain = false, had_front = false;   // (had_front: a pipelined block was queued on this context before this one)
     int slot = -1, rc;
     if (piped) {
         const int64_t set_bytes = round_up((int64_t)L.total, 256);
-        if ((rc = link_pipe_open(ctx, "wf_link_run", set_bytes, workspace_bytes, false))) return rc;
-        // The prologue-ahead order.  A block's PROLOGUE (PRBS + precoder, tile sums, tile scan: ~60 us of small kernels that otherwise
-        // sit between two front ends) depends only on its set of intermediates being free: the host queues block k + 1 while block
-        // k's front end runs, so it runs BESIDE that front end — on the caller's stream, or on pipe_pro for a caller on the NULL
-        // stream (which would wait for the front end in flight).  The front-end kernel goes to pipe_main (CU-masked for N >= 1: see
-        // link_masked_stream) behind its own prologue, the previous front end and the previous block's pipe_back_go (below);
-        // detector + count to pipe_stream as in the other order.  The carries live in one of two scratch sets (slot = the set).
-        // Without pipe_back_go the dispatcher served whichever of two queues got there first: a detector placed after the next front
-        // end had filled every SIMD waited for two front-end workgroups to leave a CU at once and ran 461 us instead of 109 (0.474 ms
-        // per block against 0.457 in the other order: profiles/r06_ab_prologue_ahead_cu_mask.log, r06_timeline_soqpsk_prologue_ahead.txt).
-        // With it the detector starts at least 7 us (median 17) before the next front end in every period (profiles/order_timeline_soqpsk.txt).
-        // WF_OPT_PIPE_RESERVE_CUS: 0 = the other order (prologue between two front ends on the caller's stream), N >= 1 = this one
-        // with N CUs masked, -1 (what a context starts with) = this one without a mask WHERE IT WAS MEASURED FASTER: the short
-        // (pulse-truncation) bank — 0.435 against 0.459 ms per block at 8 samples per symbol, 0.564 against 0.591 at 10 — and the
-        // other order for the long (PAM) bank, whose front end leaves the small kernels less (0.72 against 0.654 and 0.905 against
-        // 0.851: profiles/order_ab_headline.log, order_ab_others.log).
         const int64_t rsv = ctx->opt[WF_OPT_PIPE_RESERVE_CUS];
         ahead = rsv > 0 || (rsv < 0 && cfg->mf_ntaps == cfg->sps + 1);
-        if (ahead) {
+        chain = ahead && rsv < 0 && cfg->sps == 8;      // (where chains were measured faster: below)
+        if ((rc = link_pipe_open(ctx, "wf_link_run", set_bytes, workspace_bytes, false, !chain))) return rc;
+        // The prologue-ahead order.  A block's PROLOGUE (PRBS + precoder, tile sums, tile scan: ~60 us of small kernels that otherwise
+        // sit between two front ends) depends only on its set of intermediates being free: the host queues block k + 1 while block
+        // k's front end runs, so it runs BESIDE that front end.  WF_OPT_PIPE_RESERVE_CUS: 0 = the other order (prologue between two
+        // front ends on the caller's stream), N >= 1 = this one with N CUs masked, -1 (what a context starts with) = this one without
+        // a mask WHERE IT WAS MEASURED FASTER: the short (pulse-truncation) bank — 0.435 against 0.459 ms per block at 8 samples per
+        // symbol, 0.564 against 0.591 at 10 — and the other order for the long (PAM) bank, whose front end leaves the small kernels
+        // less (0.72 against 0.654 and 0.905 against 0.851: profiles/order_ab_headline.log, order_ab_others.log).
+        //
+        // -1 with the short bank at 8 samples per symbol — CHAINS, again where they were measured faster: 0.4257 against 0.4327 ms per
+        // block from the NULL stream (the parent's passes range over 0.003) and 0.4235 against 0.469 from a caller's own stream
+        // (profiles/chain_ab_headline.log, chain_ab_own_stream.log).  At 10 samples per symbol they were slower (0.577 against 0.566:
+        // profiles/chain_ab_sps10_chains.log): that form keeps the masked form's sequence without a mask (below).  Three links side by
+        // side, each on its stream with its own context, lose 4 - 6 % (22.3 against 23.6 Gsym/s: six chain streams on four hardware
+        // queues); a call cannot tell that case from one link on a caller's stream, and with the parent's sequence kept for callers'
+        // streams it lost 12 % (profiles/chain_ab_null_only.log) — which streams share a queue decides, not the sequence.
+        // Block k's whole chain (prologue, front end, detector, fix-up, count) goes on ONE stream,
+        // pipe_chain[set of block k]; consecutive blocks take the two chains in turn.  Kernels that follow each other in a queue
+        // start back to back; a wait of one queue on an event of another costs 14 - 19 us (profiles/order_timeline_soqpsk.txt), and
+        // the detector behind its own front end needs none (what is left between the two, 11 us, is the record and the wait queued
+        // between them: profiles/chain_timeline_chains.txt).  The one edge between two chains that ever holds a kernel back: front
+        // end k + 1 waits for pipe_front, recorded behind front end k on the other chain — so detector k's launch packet, next in
+        // its queue behind that record, is placed BEFORE front end k + 1 fills every SIMD (placed after it, the detector waited for
+        // two front-end workgroups to leave a CU at once and ran 461 us instead of 109: profiles/r06_ab_prologue_ahead_cu_mask.log).
+        // What one prologue stream and one back stream used to order for free, and what orders it now (the context owns all of it,
+        // not the set; every such wait is long satisfied in steady state — chain s is idle from the end of count k - 1, a quarter
+        // of a front end after front end k started, and a back end is a quarter of a front end):
+        //   d_fsm_scratch, d_tables + tables_event / tables_stream, d_small — written by the GENERIC precoder only (fuse bit 4, or a
+        //     burst too long for the one-launch PRBS + precoder, which works in its own arguments and the set).  EDGE: a generic
+        //     prologue starts behind pipe_chain_pro, recorded behind the last generic prologue.  (The LFSR jump tables are uploaded with
+        //     a blocking copy before the call that needs them returns: no stream order involved.)
+        //   d_mod_scratch outside the two carry slots — nothing: the carry kernels write their slot only.
+        //   d_vit_edge (proof records and repair lists: fix-up k reads what detector k wrote, detector k + 1 overwrites it) and
+        //     d_vit_unmerged — EDGE: back end k + 1 starts behind pipe_done[set of k], recorded behind count k
+        //     (link_pipe_back_order; the same edge orders a chain's back end against a side stream's where forms take turns).
+        //   the carry slots and the sets of intermediates — per set: block k + 2 follows block k in the same chain.  (Slot 1 lies
+        //     behind slot 0 as the BLOCK sizes it: where two links of different burst lengths take turns on one context their slots
+        //     overlap, and the later block's chain starts behind the earlier front end — link_pipe_select.)
+        //   the stage-event slots — host objects: a record replaces the earlier one, so a slot holds the nine records of the LAST
+        //     block that used it, all on one chain; nothing on the device depends on them.
+        //   the caller's stream (counters zeroed there, tables, earlier work) — EDGE: the chain starts behind pipe_call, recorded
+        //     on the caller's stream at this call.  The chains are NON-BLOCKING: a blocking stream would order each block behind
+        //     everything queued on the legacy NULL stream and the NULL stream's record behind both chains — two blocks in series.
+        // wf_link_join / wf_ctx_check wait for pipe_done[0] and [1]: each stands at the end of what its chain holds.
+        //
+        // N >= 1, and -1 outside the chains' case — the masked form, as measured in round 6: prologue on the caller's stream (pipe_pro for a caller on the NULL stream,
+        // which would wait for the front end in flight), front-end kernel on pipe_main (CU-masked: link_masked_stream) behind its own
+        // prologue, the previous front end and the previous block's pipe_back_go (below), detector + count on pipe_stream.
+        if (chain) {
+            for (int s = 0; s < 2; ++s)
+                if (!ctx->pipe_chain[s]) {
+                    hipStream_t sc;
+                    WF_HIP(hipStreamCreateWithFlags(&sc, hipStreamNonBlocking));
+                    ctx->pipe_chain[s] = sc;
+                }
+            if (!ctx->pipe_call) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_call, hipEventDisableTiming));
+            if (!ctx->pipe_chain_pro) WF_HIP(hipEventCreateWithFlags(&ctx->pipe_chain_pro, hipEventDisableTiming));
+            s_pro = s_main = ctx->pipe_chain[ctx->pipe_set];
+            slot = ctx->pipe_set;
+            WF_HIP(hipEventRecord(ctx->pipe_call, wf_stream(stream)));
+            WF_HIP(hipStreamWaitEvent(wf_stream(s_pro), ctx->pipe_call, 0));
+        } else if (ahead) {
             if (!ctx->pipe_pro) {
                 hipStream_t sp;
                 WF_HIP(hipStreamCreateWithFlags(&sp, hipStreamDefault));       // (default flags: ordered behind what the caller queued on the NULL stream)
@@ -206,7 +252,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
             s_main = ctx->pipe_main;
             slot = ctx->pipe_set;
         }
-        if ((rc = link_pipe_select(ctx, set_bytes, w, s_pro, ahead))) return rc;     // (s_pro: the caller's stream unless a NULL-stream caller's prologue runs ahead)
+        had_front = ctx->pipe_front_recorded;
+        // (the carries' size follows from the burst length, the samples per symbol and the pulse length: J <= 9 symbols of <= 20 samples)
+        const uint64_t carries = ahead ? ((uint64_t)cfg->nsym << 20) | ((uint64_t)cfg->sps << 10) | (uint64_t)cfg->ntaps : 0;
+        if ((rc = link_pipe_select(ctx, set_bytes, w, s_pro, chain ? 2 : (ahead ? 1 : 0), carries))) return rc;     // (s_pro: the caller's stream unless the prologue runs ahead on a library stream)
     } else if ((rc = wf_link_join_internal(ctx, stream))) {     // (a context that ran pipelined blocks before: ordinary stream order from here on)
         return rc;
     }
@@ -226,7 +275,10 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
     rc = (cfg->fuse & 16) ? 1 : wf_soqpsk_prbs_encode(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, &T.next[0][0][0], &T.outp[0][0][0], bits,
                                                        cfg->nsym, syms, s_pro, ev ? (void *)ev[1] : nullptr);
     if (rc < 0) return rc;
-    if (rc == 1) {
+    const bool generic = rc == 1;
+    if (generic) {
+        // (a chain: the generic precoder works in context-owned scratch — behind the last block that did, which ran on the other chain)
+        if (chain && ctx->pipe_chain_pro_valid) WF_HIP(hipStreamWaitEvent(wf_stream(s_pro), ctx->pipe_chain_pro, 0));
         if ((rc = wf_lfsr_generate(ctx, cfg->degree, cfg->mask, cfg->state, cfg->skip, bits, cfg->nsym, nullptr, s_pro))) return rc;
         if ((rc = mark(ev, 1, s_pro))) return rc;
         if ((rc = wf_fsm_encode(ctx, &T.next[0][0][0], &T.outp[0][0][0], 2, 4, 1, bits, cfg->nsym, 0, 0, syms, nullptr, s_pro))) return rc;
@@ -246,12 +298,23 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
                 // stage events of such a block: "encode" = precoder + the two carry kernels (the prologue's tail), "fir" = the wait
                 // between the prologue's end and the main kernel's start (no kernel), "phase" = the main kernel
                 if ((rc = mark(ev, 2, s_pro))) return rc;
-                WF_HIP(hipEventRecord(ctx->pipe_pro_done, wf_stream(s_pro)));
-                WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_pro_done, 0));
-                // ... and behind the previous block's pipe_back_go: the back stream has then seen that block's front end finish and the
-                // detector's launch packet is the next one in its queue, so the detector's workgroups are placed BEFORE this front end
-                // fills every SIMD (placed after it, the detector waits for two front-end workgroups to leave a CU at once)
-                if (ctx->pipe_back_go_valid) WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_back_go, 0));
+                if (chain) {
+                    // the next generic prologue starts behind this one (no record where none is needed: every packet between the scan
+                    // kernel and the main kernel delays the main kernel); the main kernel, in the queue of its own prologue, behind the
+                    // previous block's front end on the other chain (on whatever stream, where the form has just changed)
+                    if (generic) {
+                        WF_HIP(hipEventRecord(ctx->pipe_chain_pro, wf_stream(s_pro)));
+                        ctx->pipe_chain_pro_valid = true;
+                    }
+                    if (had_front) WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_front, 0));
+                } else {
+                    WF_HIP(hipEventRecord(ctx->pipe_pro_done, wf_stream(s_pro)));
+                    WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_pro_done, 0));
+                    // ... and behind the previous block's pipe_back_go: the back stream has then seen that block's front end finish and the
+                    // detector's launch packet is the next one in its queue, so the detector's workgroups are placed BEFORE this front end
+                    // fills every SIMD (placed after it, the detector waits for two front-end workgroups to leave a CU at once)
+                    if (ctx->pipe_back_go_valid) WF_HIP(hipStreamWaitEvent(wf_stream(s_main), ctx->pipe_back_go, 0));
+                }
                 if ((rc = mark(ev, 3, s_main))) return rc;
             }
             rc = wf_mod_chan_bank_packed(ctx, syms, cfg->nsym, cfg->d_h, 1, cfg->d_pulse, cfg->ntaps, cfg->sps, M_PI / 4, cfg->d_mf_taps,
@@ -267,13 +330,14 @@ extern "C" int wf_link_run(wf_ctx *ctx, const wf_link_config *cfg, void *d_works
         if ((rc = mark(ev, 4, s_main)) || (rc = mark(ev, 5, s_main))) return rc;
         void *back = stream;                  // the stream the detector and the counter run on
         if (piped) {
-            back = ctx->pipe_stream;
+            back = chain ? s_main : ctx->pipe_stream;
             WF_HIP(hipEventRecord(ctx->pipe_front, wf_stream(s_main)));
-            WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_front, 0));
-            if (ahead) {           // the next block's front end starts behind this point of the back stream (above)
+            if (!chain) WF_HIP(hipStreamWaitEvent(wf_stream(back), ctx->pipe_front, 0));     // (a chain: the detector is next in the front end's own queue)
+            if (ahead && !chain) {           // the next block's front end starts behind this point of the back stream (above)
                 WF_HIP(hipEventRecord(ctx->pipe_back_go, wf_stream(back)));
                 ctx->pipe_back_go_valid = true;
             }
+            if ((rc = link_pipe_back_order(ctx, back))) return rc;
         }
         if ((rc = mark(ev, 6, back))) return rc;
         rc = wf_viterbi4_detect_packed(ctx, mf, L.ncols, cfg->differential, link_warmup(cfg), dbits, dsyms, nullptr, back);
