@@ -997,6 +997,42 @@ int wf_carrier_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, i
 int wf_rows_derotate(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int W, const double *d_phase, int64_t nwin, double phase0,
                      double *d_out, void *stream);
 
+/* ---- The same recovery for the generic CPM detectors (ARTM, PCM/FM) -----------------------------------------------------
+ * (waveforms_amd/sync/carrier_cpm.py restates each in numpy: cpm_map_branch_host, carrier_stat_terms_host, and
+ * carrier_track_host / interpolate_phase_host of carrier.py with a period.)  The full-phase trellis is exactly symmetric
+ * under a rotation of the rows by P = 2π / p: it moves every state's phase index v by one and leaves the input symbols
+ * alone, so the estimate is modulo P and the ambiguity never reaches the data.
+ * wf_cpm_soft_branch is wf_cpm_soft with two more outputs per call.  With T_k(s,u) = (ã_k(s) + inc_k(s,u)) + b̃_{k+1}(e(s,u)),
+ * the operand of wf_cpm_soft's λ minima:
+ *   d_branch[k] = b* = M s* + u*, the (s, u) with the smallest T_k, ties to the smallest b (S M <= 256: a byte)
+ *   d_term[2k], d_term[2k+1] = (x_k, y_k), the components of q_k = -Z_k[f] e^{-j φ_r} on that branch, f = u* + M c(s*), r of s*:
+ *     x_k = inc_k(s*, u*)   (the metric term itself),    y_k = -fma(cos_r, Im Z_k[f], -(sin_r * Re Z_k[f]))
+ * Every T is >= +0 and never -0 (the argument above), so equal T are bitwise equal and the tie rule is exact in any order of
+ * comparison.  A rotation of the rows by θ turns q_k by θ: the angle of -Σ q_k over a window estimates θ.  A coarse
+ * hypothesis is this call with a rotated table: entry r = (cos, sin)(π r / p + θ_h) detects the rows derotated by θ_h without
+ * a pass over them.  d_llr and d_bits are BITWISE wf_cpm_soft's: the bounds, proof and repair launches are the same code,
+ * only the last launch differs.  d_branch: ncalls bytes; d_term: 2 ncalls float64, 16-byte aligned, or NULL (not written).
+ * Everything else (alignment, warm-up, chunking, options, counters, scratch) as wf_cpm_soft; a NULL d_branch, a d_term not
+ * 16-byte aligned or any argument wf_cpm_soft refuses: WF_ERR_VALUE before the context is touched. */
+int wf_cpm_soft_branch(wf_ctx *ctx, const wf_cpm_detector_config *det, const double *d_rot_cs, const double *d_rows_ri,
+                       int64_t ncalls, int64_t first_call, int warmup, double *d_llr, uint8_t *d_bits, uint8_t *d_branch,
+                       double *d_term, void *stream);
+/* wf_carrier_stat from the terms wf_cpm_soft_branch wrote: d_stat[w] = (X_w, Y_w) from x = d_term[2k], y = d_term[2k+1] in
+ * exactly wf_carrier_stat's order of additions (64 lane partials from +0, i increasing, then d = 32 .. 1).  W outside its
+ * range, ncalls < 1, a NULL pointer, terms not 16-byte or d_stat not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_carrier_stat_terms(wf_ctx *ctx, const double *d_term, int64_t ncalls, int W, double *d_stat, void *stream);
+/* wf_carrier_track with `period` in place of π, in ψ_w = ((double)h*_w * period) / H + atan2(-Y, -X) and in
+ * wrap(x) = x - period ceil(x / period - 1/2); hypothesis h derotated by h period / H.  wf_carrier_track is this with
+ * period = π (one kernel), and the same bound against a host statement holds.  period not finite or outside (0, 2π], or any
+ * argument wf_carrier_track refuses: WF_ERR_VALUE before the context is touched. */
+int wf_carrier_track_mod(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, double *d_phase,
+                         uint8_t *d_choice, void *stream);
+/* wf_rows_derotate for rows of nvals complex128 (1 .. 64; ARTM 16, PCM/FM 4): the same φ_k, the same order of operations, all
+ * nvals values of row k; wf_rows_derotate is nvals = 3 (one kernel).  nvals outside 1 .. 64 or any argument wf_rows_derotate
+ * refuses: WF_ERR_VALUE before the context is touched. */
+int wf_rows_derotate_n(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int nvals, int W, const double *d_phase, int64_t nwin,
+                       double phase0, double *d_out, void *stream);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

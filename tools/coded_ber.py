@@ -56,10 +56,11 @@ runs on the SAME decisions of the same blocks, and stays the ``"rs"`` entry.  Ev
 flagged failures, miscorrections, symbols corrected, erasures declared / filled, and from the same timed blocks the device-event
 times of ``rs_mark_erasures``, of ``rs_decode`` with erasures and of ``rs_decode`` without, with their ratio.
 
-With ``--carrier-phase DEG`` / ``--carrier-freq NU`` (cycles per sample) and ``--recover`` (SOQPSK-TG, LDPC codes) the tool runs
+With ``--carrier-phase DEG`` / ``--carrier-freq NU`` (cycles per sample) and ``--recover`` (LDPC codes) the tool runs
 three FRAMED CodedSOQPSKLink on the same blocks and prints three curves: ``genie`` (no carrier offset: today's link),
 ``impaired`` (the offset, no recovery) and ``recovered`` (the offset and ``CarrierRecovery`` with ``--carrier-window`` rows per
-window, ``--carrier-hyp`` hypotheses, ``--carrier-span``, ``--carrier-refine``).  It also prints the recovery's kernel times per
+window, ``--carrier-hyp`` hypotheses, ``--carrier-span``, ``--carrier-refine``).  With ``--waveform multih|pcmfm`` the three are
+unframed CodedCPMLink and the recovery is ``CPMCarrierRecovery`` (``--carrier-hyp`` defaults to the class's 2).  It also prints the recovery's kernel times per
 block (device events around every stage, summed over the passes, ``--steps`` blocks after one warm-up) beside one plain soft
 detection of the same rows, and ``loss_db_at_fer_1e-2``: recovered minus genie, both interpolated in log FER (null where a
 curve does not cross 1e-2 inside the sweep).
@@ -133,31 +134,44 @@ def _ebn0_at_fer(points, key, target=1e-2):
 
 
 def main_carrier(args) -> None:
-    """The ``--recover`` form: genie, impaired and recovered framed links on the same blocks."""
+    """The ``--recover`` form: genie, impaired and recovered links on the same blocks (SOQPSK-TG: framed; ARTM, PCM/FM: not)."""
     import math
 
     import torch
 
     from waveforms_amd import device as dev
     from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CodedSOQPSKLink
+    from waveforms_amd.encoding.coded import CodedCPMLink, CodedSOQPSKLink
     from waveforms_amd.encoding.framing import Framing
     from waveforms_amd.sync.carrier import MAX_DRIFT_TURNS, CarrierRecovery
+    from waveforms_amd.sync.carrier_cpm import DEFAULT_HYPOTHESES, MAX_DRIFT_PERIODS, CPMCarrierRecovery
 
     torch.cuda.set_device(0)
     code = ldpc.demo_code(128 if args.code == "demo" else 1024)
     per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
-    fr = Framing(code)
-    rec = CarrierRecovery(args.carrier_window, args.carrier_span, args.carrier_hyp, args.carrier_refine)
+    cpm = args.waveform != "soqpsk"
     carrier = (math.radians(args.carrier_phase), args.carrier_freq)
-    kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
-    links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, carrier=carrier, **kw),
-             "recovered": CodedSOQPSKLink(code, per, carrier=carrier, recovery=rec, **kw)}
+    if cpm:
+        from waveforms_amd.viterbi import cpm as vc
+
+        spec = vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
+        rec = CPMCarrierRecovery(spec, args.carrier_window, args.carrier_span, args.carrier_hyp or DEFAULT_HYPOTHESES, args.carrier_refine)
+        cls, kw, limit = CodedCPMLink, dict(waveform=args.waveform, alpha=args.alpha, max_iter=args.max_iter), MAX_DRIFT_PERIODS / spec.p
+        recover, soft = rec.recover, lambda rows: dev.cpm_soft(rows, spec, 0, 0, d_rot=links["genie"]._d_rot)
+        framed = None
+    else:
+        fr = Framing(code)
+        rec = CarrierRecovery(args.carrier_window, args.carrier_span, args.carrier_hyp or 8, args.carrier_refine)
+        cls, kw, limit = CodedSOQPSKLink, dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits), MAX_DRIFT_TURNS
+        recover, soft = lambda rows: rec.recover(rows, True), lambda rows: dev.viterbi_soft(rows, True)
+        framed = {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits}
+    links = {"genie": cls(code, per, **kw), "impaired": cls(code, per, carrier=carrier, **kw),
+             "recovered": cls(code, per, carrier=carrier, recovery=rec, **kw)}
     sps = links["genie"].sps
-    out = {"tool": "coded_ber", "form": "carrier", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
-           "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
+    out = {"tool": "coded_ber", "form": "carrier", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
+           "detector": None if cpm else args.detector, "block_codewords": per, "framed": framed,
            "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
-                       "drift_turns_per_window": abs(args.carrier_freq) * sps * rec.window, "documented_limit_turns_per_window": MAX_DRIFT_TURNS},
+                       "drift_turns_per_window": abs(args.carrier_freq) * sps * rec.window, "documented_limit_turns_per_window": limit},
            "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine}, "points": []}
     for e in args.ebn0:
         point = {"ebn0_info_db": e}
@@ -171,7 +185,7 @@ def main_carrier(args) -> None:
             be, fe, nc, m, mean_it = lk.result()
             ue, um = lk.uncoded_result()
             point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
-                           "mean_iters": round(mean_it, 3), "uncoded_ber": ue / um, "wrong_locks": lk.sync_result()[1]}
+                           "mean_iters": round(mean_it, 3), "uncoded_ber": ue / um, "wrong_locks": None if cpm else lk.sync_result()[1]}
         point["codewords"] = b * per
         # the recovery's stages on one burst, each bracketed by device events, beside one plain soft detection
         lk = links["recovered"]
@@ -180,10 +194,10 @@ def main_carrier(args) -> None:
         tot, soft_ms = {}, 0.0
         rec.times = True
         for s in range(args.steps + 1):
-            rec.recover(rows, True)
+            recover(rows)
             t = rec.stage_times()
             ev[0].record()
-            dev.viterbi_soft(rows, True)
+            soft(rows)
             ev[1].record()
             torch.cuda.synchronize()
             if s:                                                         # (the first round warms up)
@@ -373,15 +387,15 @@ def main() -> None:
     ap.add_argument("--carrier-freq", type=float, default=0.0, help="carrier frequency offset, cycles per sample")
     ap.add_argument("--recover", action="store_true", help="genie, impaired and recovered framed links on the same blocks (CarrierRecovery)")
     ap.add_argument("--carrier-window", type=int, default=256, help="--recover: rows per window")
-    ap.add_argument("--carrier-hyp", type=int, default=8, help="--recover: coarse hypotheses")
+    ap.add_argument("--carrier-hyp", type=int, default=0, help="--recover: coarse hypotheses (0: 8 for SOQPSK-TG, the class's 2 for ARTM and PCM/FM)")
     ap.add_argument("--carrier-span", type=int, default=5, help="--recover: windows of the centred mean")
     ap.add_argument("--carrier-refine", type=int, default=1, help="--recover: refinement passes")
     args = ap.parse_args()
     if args.recover or args.carrier_phase or args.carrier_freq:
         if not args.recover:
             ap.error("--carrier-phase / --carrier-freq go with --recover")
-        if args.waveform != "soqpsk" or args.code.startswith("conv") or args.outer or args.live_only:
-            ap.error("--recover is the framed CodedSOQPSKLink's: --waveform soqpsk, an LDPC code, no --outer / --live-only")
+        if args.code.startswith("conv") or args.outer or args.live_only:
+            ap.error("--recover is CodedSOQPSKLink's (framed) and CodedCPMLink's: an LDPC code, no --outer / --live-only")
         return main_carrier(args)
     if args.live_only and (args.waveform != "soqpsk" or args.outer < 1):
         ap.error("--live-only is the SOQPSK-TG loop's: it needs --waveform soqpsk and --outer N")

@@ -135,6 +135,10 @@ SIGNATURES = {
     "wf_carrier_stat": (c_int, [_P, _P, _P, c_int64, c_int, _P, _P]),
     "wf_carrier_track": (c_int, [_P, _P, c_int, c_int64, c_int, _P, _P, _P]),
     "wf_rows_derotate": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, c_double, _P, _P]),
+    "wf_cpm_soft_branch": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int, _P, _P, _P, _P, _P]),
+    "wf_carrier_stat_terms": (c_int, [_P, _P, c_int64, c_int, _P, _P]),
+    "wf_carrier_track_mod": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, _P, _P, _P]),
+    "wf_rows_derotate_n": (c_int, [_P, _P, c_int64, c_int, c_int, _P, c_int64, c_double, _P, _P]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

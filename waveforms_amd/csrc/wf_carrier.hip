@@ -1,5 +1,6 @@
 // wf_carrier.hip — carrier phase and frequency: the impairment (wf_carrier_offset_c128) and the stages of the
-// decision-directed recovery over windows of detector rows (wf_carrier_stat, wf_carrier_track, wf_rows_derotate).
+// decision-directed recovery over windows of detector rows (wf_carrier_stat, wf_carrier_track, wf_rows_derotate, and their
+// forms for the CPM detectors: wf_carrier_stat_terms, wf_carrier_track_mod, wf_rows_derotate_n — the same kernels).
 // include/wfhip.h states every definition; waveforms_amd/sync/carrier.py restates them in numpy.  The reference has no
 // synchroniser: these are the build's own.  The branch decisions come from wf_viterbi4_soft_branch (wf_viterbi_soft.hip).
 //
@@ -10,10 +11,10 @@
 //                           (d = 32 .. 1) in the order the header states.  q = state_exp_term[start] z[idx] is a signed
 //                           pick of z's components: no product, nothing rounded but the sums.
 //   carrier_track_kernel    ONE workgroup: per window the best hypothesis and its phase (threads in parallel), the
-//                           unwrapping modulo π as a blocked scan (a segment of windows per thread, the 1024 segment sums
+//                           unwrapping modulo the period (π, or 2π/p for CPM) as a blocked scan (a segment of windows per thread, the 1024 segment sums
 //                           added in order: the definition's running sum to rounding), the centred mean (threads in
 //                           parallel).  The unwrapped phases pass through the context's detector scratch.
-//   rows_derotate_kernel    a thread per 48-byte row: 96 B of traffic and one fp64 sincos.
+//   rows_derotate_kernel    a thread per row of nvals values (3: the 48-byte rows; 4 / 16: PCM/FM / ARTM): one fp64 sincos a row.
 //
 // The phase arithmetic is written one operation per statement where the host statement must see the same roundings
 // (-ffp-contract=on fuses within an expression only).
@@ -48,6 +49,20 @@ __device__ __forceinline__ double2 carrier_q(int start, double2 z)
     return start == 0 ? make_double2(-z.y, z.x) : start == 1 ? make_double2(-z.x, -z.y) : start == 2 ? z : make_double2(z.y, -z.x);
 }
 
+// the 64 lane partials of a window folded by a shuffle-down butterfly, d = 32 .. 1; lane 0 writes (X_w, Y_w)
+__device__ __forceinline__ void carrier_fold(double px, double py, int lane, double *__restrict__ out)
+{
+#pragma unroll
+    for (int d = WF_WAVE / 2; d >= 1; d >>= 1) {        // p_l + p_{l+d} is what lanes l < d keep; the others' sums are never read
+        px += __shfl_down(px, d, WF_WAVE);
+        py += __shfl_down(py, d, WF_WAVE);
+    }
+    if (lane == 0) {
+        out[0] = px;
+        out[1] = py;
+    }
+}
+
 __global__ __launch_bounds__(CARRIER_THREADS) void carrier_stat_kernel(const double *__restrict__ rows, const uint8_t *__restrict__ branch, int64_t n, int W,
                                                                        int64_t nwin, double *__restrict__ stat)
 {
@@ -65,27 +80,38 @@ __global__ __launch_bounds__(CARRIER_THREADS) void carrier_stat_kernel(const dou
             py += q.y;
         }
     }
-#pragma unroll
-    for (int d = WF_WAVE / 2; d >= 1; d >>= 1) {        // p_l + p_{l+d} is what lanes l < d keep; the others' sums are never read
-        px += __shfl_down(px, d, WF_WAVE);
-        py += __shfl_down(py, d, WF_WAVE);
-    }
-    if (lane == 0) {
-        stat[2 * w] = px;
-        stat[2 * w + 1] = py;
-    }
+    carrier_fold(px, py, lane, stat + 2 * w);
 }
 
-// x - π ceil(x / π - 1/2): into (-π/2, π/2]
-__device__ __forceinline__ double carrier_wrap_pi(double x)
+// the same statistic from the terms wf_cpm_soft_branch wrote: q_k = (x_k, y_k) is read, not formed
+__global__ __launch_bounds__(CARRIER_THREADS) void carrier_stat_terms_kernel(const double2 *__restrict__ term, int64_t n, int W, int64_t nwin,
+                                                                             double *__restrict__ stat)
 {
-    const double r = x / kCarrierPi;
+    const int64_t w = (int64_t)blockIdx.x * CARRIER_WAVES + threadIdx.x / WF_WAVE;      // wave-uniform
+    if (w >= nwin) return;
+    const int lane = wf_lane();
+    double px = 0.0, py = 0.0;
+    for (int i = 0; i < W / WF_WAVE; ++i) {
+        const int64_t k = w * W + (int64_t)i * WF_WAVE + lane;
+        if (k < n) {
+            const double2 q = term[k];
+            px += q.x;
+            py += q.y;
+        }
+    }
+    carrier_fold(px, py, lane, stat + 2 * w);
+}
+
+// x - P ceil(x / P - 1/2): into (-P/2, P/2], P the period (π for SOQPSK-TG)
+__device__ __forceinline__ double carrier_wrap(double x, double period)
+{
+    const double r = x / period;
     const double c = ceil(r - 0.5);
-    const double m = kCarrierPi * c;
+    const double m = period * c;
     return x - m;
 }
 
-__device__ __forceinline__ double carrier_psi(const double *stat, int H, int64_t nwin, int64_t w, uint8_t *choice)
+__device__ __forceinline__ double carrier_psi(const double *stat, int H, int64_t nwin, double period, int64_t w, uint8_t *choice)
 {
     int best = 0;
     double bx = stat[2 * w];
@@ -98,17 +124,17 @@ __device__ __forceinline__ double carrier_psi(const double *stat, int H, int64_t
     }
     if (choice) choice[w] = (uint8_t)best;
     const double by = stat[2 * ((int64_t)best * nwin + w) + 1];
-    const double base = (double)best * kCarrierPi;
+    const double base = (double)best * period;
     const double off = base / (double)H;
     const double at = atan2(-by, -bx);
     return off + at;
 }
 
-__global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const double *__restrict__ stat, int H, int64_t nwin, int span, double *tmp,
+__global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const double *__restrict__ stat, int H, int64_t nwin, int span, double period, double *tmp,
                                                                         double *__restrict__ phase, uint8_t *__restrict__ choice)
 {
     __shared__ double s_seg[TRACK_THREADS];
-    for (int64_t w = threadIdx.x; w < nwin; w += TRACK_THREADS) tmp[w] = carrier_psi(stat, H, nwin, w, choice);      // ψ_w, once per window
+    for (int64_t w = threadIdx.x; w < nwin; w += TRACK_THREADS) tmp[w] = carrier_psi(stat, H, nwin, period, w, choice);      // ψ_w, once per window
     __syncthreads();
     // u_w = ψ_0 + Σ_{j <= w} wrap(ψ_j - ψ_{j-1}) as a blocked scan: thread t owns the windows [a, e), adds its own steps, thread 0
     // adds the 1024 segment sums in order, and every thread rewrites its ψ_w as offset + its running sum (ψ_{a-1}, the one value it
@@ -119,7 +145,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const doub
     double sum = 0.0, prev = before;
     for (int64_t w = a; w < e; ++w) {
         const double psi = tmp[w];
-        sum += w == 0 ? psi : carrier_wrap_pi(psi - prev);
+        sum += w == 0 ? psi : carrier_wrap(psi - prev, period);
         prev = psi;
     }
     s_seg[threadIdx.x] = sum;
@@ -138,7 +164,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const doub
     prev = before;
     for (int64_t w = a; w < e; ++w) {
         const double psi = tmp[w];
-        sum += w == 0 ? psi : carrier_wrap_pi(psi - prev);
+        sum += w == 0 ? psi : carrier_wrap(psi - prev, period);
         prev = psi;
         tmp[w] = off + sum;
     }
@@ -152,8 +178,8 @@ __global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const doub
     }
 }
 
-__global__ __launch_bounds__(CARRIER_THREADS) void rows_derotate_kernel(const double2 *rows, int64_t n, int W, const double *__restrict__ phase, int64_t nwin,
-                                                                        double phase0, double2 *out)
+__global__ __launch_bounds__(CARRIER_THREADS) void rows_derotate_kernel(const double2 *rows, int64_t n, int nvals, int W, const double *__restrict__ phase,
+                                                                        int64_t nwin, double phase0, double2 *out)
 {
     const double c0 = 0.5 * (double)(W - 1);
     for (int64_t k = (int64_t)blockIdx.x * CARRIER_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * CARRIER_THREADS) {
@@ -177,10 +203,9 @@ __global__ __launch_bounds__(CARRIER_THREADS) void rows_derotate_kernel(const do
         const double tot = phase0 + phi;
         double sn, cs;
         sincos(-tot, &sn, &cs);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const double2 z = rows[3 * k + j];
-            out[3 * k + j] = make_double2(z.x * cs - z.y * sn, z.x * sn + z.y * cs);
+        for (int j = 0; j < nvals; ++j) {
+            const double2 z = rows[(int64_t)nvals * k + j];
+            out[(int64_t)nvals * k + j] = make_double2(z.x * cs - z.y * sn, z.x * sn + z.y * cs);
         }
     }
 }
@@ -217,17 +242,61 @@ extern "C" int wf_carrier_stat(wf_ctx *ctx, const double *d_rows, const uint8_t 
     return WF_OK;
 }
 
-extern "C" int wf_carrier_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double *d_phase, uint8_t *d_choice, void *stream)
+extern "C" int wf_carrier_stat_terms(wf_ctx *ctx, const double *d_term, int64_t ncalls, int W, double *d_stat, void *stream)
 {
-    WF_REQUIRE(ctx && d_stat_h && d_phase && d_choice, "wf_carrier_track: NULL argument");
-    WF_REQUIRE(H >= 1 && H <= 256, "wf_carrier_track: H must be 1 .. 256");
-    WF_REQUIRE(nwin >= 1 && nwin <= ((int64_t)1 << 40), "wf_carrier_track: nwin must be at least 1");
-    WF_REQUIRE(span >= 1 && span % 2 == 1, "wf_carrier_track: span must be odd and at least 1");
-    WF_REQUIRE(!carrier_mis(d_stat_h, 7) && !carrier_mis(d_phase, 7), "wf_carrier_track: stat and phase must be 8-byte aligned");
+    WF_REQUIRE(ctx && d_term && d_stat, "wf_carrier_stat_terms: NULL argument");
+    WF_REQUIRE(ncalls >= 1, "wf_carrier_stat_terms: ncalls must be at least 1");
+    WF_REQUIRE(carrier_window_ok(W), "wf_carrier_stat_terms: W must be a multiple of 64 from 64 to 8192");
+    WF_REQUIRE(!carrier_mis(d_term, 15) && !carrier_mis(d_stat, 7), "wf_carrier_stat_terms: terms must be 16-byte and stat 8-byte aligned");
+    const int64_t nwin = (ncalls + W - 1) / W;
+    WF_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(carrier_stat_terms_kernel, dim3((unsigned)((nwin + CARRIER_WAVES - 1) / CARRIER_WAVES)), dim3(CARRIER_THREADS), 0, wf_stream(stream),
+                       reinterpret_cast<const double2 *>(d_term), ncalls, W, nwin, d_stat);
+    WF_LAUNCH_CHECK();
+    return WF_OK;
+}
+
+static int carrier_track_run(const char *who, wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, double *d_phase,
+                             uint8_t *d_choice, void *stream)
+{
+    WF_REQUIRE(ctx && d_stat_h && d_phase && d_choice, "%s: NULL argument", who);
+    WF_REQUIRE(H >= 1 && H <= 256, "%s: H must be 1 .. 256", who);
+    WF_REQUIRE(nwin >= 1 && nwin <= ((int64_t)1 << 40), "%s: nwin must be at least 1", who);
+    WF_REQUIRE(span >= 1 && span % 2 == 1, "%s: span must be odd and at least 1", who);
+    WF_REQUIRE(std::isfinite(period) && period > 0.0 && period <= kCarrierTwoPi, "%s: period must be in (0, 2 pi]", who);
+    WF_REQUIRE(!carrier_mis(d_stat_h, 7) && !carrier_mis(d_phase, 7), "%s: stat and phase must be 8-byte aligned", who);
     WF_HIP(hipSetDevice(ctx->device));
     const int rc = wf_ctx_reserve_vit(ctx, (size_t)nwin);
     if (rc) return rc;
-    hipLaunchKernelGGL(carrier_track_kernel, dim3(1), dim3(TRACK_THREADS), 0, wf_stream(stream), d_stat_h, H, nwin, span, ctx->d_vit_edge, d_phase, d_choice);
+    hipLaunchKernelGGL(carrier_track_kernel, dim3(1), dim3(TRACK_THREADS), 0, wf_stream(stream), d_stat_h, H, nwin, span, period, ctx->d_vit_edge, d_phase,
+                       d_choice);
+    WF_LAUNCH_CHECK();
+    return WF_OK;
+}
+
+extern "C" int wf_carrier_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double *d_phase, uint8_t *d_choice, void *stream)
+{
+    return carrier_track_run("wf_carrier_track", ctx, d_stat_h, H, nwin, span, kCarrierPi, d_phase, d_choice, stream);
+}
+
+extern "C" int wf_carrier_track_mod(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, double *d_phase, uint8_t *d_choice,
+                                    void *stream)
+{
+    return carrier_track_run("wf_carrier_track_mod", ctx, d_stat_h, H, nwin, span, period, d_phase, d_choice, stream);
+}
+
+static int rows_derotate_run(const char *who, wf_ctx *ctx, const double *d_rows, int64_t ncalls, int nvals, int W, const double *d_phase, int64_t nwin,
+                             double phase0, double *d_out, void *stream)
+{
+    WF_REQUIRE(ctx && d_rows && d_out, "%s: NULL argument", who);
+    WF_REQUIRE(ncalls >= 1, "%s: ncalls must be at least 1", who);
+    WF_REQUIRE(nvals >= 1 && nvals <= 64, "%s: nvals must be 1 .. 64", who);
+    WF_REQUIRE(std::isfinite(phase0), "%s: phase0 must be finite", who);
+    WF_REQUIRE(!d_phase || (carrier_window_ok(W) && nwin >= 1), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
+    WF_REQUIRE(!carrier_mis(d_rows, 15) && !carrier_mis(d_out, 15) && !carrier_mis(d_phase, 7), "%s: rows must be 16-byte and phase 8-byte aligned", who);
+    WF_HIP(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(rows_derotate_kernel, dim3(wf_grid_for(ncalls, CARRIER_THREADS, 1 << 16)), dim3(CARRIER_THREADS), 0, wf_stream(stream),
+                       reinterpret_cast<const double2 *>(d_rows), ncalls, nvals, d_phase ? W : 64, d_phase, nwin, phase0, reinterpret_cast<double2 *>(d_out));
     WF_LAUNCH_CHECK();
     return WF_OK;
 }
@@ -235,14 +304,11 @@ extern "C" int wf_carrier_track(wf_ctx *ctx, const double *d_stat_h, int H, int6
 extern "C" int wf_rows_derotate(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int W, const double *d_phase, int64_t nwin, double phase0, double *d_out,
                                 void *stream)
 {
-    WF_REQUIRE(ctx && d_rows && d_out, "wf_rows_derotate: NULL argument");
-    WF_REQUIRE(ncalls >= 1, "wf_rows_derotate: ncalls must be at least 1");
-    WF_REQUIRE(std::isfinite(phase0), "wf_rows_derotate: phase0 must be finite");
-    WF_REQUIRE(!d_phase || (carrier_window_ok(W) && nwin >= 1), "wf_rows_derotate: W must be a multiple of 64 from 64 to 8192 and nwin at least 1");
-    WF_REQUIRE(!carrier_mis(d_rows, 15) && !carrier_mis(d_out, 15) && !carrier_mis(d_phase, 7), "wf_rows_derotate: rows must be 16-byte and phase 8-byte aligned");
-    WF_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(rows_derotate_kernel, dim3(wf_grid_for(ncalls, CARRIER_THREADS, 1 << 16)), dim3(CARRIER_THREADS), 0, wf_stream(stream),
-                       reinterpret_cast<const double2 *>(d_rows), ncalls, d_phase ? W : 64, d_phase, nwin, phase0, reinterpret_cast<double2 *>(d_out));
-    WF_LAUNCH_CHECK();
-    return WF_OK;
+    return rows_derotate_run("wf_rows_derotate", ctx, d_rows, ncalls, 3, W, d_phase, nwin, phase0, d_out, stream);
+}
+
+extern "C" int wf_rows_derotate_n(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int nvals, int W, const double *d_phase, int64_t nwin, double phase0,
+                                  double *d_out, void *stream)
+{
+    return rows_derotate_run("wf_rows_derotate_n", ctx, d_rows, ncalls, nvals, W, d_phase, nwin, phase0, d_out, stream);
 }

@@ -10,6 +10,8 @@
 //   * inc'(s, u) = inc(s, u) + Π(u) for u != 0, one addition on the branch, before the exchange
 //     (forward) and before the minimum (backward);
 //   * the λ step leaves the own bit's prior out and keeps the other bit's (M = 4).
+// The last launch also carries BR (plain only): true adds the decided branch and its term per call (wf_cpm_soft_branch,
+// wf_cpm_carrier.hip); false compiles to the code without it.
 // The kernels themselves are thin wrappers around the cs_*_body functions, so each file names its own.
 #pragma once
 #include <stddef.h>
@@ -208,10 +210,16 @@ __device__ __forceinline__ void cs_bwd(const cs_lane<M, LP, AP> &L, const cpm_so
 
 // λ_{k,i} (into lam, uniform across the wave) from a = ã_k(s) and b = b̃_{k+1}, then b -> b̃_k.  AP: λᵉ — bit i's minima
 // run over inc plus the prior of the OTHER bit of u where that bit is 1 (M = 2: over inc alone) — and π_{k,i} into pi.
-template <int M, int LP, bool AP>
+// BR (plain only): the branch b* = M s* + u* with the smallest T = tt over the wave, ties to the smallest b, and its term q = (x, y)
+// (include/wfhip.h, wf_cpm_soft_branch).  The argmin lives in the lanes: per-lane minimum over u, the wave-wide minimum (the
+// smaller of the two minima bit 0's λ has just taken: every (s, u) is in one of them), a ballot of the lanes that hold it —
+// the lowest is s* — and the smallest u of that lane that attains it.  bsel = b* in lane s*, -1 in every other lane; q is
+// formed in lane s* alone.  Every T is >= +0 and never -0: equal operands are bitwise equal.
+template <int M, int LP, bool AP, bool BR = false>
 __device__ __forceinline__ void cs_llr(const cs_lane<M, LP, AP> &L, const cpm_soft_params &P, int t, int tilt, int kv, double a, double &b,
-                                       double lam[cs_lane<M, LP, AP>::LGM], double pi[cs_lane<M, LP, AP>::LGM])
+                                       double lam[cs_lane<M, LP, AP>::LGM], double pi[cs_lane<M, LP, AP>::LGM], int &bsel, double2 &q)
 {
+    static_assert(!(AP && BR), "the branch output is the plain detector's");
     double inc[M], g[M], tt[M];
     cs_incs(L, P, t, tilt, inc);
     cs_gather(L, kv, b, g);
@@ -219,11 +227,41 @@ __device__ __forceinline__ void cs_llr(const cs_lane<M, LP, AP> &L, const cpm_so
     if constexpr (!AP) {
 #pragma unroll
         for (int u = 0; u < M; ++u) tt[u] = (av + inc[u]) + g[u];
+        double w1, w0;                               // bit 0's two minima over the wave: the smaller is the minimum of all T
         if constexpr (M == 2) {
-            lam[0] = wide_wave_min(tt[1]) - wide_wave_min(tt[0]);
+            w1 = wide_wave_min(tt[1]);
+            w0 = wide_wave_min(tt[0]);
+            lam[0] = w1 - w0;
         } else {                                     // bit 0 = MSB of U: 1 for U in {2, 3}; bit 1 = LSB: 1 for U in {1, 3}
-            lam[0] = wide_wave_min(wide_min_raw(tt[2], tt[3])) - wide_wave_min(wide_min_raw(tt[0], tt[1]));
+            w1 = wide_wave_min(wide_min_raw(tt[2], tt[3]));
+            w0 = wide_wave_min(wide_min_raw(tt[0], tt[1]));
+            lam[0] = w1 - w0;
             lam[1] = wide_wave_min(wide_min_raw(tt[1], tt[3])) - wide_wave_min(wide_min_raw(tt[0], tt[2]));
+        }
+        if constexpr (BR) {
+            double lm = tt[0];
+#pragma unroll
+            for (int u = 1; u < M; ++u) lm = wide_min_raw(lm, tt[u]);
+            const double wm = wide_min_raw(w1, w0);  // = wide_wave_min(lm): no further pass over the wave
+            const unsigned long long held = __builtin_amdgcn_ballot_w64(lm == wm);       // (lanes that hold no state carry +inf)
+            const int sstar = held ? __builtin_ctzll(held) : 0;                          // (held = 0: rows that are not finite)
+            bsel = -1;
+            if (L.lane == sstar) {
+                int us = M - 1;
+                double x = inc[M - 1];
+#pragma unroll
+                for (int u = M - 2; u >= 0; --u) {
+                    const bool hit = tt[u] == wm;
+                    us = hit ? u : us;
+                    x = hit ? inc[u] : x;
+                }
+                int r = L.v2 - tilt;
+                r += r < 0 ? 2 * P.p : 0;
+                const double cr = L.rot[r], sr = L.rot[CPM_ROT_SIN + r];
+                const double2 z = L.rowbuf[t * cs_lane<M, LP, AP>::NF + L.zoff + us];
+                bsel = M * sstar + us;
+                q = make_double2(x, -fma(cr, z.y, -(sr * z.x)));
+            }
         }
     } else {
         cs_pi(L, t, pi);
@@ -436,11 +474,12 @@ __device__ __forceinline__ void cs_repair_body(char *smem, double *rot, const do
 }
 
 // ring_all: CS_WAVES * CS_SUB * 64 doubles — ã of the sub-block, lane-private columns.  AP: out = λᵉ, bits = (λᵉ + π) < 0.
-template <int M, int LP, bool AP>
+// BR: lane s* of call k writes branch[k] and, where term is not NULL, term[k] (1 + 16 bytes a call).
+template <int M, int LP, bool AP, bool BR = false>
 __device__ __forceinline__ void cs_llr_body(char *smem, double *ring_all, double *rot, const double2 *__restrict__ rows,
                                             const double2 *__restrict__ rot_cs, const uint64_t *__restrict__ bedge, const double *__restrict__ ckpt,
                                             double *__restrict__ llr, uint8_t *__restrict__ bits, const cpm_soft_params &P,
-                                            const cpm_soft_prior &prior)
+                                            const cpm_soft_prior &prior, uint8_t *__restrict__ branch = nullptr, double2 *__restrict__ term = nullptr)
 {
     constexpr int LGM = cs_lane<M, LP, AP>::LGM;
     cs_stage_rot(rot_cs, P, rot);
@@ -463,7 +502,15 @@ __device__ __forceinline__ void cs_llr_body(char *smem, double *ring_all, double
         });
         cs_sweep<M, LP, false>(L, P, k0, k1, [&](int64_t k, int t, int tilt, int kv) __attribute__((always_inline)) {
             double lam[LGM], pi[LGM];
-            cs_llr(L, P, t, tilt, kv, ring[(int)(k - k0) * 64], b, lam, pi);
+            int bsel = -1;
+            double2 q = make_double2(0.0, 0.0);
+            cs_llr<M, LP, AP, BR>(L, P, t, tilt, kv, ring[(int)(k - k0) * 64], b, lam, pi, bsel, q);
+            if constexpr (BR) {
+                if (bsel >= 0) {
+                    branch[k] = (uint8_t)bsel;
+                    if (term) term[k] = q;
+                }
+            }
             if (L.lane < LGM) {
                 const double v = LGM == 1 || L.lane == 0 ? lam[0] : lam[LGM - 1];
                 llr[LGM * k + L.lane] = v;
@@ -549,6 +596,9 @@ static void cs_build_tables(const wf_cpm_detector_config *d, cpm_soft_params &P)
         }
     }
 }
+
+// wf_cpm_soft's launches but the last — bounds, proof and repairs of both directions — into the context's scratch (wf_cpm_soft.hip)
+int cpm_soft_front(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, const double2 *rows, const double2 *rot, hipStream_t s);
 
 // the launch parameters of one burst (tables, geometry) — after the arguments have been checked
 static void cs_fill_params(const wf_cpm_detector_config *det, const cs_geom &g, int64_t ncalls, int64_t first_call, cpm_soft_params &P)

@@ -79,9 +79,9 @@ extern "C" int wf_cpm_soft_geometry(wf_ctx *ctx, const wf_cpm_detector_config *d
     return WF_OK;
 }
 
+// every launch but the last: bounds, then proof and repairs in both directions
 template <int M, int LP>
-static int cs_run(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, const double2 *rows, const double2 *rot, double *llr, uint8_t *bits,
-                  hipStream_t s)
+static int cs_front(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, const double2 *rows, const double2 *rot, hipStream_t s)
 {
     uint64_t *fedge = reinterpret_cast<uint64_t *>(ctx->d_vit_edge), *bedge = fedge + g.off_b;
     double *ckpt = ctx->d_vit_edge + g.off_ck;
@@ -114,7 +114,24 @@ static int cs_run(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, const
             }
         }
     }
-    hipLaunchKernelGGL((cpm_soft_llr_kernel<M, LP>), dim3(grid), dim3(CS_THREADS), 0, s, rows, rot, bedge, ckpt, llr, bits, P);
+    return WF_OK;
+}
+
+// ... for the detectors whose last launch lives in another file (wf_cpm_carrier.hip: wf_cpm_soft_branch)
+int cpm_soft_front(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, const double2 *rows, const double2 *rot, hipStream_t s)
+{
+    if (P.M == 4) return P.Lp == 1 ? cs_front<4, 1>(ctx, P, g, rows, rot, s) : (P.Lp == 2 ? cs_front<4, 2>(ctx, P, g, rows, rot, s) : cs_front<4, 3>(ctx, P, g, rows, rot, s));
+    return P.Lp == 1 ? cs_front<2, 1>(ctx, P, g, rows, rot, s) : (P.Lp == 2 ? cs_front<2, 2>(ctx, P, g, rows, rot, s) : cs_front<2, 3>(ctx, P, g, rows, rot, s));
+}
+
+template <int M, int LP>
+static int cs_run(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, const double2 *rows, const double2 *rot, double *llr, uint8_t *bits,
+                  hipStream_t s)
+{
+    const int rc = cs_front<M, LP>(ctx, P, g, rows, rot, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL((cpm_soft_llr_kernel<M, LP>), dim3((unsigned)((g.nch + CS_WAVES - 1) / CS_WAVES)), dim3(CS_THREADS), 0, s, rows, rot,
+                       reinterpret_cast<const uint64_t *>(ctx->d_vit_edge) + g.off_b, ctx->d_vit_edge + g.off_ck, llr, bits, P);
     WF_LAUNCH_CHECK();
     return WF_OK;
 }

@@ -303,17 +303,62 @@ def carrier_stat(rows, branch, window: int, out=None, ctx=None):
     return out
 
 
-def carrier_track(stat, span: int = 1, ctx=None):
+def carrier_track(stat, span: int = 1, ctx=None, period=None):
     """Statistics of H hypothesis passes -> (phase f64[nwin], choice u8[nwin]) on device (``wf_carrier_track``; include/wfhip.h
-    states the definition).  ``stat``: contiguous device float64[H, nwin, 2], pass h over rows derotated by h π / H."""
+    states the definition).  ``stat``: contiguous device float64[H, nwin, 2], pass h over rows derotated by h π / H.
+    ``period``: the symmetry of the trellis in radians in place of π (``wf_carrier_track_mod``: 2π/p for the CPM detectors)."""
     if stat.dtype != _hip.torch().float64 or not stat.is_contiguous() or stat.dim() != 3 or stat.shape[2] != 2:
         raise ValueError("stat must be contiguous float64[H, nwin, 2]")
     H, nwin = int(stat.shape[0]), int(stat.shape[1])
     phase = _hip.empty(max(nwin, 1), "float64")
     choice = _hip.empty(max(nwin, 1) + 16, "uint8")
-    _hip.check(_hip.lib().wf_carrier_track(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), _hip.ptr(phase), _hip.ptr(choice),
-                                           _hip.stream()))
+    if period is None:
+        _hip.check(_hip.lib().wf_carrier_track(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), _hip.ptr(phase), _hip.ptr(choice),
+                                               _hip.stream()))
+    else:
+        _hip.check(_hip.lib().wf_carrier_track_mod(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), float(period), _hip.ptr(phase),
+                                                   _hip.ptr(choice), _hip.stream()))
     return phase[:nwin], choice[:nwin]
+
+
+def carrier_stat_terms(term, window: int, out=None, ctx=None):
+    """``carrier_stat`` from the terms ``cpm_soft_branch`` wrote (``wf_carrier_stat_terms``; include/wfhip.h states the
+    definition) -> device float64[nwin, 2] = (X_w, Y_w).  ``term``: contiguous device float64[ncalls, 2]."""
+    torch = _hip.torch()
+    if term.dtype != torch.float64 or not term.is_contiguous() or term.numel() % 2 or term.numel() == 0:
+        raise ValueError("term must be contiguous float64[ncalls, 2]")
+    ncalls = term.numel() // 2
+    nwin = -(-ncalls // int(window))
+    if out is None:
+        out = _hip.empty((nwin, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
+        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    _hip.check(_hip.lib().wf_carrier_stat_terms(_ctx(ctx), _hip.ptr(term), ncalls, int(window), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def rows_derotate_n(rows, nvals: int, window: int = 64, phase=None, phase0: float = 0.0, out=None, ctx=None):
+    """``rows_derotate`` for rows of ``nvals`` complex128 (``wf_rows_derotate_n``; include/wfhip.h states the definition): the
+    rows ``cpm_mf_rows`` writes, float64[ncalls, nvals, 2] (ARTM 16, PCM/FM 4).  ``out=rows`` works in place."""
+    torch = _hip.torch()
+    nvals = int(nvals)
+    if not 1 <= nvals <= 64:
+        raise ValueError(f"nvals = {nvals} outside 1 .. 64")
+    if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.numel() == 0 or rows.numel() % (2 * nvals):
+        raise ValueError(f"rows must be contiguous float64, a whole number of rows of {nvals} complex values")
+    ncalls = rows.numel() // (2 * nvals)
+    nwin = 0
+    if phase is not None:
+        if phase.dtype != torch.float64 or not phase.is_contiguous() or phase.numel() < 1:
+            raise ValueError("phase must be contiguous float64[nwin]")
+        nwin = int(phase.numel())
+    if out is None:
+        out = _hip.empty(tuple(rows.shape), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows.numel():
+        raise ValueError("out must be contiguous float64 of the rows' size")
+    _hip.check(_hip.lib().wf_rows_derotate_n(_ctx(ctx), _hip.ptr(rows), ncalls, nvals, int(window), _hip.ptr(phase), nwin,
+                                             float(phase0), _hip.ptr(out), _hip.stream()))
+    return out
 
 
 def rows_derotate(rows, window: int = 64, phase=None, phase0: float = 0.0, out=None, ctx=None):
@@ -417,6 +462,33 @@ def cpm_soft(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=N
     _hip.check(_hip.lib().wf_cpm_soft(_ctx(ctx), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n,
                                       int(first_call), int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.stream()))
     return llr[:n * lg], bits[:n * lg]
+
+
+def cpm_soft_branch(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None, terms: bool = True):
+    """``cpm_soft`` with the decided branch of every call and its phase term (``wf_cpm_soft_branch``; include/wfhip.h states
+    the definition) -> (llr f64[n lgM], bits u8[n lgM], branch u8[n], term f64[n, 2] or None) on device.  llr and bits are
+    bitwise ``cpm_soft``'s; branch[k] = M s* + u* of the section-k branch of a maximum-likelihood path, term[k] = (x, y) of
+    q_k on it.  ``d_rot``: the device rotation table; a rotated one (``sync.carrier_cpm.hypothesis_table``) detects the rows
+    derotated by its angle.  ``terms=False``: no term is written."""
+    from .viterbi.cpm import rotation_table
+
+    if not rows.is_contiguous():
+        raise ValueError("rows must be contiguous")
+    per = 2 * spec.nfilt
+    if rows.numel() % per:
+        raise ValueError(f"{rows.numel()} doubles of rows are not a whole number of {spec.nfilt}-filter rows")
+    n, lg = rows.numel() // per, spec.bits_per_symbol
+    if d_rot is None:
+        d_rot = _hip.to_device(rotation_table(spec))
+    llr = _hip.empty(max(n * lg, 1), "float64")
+    bits = _hip.empty(n * lg + 16, "uint8")
+    branch = _hip.empty(n + 16, "uint8")
+    term = _hip.empty((max(n, 1), 2), "float64") if terms else None
+    cfg = spec.c_config()
+    _hip.check(_hip.lib().wf_cpm_soft_branch(_ctx(ctx), ctypes.byref(cfg), _hip.ptr(d_rot), _hip.ptr(rows), n, int(first_call),
+                                             int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.ptr(branch), _hip.ptr(term),
+                                             _hip.stream()))
+    return llr[:n * lg], bits[:n * lg], branch[:n], (term[:n] if terms else None)
 
 
 def cpm_soft_apriori(rows, spec, apriori=None, apriori_scale: float = 1.0, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None):

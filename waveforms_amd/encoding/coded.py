@@ -25,7 +25,9 @@ buffer (``_Framed``).  With ``framing=None`` every class does exactly what it di
 The two SOQPSK-TG classes also take ``carrier=(theta0, nu)``, a carrier phase and frequency offset applied to the modulated
 signal (``carrier_offset``), and ``recovery``, a :class:`waveforms_amd.sync.carrier.CarrierRecovery` the rows pass through in
 front of the detector; ``recovery`` needs a ``framing`` (the phase comes back modulo π).  Both default to None: the same calls
-as before.
+as before.  The two CPM classes take the same pair with a :class:`waveforms_amd.sync.carrier_cpm.CPMCarrierRecovery`, which
+needs no framing: the phase comes back modulo 2π/p, a rotation that relabels the trellis's phase states and leaves the data
+alone.  Either class refuses the other's recovery.
 """
 from __future__ import annotations
 
@@ -81,13 +83,14 @@ class _Framed:
             if not (math.isfinite(theta0) and math.isfinite(nu)):
                 raise ValueError("carrier = (theta0, nu) must be finite")
             carrier = (theta0, nu)
-        if recovery is not None and self.framing is None:
-            raise ValueError("recovery needs a framing: the phase is recovered modulo π and the frame search's polarity resolves the rest")
+        if recovery is not None:
+            self._check_recovery(recovery)
         self.carrier, self.recovery = carrier, recovery
         self._carrier_phase = self._carrier_choice = None
 
     def carrier_result(self):
-        """(phase float64[nwin] in radians, modulo π; choice uint8[nwin]) of the last block's recovery - synchronises."""
+        """(phase float64[nwin] in radians, modulo π - modulo 2π/p on the CPM links; choice uint8[nwin]) of the last block's
+        recovery - synchronises."""
         if self.recovery is None or self._carrier_phase is None:
             raise RuntimeError("carrier_result needs a recovery and a block that ran")
         return _hip.to_host(self._carrier_phase), _hip.to_host(self._carrier_choice)
@@ -95,7 +98,7 @@ class _Framed:
     def _recovered(self, rows):
         if self.recovery is None:
             return rows
-        rows, self._carrier_phase, self._carrier_choice = self.recovery.recover(rows, True)
+        rows, self._carrier_phase, self._carrier_choice = self._recover(rows)
         return rows
 
     def _rate_db(self) -> float:
@@ -263,6 +266,17 @@ class _SOQPSK(_Link):
                                 np.exp(-1j * np.pi / 4))
         return rows, syms
 
+    def _check_recovery(self, recovery) -> None:
+        from ..sync.carrier import CarrierRecovery
+
+        if not isinstance(recovery, CarrierRecovery):
+            raise ValueError("an SOQPSK-TG link's recovery is a waveforms_amd.sync.carrier.CarrierRecovery")
+        if self.framing is None:
+            raise ValueError("recovery needs a framing: the phase is recovered modulo π and the frame search's polarity resolves the rest")
+
+    def _recover(self, rows):
+        return self.recovery.recover(rows, True)
+
     def _soft(self, rows):
         return dev.viterbi_soft(rows, True)
 
@@ -323,9 +337,22 @@ class _CPM(_Link):
         bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
         syms = dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
         sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
+        if self.carrier is not None:
+            dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
         received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
         rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
         return rows, syms
+
+    def _check_recovery(self, recovery) -> None:
+        from ..sync.carrier_cpm import CPMCarrierRecovery
+
+        if not isinstance(recovery, CPMCarrierRecovery):
+            raise ValueError("a CPM link's recovery is a waveforms_amd.sync.carrier_cpm.CPMCarrierRecovery")
+        if recovery.spec != self.spec:
+            raise ValueError(f"the recovery is for another design than the link's {self.waveform!r} full-phase trellis")
+
+    def _recover(self, rows):
+        return self.recovery.recover(rows)
 
     def _soft(self, rows):
         return dev.cpm_soft(rows, self.spec, 0, 0, d_rot=self._d_rot)
@@ -398,9 +425,9 @@ class CodedCPMLink(_LDPC, _CPM):
     first codeword at most lgM channel errors (one decoder iteration when there is no noise)."""
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0) -> None:
+                 lead_bits: int = 0, carrier=None, recovery=None) -> None:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
-        super().__init__(code, ncw, waveform, sps, framing=framing, lead_bits=lead_bits)
+        super().__init__(code, ncw, waveform, sps, framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
 
 
 class _LDPCLoop:
@@ -593,12 +620,14 @@ class IterativeCPMLink(_LDPCLoop, CodedCPMLink):
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False,
-                 prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None) -> None:
+                 prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None, carrier=None,
+                 recovery=None) -> None:
         if prior_warmup < 0:
             raise ValueError("prior_warmup must not be negative")
         self.prior_warmup = int(prior_warmup)
         super().__init__(code, ncw, waveform=waveform, sps=sps, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
-                         ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior)
+                         ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, carrier=carrier,
+                         recovery=recovery)
 
     def begin(self, ncalls: int | None = None) -> None:
         """Fresh loop state of one block: prior 0 on every bit of every call, every codeword open, no iterations."""

@@ -17,8 +17,9 @@ the pass whose Σ Re q is most negative.  The trellis is symmetric under a rotat
 Limits.  The phase must stay within the decision-directed pull-in across one window: the supported frequency offset is
 |nu| sps W <= ``MAX_DRIFT_TURNS`` turns per window (nu in cycles per sample), measured on ``recover_host``
 (tests/test_carrier.py).  No timing recovery; the hypothesis rotation is a pass of its own over the rows (not fused into
-the detector's row load); the recovery passes carry no prior; the CPM detectors are not covered.  H hypotheses cost H
-detections: the price of needing no sequential loop.
+the detector's row load); the recovery passes carry no prior.  H hypotheses cost H detections: the price of needing no
+sequential loop.  The CPM detectors (ARTM, PCM/FM) have the same scheme in ``waveforms_amd.sync.carrier_cpm``, which shares
+``carrier_track_host`` (with its period) and ``interpolate_phase_host`` with this module.
 """
 from __future__ import annotations
 
@@ -145,8 +146,13 @@ def branch_terms_host(rows, branch):
 def carrier_stat_host(rows, branch, window: int = DEFAULT_WINDOW) -> np.ndarray:
     """``wf_carrier_stat`` -> float64[nwin, 2] = (X_w, Y_w), in the header's order of additions: 64 lane partials per window
     (rows w W + 64 i + l, i increasing, from +0), then p_l += p_{l+d} for d = 32 .. 1."""
+    return stat_terms_host(*branch_terms_host(rows, branch), window)
+
+
+def stat_terms_host(x, y, window: int = DEFAULT_WINDOW) -> np.ndarray:
+    """(X_w, Y_w) from the terms themselves, in ``wf_carrier_stat``'s order of additions (``wf_carrier_stat_terms``)."""
     window = _check_window(window)
-    x, y = branch_terms_host(rows, branch)
+    x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
     n = x.size
     nwin = -(-n // window)
     out = np.empty((nwin, 2))
@@ -165,12 +171,20 @@ def carrier_stat_host(rows, branch, window: int = DEFAULT_WINDOW) -> np.ndarray:
     return out
 
 
+def _wrap(x, period):
+    return x - period * np.ceil(x / period - 0.5)
+
+
 def _wrap_pi(x):
-    return x - math.pi * np.ceil(x / math.pi - 0.5)
+    return _wrap(x, math.pi)
 
 
-def carrier_track_host(stat, span: int = DEFAULT_SPAN):
-    """``wf_carrier_track``: float64[H, nwin, 2] -> (phase f64[nwin], choice u8[nwin])."""
+def carrier_track_host(stat, span: int = DEFAULT_SPAN, period: float = math.pi):
+    """``wf_carrier_track``: float64[H, nwin, 2] -> (phase f64[nwin], choice u8[nwin]).  ``period``: the symmetry of the
+    trellis in place of π (``wf_carrier_track_mod``)."""
+    period = float(period)
+    if not (math.isfinite(period) and 0.0 < period <= 2.0 * math.pi):
+        raise ValueError(f"period = {period} outside (0, 2π]")
     stat = np.asarray(stat, dtype=np.float64)
     if stat.ndim == 2:
         stat = stat[None]
@@ -181,10 +195,10 @@ def carrier_track_host(stat, span: int = DEFAULT_SPAN):
     choice = np.argmin(stat[:, :, 0], axis=0)              # the first of equal minima
     w = np.arange(nwin)
     bx, by = stat[choice, w, 0], stat[choice, w, 1]
-    psi = (choice.astype(np.float64) * math.pi) / float(H) + np.arctan2(-by, -bx)
+    psi = (choice.astype(np.float64) * period) / float(H) + np.arctan2(-by, -bx)
     u = np.empty(nwin)
     u[0] = psi[0]
-    delta = _wrap_pi(psi[1:] - psi[:-1])
+    delta = _wrap(psi[1:] - psi[:-1], period)
     for j in range(1, nwin):
         u[j] = u[j - 1] + delta[j - 1]
     r = span // 2
