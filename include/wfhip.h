@@ -1033,6 +1033,55 @@ int wf_carrier_track_mod(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwi
 int wf_rows_derotate_n(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int nvals, int W, const double *d_phase, int64_t nwin,
                        double phase0, double *d_out, void *stream);
 
+/* ---- Symbol timing for the SOQPSK-TG receiver: the impairment, a resampling matched-filter bank and a feed-forward recovery --
+ * (The reference has no synchroniser; these entry points are defined here.  waveforms_amd/sync/timing.py restates each in
+ * numpy: lagrange_host, timing_offset_host, mf_bank_resample_host, timing_track_host, timing_refine_host.)  All float64.
+ * The cubic Lagrange weights of the nodes -1, 0, 1, 2 at a fraction μ in [0, 1):
+ *   c_-1 = -μ(μ-1)(μ-2)/6    c_0 = (μ+1)(μ-1)(μ-2)/2    c_1 = -(μ+1)μ(μ-2)/2    c_2 = (μ+1)μ(μ-1)/6
+ * (each the products left to right, then the division).
+ * wf_timing_offset_c128, the impairment at sample rate: the signal read at n + t_n,
+ *   t_n = tau0 + (eps * (double)(first_index + n))   (the product rounded, then the sum);   b_n = floor(t_n);   μ_n = t_n - b_n   (exact)
+ *   out_n = Σ_{i = -1 .. 2} c_i(μ_n) in[n + b_n + i],   a sample outside [0, n) counting as zero
+ * so (0, 0) returns the input.  OUT OF PLACE only: an output that overlaps the input is refused.  n < 1, first_index < 0,
+ * first_index + n > 2^53, tau0 or eps not finite, a NULL pointer, samples not 16-byte aligned or overlapping: WF_ERR_VALUE
+ * before anything is launched. */
+int wf_timing_offset_c128(wf_ctx *ctx, const double *d_in_ri, int64_t n, double tau0, double eps, int64_t first_index,
+                          double *d_out_ri, void *stream);
+/* Matched-filter rows at fractional, time-varying instants, in one pass over the samples.  With v_f(n) the full-rate value of
+ * wf_mf_bank_c128 (np.convolve(r, taps[f], "same")[n] for 0 <= n < nsamp, 0 elsewhere), row k < ncols samples the bank at
+ *   T_k = first + k step + tau0 + τ_k:   t = tau0 + τ_k;   B_k = first + k step + floor(t);   μ_k = t - floor(t)   (exact)
+ *   d_out[k][f] = Σ_{i = -1 .. 2} c_i(μ_k) v_f(B_k + i),    f < 3
+ * τ_k interpolates d_tau[nwin] exactly as wf_rows_derotate interpolates its phase (linear between the window centres
+ * w W + (W - 1) / 2, flat outside the first and the last; each operation rounded once); d_tau NULL: τ_k = 0 (W and nwin are
+ * then not read).  A t that is not finite (or at or beyond 2^62) writes a zero row.  Any finite trajectory is served: rows
+ * may fall before sample 0 or behind the last one, and neighbouring rows may be any distance apart.  The full-rate bank is
+ * never formed: by linearity the kernel interpolates each of the ntaps samples a row needs once and runs the three filters on
+ * them, so the result agrees with the definition to the rounding of a sum of ntaps + 4 terms, not bitwise.  d_taps_ri:
+ * 3 x ntaps complex128; d_out_ri: ncols 48-byte rows.  nfilt other than 3, ntaps even or outside 1 .. 255, step outside
+ * 1 .. 64, nsamp or ncols outside 1 .. 2^40, |first| > 2^40, tau0 not finite, (with d_tau) W outside 64 .. 8192 in steps of 64
+ * or nwin < 1, a NULL ctx / samples / taps / out, data not 16-byte or d_tau not 8-byte aligned: WF_ERR_VALUE before the context
+ * is touched. */
+int wf_mf_bank_resample_c128(wf_ctx *ctx, const double *d_r_ri, int64_t nsamp, const double *d_taps_ri, int nfilt, int ntaps,
+                             int64_t first, int step, int64_t ncols, int W, const double *d_tau, int64_t nwin, double tau0,
+                             double *d_out_ri, void *stream);
+/* The guarded vertex of the parabola through (-1, a), (0, b), (1, c): den = (a - b) + (c - b); V = 0.5 (a - c) / den if
+ * den > 0, otherwise 0 (three points that are not strictly convex have no minimum to offer), then clamped to ±lim.
+ * wf_timing_track: statistics -> a timing trajectory in samples.  d_stat_h: H x nwin x 2 float64 as wf_carrier_stat writes it
+ * (only X is read), pass h taken at the instant s_h = (h * (period / H)) - period / 2, 3 <= H <= 64.  Per window
+ *   i = argmin_h X_{h,w} (ties to the smallest h);   V = vertex(X_{(i-1) mod H}, X_i, X_{(i+1) mod H}), lim = 1/2
+ *   ψ_w = s_i + ((period / H) * V)
+ *   u_0 = ψ_0;  u_w = u_{w-1} + wrap(ψ_w - ψ_{w-1}),  wrap(x) = x - period ceil(x / period - 1/2)      (w increasing)
+ *   d_tau[w] = the centred mean of u over span windows, exactly as wf_carrier_track takes it
+ * d_choice: nwin bytes (i).  The running sum is a blocked scan through the context's detector scratch, as wf_carrier_track's:
+ * within (nwin + span + 8) 2^-53 (|ψ_0| + Σ |wrapped steps|) of a host statement.  H outside 3 .. 64, nwin < 1, span even or
+ * < 1, period not finite or not positive, a NULL pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_timing_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, double *d_tau,
+                    uint8_t *d_choice, void *stream);
+/* A refinement: d_stat3 is 3 x nwin x 2, taken at τ - δ, τ, τ + δ.  d_more[w] = the centred mean over span windows of
+ * δ * vertex(X_{0,w}, X_{1,w}, X_{2,w}) with lim = 1; no unwrapping.  The caller adds d_more to τ.  nwin < 1, span even or < 1,
+ * delta not finite or not positive, a NULL pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_timing_refine(wf_ctx *ctx, const double *d_stat3, int64_t nwin, int span, double delta, double *d_more, void *stream);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

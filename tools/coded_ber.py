@@ -7,6 +7,7 @@ decoder's speed; prints ONE JSON line.
     python tools/coded_ber.py --code conv-k3|conv-k7 [--info-bits K] [--interleave] [--outer N --damping D] [--ebn0 ...]
     python tools/coded_ber.py --code conv-k3|conv-k7 --rs 16|8 [--rs-depth I] [--rs-n N] [--rs-erasures F [--rs-erase-below X]] ...
     python tools/coded_ber.py --carrier-phase DEG --carrier-freq NU --recover [--carrier-window W --carrier-hyp H] [--ebn0 ...]
+    python tools/coded_ber.py --timing-offset TAU --timing-drift EPS --recover-timing [--timing-window W --timing-hyp H --timing-refine R]
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -64,6 +65,12 @@ unframed CodedCPMLink and the recovery is ``CPMCarrierRecovery`` (``--carrier-hy
 block (device events around every stage, summed over the passes, ``--steps`` blocks after one warm-up) beside one plain soft
 detection of the same rows, and ``loss_db_at_fer_1e-2``: recovered minus genie, both interpolated in log FER (null where a
 curve does not cross 1e-2 inside the sweep).
+
+With ``--timing-offset TAU`` (samples) / ``--timing-drift EPS`` (samples per sample) and ``--recover-timing`` the tool does the
+same for the symbol timing of the framed SOQPSK-TG link: ``genie`` (no offset), ``impaired`` (``timing=(TAU, EPS)``, no recovery)
+and ``recovered`` (the offset and ``TimingRecovery`` with ``--timing-window``, ``--timing-hyp``, ``--timing-span``,
+``--timing-refine``, ``--timing-delta``) on the same blocks, the recovery's stage times beside the fused front end and one
+soft detection, and the same ``loss_db_at_fer_1e-2``.
 """
 import argparse
 import json
@@ -210,6 +217,87 @@ def main_carrier(args) -> None:
         point["recovery_ms_per_block"]["total"] = round(sum(tot.values()) / n, 4)
         point["soft_detector_ms"] = round(soft_ms / n, 4)
         point["burst_rows"] = int(rows.shape[0])
+        out["points"].append(point)
+    g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
+    out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
+    out["loss_db_at_fer_1e-2"] = None if g is None or r is None else round(r - g, 3)
+    print(json.dumps(out))
+
+
+def main_timing(args) -> None:
+    """The ``--recover-timing`` form: genie, impaired and recovered FRAMED SOQPSK-TG links on the same blocks."""
+    import torch
+
+    from waveforms_amd import device as dev
+    from waveforms_amd.encoding import ldpc
+    from waveforms_amd.encoding.coded import TIMING_OFFSET, CodedSOQPSKLink
+    from waveforms_amd.encoding.framing import Framing
+    from waveforms_amd.sync.timing import MAX_DRIFT_SAMPLES, TimingRecovery
+
+    torch.cuda.set_device(0)
+    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
+    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
+    timing = (args.timing_offset, args.timing_drift)
+    fr = Framing(code)
+    kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
+    sps = 8
+    rec = TimingRecovery(sps, args.timing_window, args.timing_span, args.timing_hyp, args.timing_refine, args.timing_delta)
+    links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, timing=timing, **kw),
+             "recovered": CodedSOQPSKLink(code, per, timing=timing, timing_recovery=rec, **kw)}
+    out = {"tool": "coded_ber", "form": "timing", "waveform": "soqpsk", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
+           "detector": args.detector, "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
+           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * sps * rec.window,
+                      "documented_limit_samples_per_window": MAX_DRIFT_SAMPLES},
+           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine, "delta": rec.delta}, "points": []}
+    for e in args.ebn0:
+        point = {"ebn0_info_db": e}
+        b = 0
+        for name, lk in links.items():
+            lk.reset_counts()
+            b = 0
+            while b * per < args.codewords:
+                lk.run_block(e, seed=1, stream_id=b)
+                b += 1
+            be, fe, nc, m, mean_it = lk.result()
+            ue, um = (None, None) if name == "recovered" else lk.uncoded_result()     # (a recovered link does not count channel bits)
+            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
+                           "mean_iters": round(mean_it, 3), "uncoded_ber": None if um is None else ue / um, "wrong_locks": lk.sync_result()[1],
+                           "last_lock": lk.sync_result()[2][0]}
+        point["codewords"] = b * per
+        # the recovery's stages on one burst's noisy samples, each bracketed by device events, beside the fused front end
+        # (channel + bank, what the genie link runs) and one plain soft detection of its rows
+        lk = links["recovered"]
+        tx = dev.ldpc_encode(code, lk.info_bits(b))
+        bits = torch.cat((lk.channel_bits(tx, b), lk._pad))
+        sig = dev.timing_offset(dev.cpm_modulate(dev.fsm_encode(*lk._tables, bits)[0], lk._d_h, lk._d_pulse, sps), *timing)
+        first, ncols = dev.decimation(int(sig.shape[0]), sps, 2, TIMING_OFFSET[args.detector])
+        received = dev.awgn(sig, int(sig.shape[0]), lk.sigma(e), 1, b, 0, np.exp(-1j * np.pi / 4))
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        tot, front_ms, soft_ms = {}, 0.0, 0.0
+        rec.times = True
+        for s in range(args.steps + 1):
+            rec.recover(received, lk._d_taps, first, ncols, True)
+            t = rec.stage_times()
+            ev[0].record()
+            rows = dev.awgn_mf_bank(sig, lk._d_taps, first, sps, ncols, lk.sigma(e), 1, b, 0, np.exp(-1j * np.pi / 4))
+            ev[1].record()
+            dev.viterbi_soft(rows, True)
+            ev[2].record()
+            torch.cuda.synchronize()
+            if s:                                                         # (the first round warms up)
+                front_ms += ev[0].elapsed_time(ev[1])
+                soft_ms += ev[1].elapsed_time(ev[2])
+                for k, v in t.items():
+                    tot[k] = tot.get(k, 0.0) + v
+        rec.times = False
+        n = max(args.steps, 1)
+        point["recovery_ms_per_block"] = {k: round(v / n, 4) for k, v in tot.items()}
+        point["recovery_ms_per_block"]["total"] = round(sum(tot.values()) / n, 4)
+        point["fused_front_end_ms"] = round(front_ms / n, 4)
+        point["soft_detector_ms"] = round(soft_ms / n, 4)
+        point["burst_rows"] = int(ncols)
+        tau = links["recovered"].timing_result()[0]
+        point["tau_samples"] = {"first": round(float(tau[0]), 3), "last": round(float(tau[-1]), 3), "windows": int(tau.size)}
         out["points"].append(point)
     g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
     out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
@@ -390,7 +478,21 @@ def main() -> None:
     ap.add_argument("--carrier-hyp", type=int, default=0, help="--recover: coarse hypotheses (0: 8 for SOQPSK-TG, the class's 2 for ARTM and PCM/FM)")
     ap.add_argument("--carrier-span", type=int, default=5, help="--recover: windows of the centred mean")
     ap.add_argument("--carrier-refine", type=int, default=1, help="--recover: refinement passes")
+    ap.add_argument("--timing-offset", type=float, default=0.0, help="timing offset of the modulated signal, samples")
+    ap.add_argument("--timing-drift", type=float, default=0.0, help="timing drift, samples per sample")
+    ap.add_argument("--recover-timing", action="store_true", help="genie, impaired and recovered framed links on the same blocks (TimingRecovery)")
+    ap.add_argument("--timing-window", type=int, default=256, help="--recover-timing: rows per window")
+    ap.add_argument("--timing-hyp", type=int, default=8, help="--recover-timing: coarse hypotheses over two symbols")
+    ap.add_argument("--timing-span", type=int, default=5, help="--recover-timing: windows of the centred mean")
+    ap.add_argument("--timing-refine", type=int, default=1, help="--recover-timing: refinement rounds")
+    ap.add_argument("--timing-delta", type=float, default=2.0, help="--recover-timing: spacing of a refinement's three points, samples")
     args = ap.parse_args()
+    if args.recover_timing or args.timing_offset or args.timing_drift:
+        if not args.recover_timing:
+            ap.error("--timing-offset / --timing-drift go with --recover-timing")
+        if args.waveform != "soqpsk" or args.code.startswith("conv") or args.outer or args.live_only or args.recover:
+            ap.error("--recover-timing is the framed CodedSOQPSKLink's: SOQPSK-TG, an LDPC code, no --outer / --live-only / --recover")
+        return main_timing(args)
     if args.recover or args.carrier_phase or args.carrier_freq:
         if not args.recover:
             ap.error("--carrier-phase / --carrier-freq go with --recover")

@@ -139,6 +139,10 @@ SIGNATURES = {
     "wf_carrier_stat_terms": (c_int, [_P, _P, c_int64, c_int, _P, _P]),
     "wf_carrier_track_mod": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, _P, _P, _P]),
     "wf_rows_derotate_n": (c_int, [_P, _P, c_int64, c_int, c_int, _P, c_int64, c_double, _P, _P]),
+    "wf_timing_offset_c128": (c_int, [_P, _P, c_int64, c_double, c_double, c_int64, _P, _P]),
+    "wf_mf_bank_resample_c128": (c_int, [_P, _P, c_int64, _P, c_int, c_int, c_int64, c_int, c_int64, c_int, _P, c_int64, c_double, _P, _P]),
+    "wf_timing_track": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, _P, _P, _P]),
+    "wf_timing_refine": (c_int, [_P, _P, c_int64, c_int, c_double, _P, _P]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

@@ -381,6 +381,74 @@ def rows_derotate(rows, window: int = 64, phase=None, phase0: float = 0.0, out=N
     return out
 
 
+def timing_offset(signal, tau0: float, eps: float, first_index: int = 0, out=None):
+    """The timing impairment at sample rate (``wf_timing_offset_c128``; include/wfhip.h states the definition): the signal read
+    at n + tau0 + eps (first_index + n) by cubic Lagrange interpolation, samples outside the burst counting as zero.
+    ``signal``: contiguous device float64[n, 2].  Out of place only: ``out`` must not overlap ``signal``."""
+    torch = _hip.torch()
+    if signal.dtype != torch.float64 or not signal.is_contiguous() or signal.numel() % 2 or signal.numel() == 0:
+        raise ValueError("signal must be contiguous float64[n, 2]")
+    n = signal.numel() // 2
+    if out is None:
+        out = _hip.empty((n, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != signal.numel():
+        raise ValueError("out must be contiguous float64[n, 2]")
+    _hip.check(_hip.lib().wf_timing_offset_c128(_hip.ctx(), _hip.ptr(signal), n, float(tau0), float(eps), int(first_index), _hip.ptr(out),
+                                                _hip.stream()))
+    return out
+
+
+def mf_bank_resample(received, taps, first: int, step: int, ncols: int, window: int = 64, tau=None, tau0: float = 0.0, out=None, ctx=None):
+    """Matched-filter rows at the instants first + k step + tau0 + τ_k (``wf_mf_bank_resample_c128``; include/wfhip.h states the
+    definition) -> device float64[ncols, 3, 2].  ``received``: contiguous device float64[nsamp, 2]; ``taps``: float64[3, ntaps, 2],
+    ntaps odd; ``tau``: device float64[nwin] in samples, interpolated between the centres of the windows of ``window`` rows as
+    ``rows_derotate`` interpolates its phase (None: τ = 0).  ``first`` may be negative and rows may run past the end."""
+    torch = _hip.torch()
+    if received.dtype != torch.float64 or not received.is_contiguous() or received.numel() % 2 or received.numel() == 0:
+        raise ValueError("received must be contiguous float64[nsamp, 2]")
+    if taps.dtype != torch.float64 or not taps.is_contiguous() or taps.dim() != 3 or taps.shape[2] != 2:
+        raise ValueError("taps must be contiguous float64[3, ntaps, 2]")
+    nsamp, ncols = received.numel() // 2, int(ncols)
+    nfilt, ntaps = int(taps.shape[0]), int(taps.shape[1])
+    nwin = 0
+    if tau is not None:
+        if tau.dtype != torch.float64 or not tau.is_contiguous() or tau.numel() < 1:
+            raise ValueError("tau must be contiguous float64[nwin]")
+        nwin = int(tau.numel())
+    if out is None:
+        out = _hip.empty((max(ncols, 1), 3, 2), "float64")[:max(ncols, 0)]
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 6 * ncols:
+        raise ValueError(f"out must be contiguous float64[{ncols}, 3, 2]")
+    _hip.check(_hip.lib().wf_mf_bank_resample_c128(_ctx(ctx), _hip.ptr(received), nsamp, _hip.ptr(taps), nfilt, ntaps, int(first), int(step), ncols,
+                                                   int(window), _hip.ptr(tau), nwin, float(tau0), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def timing_track(stat, period: float, span: int = 1, ctx=None):
+    """Statistics of H timing hypotheses -> (tau f64[nwin] in samples, choice u8[nwin]) on device (``wf_timing_track``;
+    include/wfhip.h states the definition).  ``stat``: contiguous device float64[H, nwin, 2] as ``carrier_stat`` writes it, pass
+    h taken at the instant -period/2 + h period/H; only X is read."""
+    if stat.dtype != _hip.torch().float64 or not stat.is_contiguous() or stat.dim() != 3 or stat.shape[2] != 2:
+        raise ValueError("stat must be contiguous float64[H, nwin, 2]")
+    H, nwin = int(stat.shape[0]), int(stat.shape[1])
+    tau = _hip.empty(max(nwin, 1), "float64")
+    choice = _hip.empty(max(nwin, 1) + 16, "uint8")
+    _hip.check(_hip.lib().wf_timing_track(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), float(period), _hip.ptr(tau), _hip.ptr(choice),
+                                          _hip.stream()))
+    return tau[:nwin], choice[:nwin]
+
+
+def timing_refine(stat3, delta: float, span: int = 1, ctx=None):
+    """Statistics at τ - δ, τ, τ + δ -> the correction to τ, f64[nwin] in samples, on device (``wf_timing_refine``; include/wfhip.h
+    states the definition).  ``stat3``: contiguous device float64[3, nwin, 2]."""
+    if stat3.dtype != _hip.torch().float64 or not stat3.is_contiguous() or stat3.dim() != 3 or stat3.shape[0] != 3 or stat3.shape[2] != 2:
+        raise ValueError("stat3 must be contiguous float64[3, nwin, 2]")
+    nwin = int(stat3.shape[1])
+    more = _hip.empty(max(nwin, 1), "float64")
+    _hip.check(_hip.lib().wf_timing_refine(_ctx(ctx), _hip.ptr(stat3), nwin, int(span), float(delta), _hip.ptr(more), _hip.stream()))
+    return more[:nwin]
+
+
 def idd_windows(state, nrows: int, n_tx: int, period: int | None = None, row_offset: int = 1, lock=None, marker_bits: int = 0,
                 guard: int = 128, out=None, ctx=None):
     """The live windows of a burst from the decoder's freeze states (``wf_idd_windows``; include/wfhip.h states the definition,

@@ -28,6 +28,13 @@ front of the detector; ``recovery`` needs a ``framing`` (the phase comes back mo
 as before.  The two CPM classes take the same pair with a :class:`waveforms_amd.sync.carrier_cpm.CPMCarrierRecovery`, which
 needs no framing: the phase comes back modulo 2π/p, a rotation that relabels the trellis's phase states and leaves the data
 alone.  Either class refuses the other's recovery.
+
+The two SOQPSK-TG classes also take ``timing=(tau0, eps)``, a symbol timing offset and drift in samples applied to the modulated
+signal (``timing_offset``: the signal read at n + tau0 + eps n) in front of the unchanged channel, and ``timing_recovery``, a
+:class:`waveforms_amd.sync.timing.TimingRecovery`: the noisy samples are then materialised (``awgn``, the same rotation and the
+same noise coordinates as the fused front end's) and the recovery makes the detector's rows from them.  It needs a ``framing``
+(the instant comes back modulo two symbols: the rows may be two early or late) and excludes ``carrier`` and ``recovery``.  Both
+default to None: the same calls as before.
 """
 from __future__ import annotations
 
@@ -100,6 +107,37 @@ class _Framed:
             return rows
         rows, self._carrier_phase, self._carrier_choice = self._recover(rows)
         return rows
+
+    def _timing_init(self, timing, timing_recovery, sps: int, framing, carrier, recovery) -> None:
+        """``timing=(tau0, eps)``: the modulated signal is read at n + tau0 + eps n (``timing_offset``, in samples) in front of the
+        unchanged channel; ``timing_recovery``: a ``waveforms_amd.sync.timing.TimingRecovery`` that makes the detector's rows from
+        the noisy samples.  Both None: nothing is added to the chain.  Checked against the link's other keywords before anything
+        touches the device."""
+        if timing is not None:
+            tau0, eps = (float(v) for v in timing)
+            if not (math.isfinite(tau0) and math.isfinite(eps)):
+                raise ValueError("timing = (tau0, eps) must be finite")
+            timing = (tau0, eps)
+        if timing_recovery is not None:
+            from ..sync.timing import TimingRecovery
+
+            if not isinstance(timing_recovery, TimingRecovery):
+                raise ValueError("timing_recovery is a waveforms_amd.sync.timing.TimingRecovery")
+            if recovery is not None or carrier is not None:
+                raise ValueError("timing_recovery excludes carrier and recovery: joint timing and carrier acquisition is not implemented")
+            if timing_recovery.sps != sps:
+                raise ValueError(f"the timing recovery is for sps = {timing_recovery.sps}, the link has {sps}")
+            if framing is None:
+                raise ValueError("timing_recovery needs a framing: the instant is recovered modulo two symbols and the frame search absorbs the shift")
+        self.timing, self.timing_recovery = timing, timing_recovery
+        self._timing_tau = self._timing_choice = None
+
+    def timing_result(self):
+        """(tau float64[nwin] in samples, modulo two symbols; choice uint8[nwin]) of the last block's timing recovery -
+        synchronises."""
+        if self.timing_recovery is None or self._timing_tau is None:
+            raise RuntimeError("timing_result needs a timing_recovery and a block that ran")
+        return _hip.to_host(self._timing_tau), _hip.to_host(self._timing_choice)
 
     def _rate_db(self) -> float:
         """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""
@@ -230,10 +268,11 @@ class _SOQPSK(_Link):
 
     bits_per_symbol, _lam0 = 1, 1
 
-    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", **burst) -> None:
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", *, timing=None, timing_recovery=None, **burst) -> None:
         if detector not in TIMING_OFFSET:
             raise ValueError(f"unknown detector {detector!r}")
         self.detector = detector
+        self._timing_init(timing, timing_recovery, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -259,9 +298,15 @@ class _SOQPSK(_Link):
         sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
         if self.carrier is not None:
             dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
+        if self.timing is not None:
+            sig = dev.timing_offset(sig, self.timing[0], self.timing[1], 0)
         first, ncols = dev.decimation(int(sig.shape[0]), self.sps, 2, TIMING_OFFSET[self.detector])
         if ncols < self.nch + 1:
             raise RuntimeError(f"{ncols} detector rows for {self.nch} channel bits")
+        if self.timing_recovery is not None:
+            received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
+            rows, self._timing_tau, self._timing_choice = self.timing_recovery.recover(received, self._d_taps, first, ncols, True)
+            return rows, syms
         rows = dev.awgn_mf_bank(sig, self._d_taps, first, self.sps, ncols, self.sigma(ebn0_db), seed, stream_id, 0,
                                 np.exp(-1j * np.pi / 4))
         return rows, syms
@@ -284,7 +329,14 @@ class _SOQPSK(_Link):
         return dev.viterbi_soft_apriori(rows, prior, self.damping)
 
     def count_uncoded(self, hard, tx, syms) -> None:
-        dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
+        if self.timing_recovery is None:            # (recovered rows may sit two rows from the sent bits: nothing to compare at)
+            dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
+
+    def uncoded_result(self) -> tuple[int, int]:
+        if self.timing_recovery is not None:
+            raise RuntimeError("uncoded_result: a timing recovery leaves the rows two rows early or late in some bursts; "
+                               "the channel bits are not counted (the decoder's counts hold)")
+        return super().uncoded_result()
 
 
 class _CPM(_Link):
@@ -403,9 +455,10 @@ class CodedSOQPSKLink(_LDPC, _SOQPSK):
     is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0, carrier=None, recovery=None) -> None:
+                 lead_bits: int = 0, carrier=None, recovery=None, timing=None, timing_recovery=None) -> None:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
-        super().__init__(code, ncw, sps, detector, framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
+        super().__init__(code, ncw, sps, detector, timing=timing, timing_recovery=timing_recovery, framing=framing, lead_bits=lead_bits,
+                         carrier=carrier, recovery=recovery)
 
 
 class CodedCPMLink(_LDPC, _CPM):
@@ -536,13 +589,13 @@ class IterativeSOQPSKLink(_LDPCLoop, CodedSOQPSKLink):
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
                  lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD, carrier=None,
-                 recovery=None) -> None:
+                 recovery=None, timing=None, timing_recovery=None) -> None:
         if int(guard) < 0:
             raise ValueError(f"guard = {guard} must not be negative")
         self.live_only, self.guard = bool(live_only), int(guard)
         super().__init__(code, ncw, sps=sps, detector=detector, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
                          ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, carrier=carrier,
-                         recovery=recovery)
+                         recovery=recovery, timing=timing, timing_recovery=timing_recovery)
         self.live_counts = _hip.zeros((self.outer, 3), "int64") if self.live_only else None
         self.windows = _hip.zeros(4 + 2 * self.ncw, "int64") if self.live_only else None
         self._live_out, self._live_first = None, 0          # the block's ext / bits buffers; first passes run
