@@ -1082,6 +1082,44 @@ int wf_timing_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, in
  * delta not finite or not positive, a NULL pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
 int wf_timing_refine(wf_ctx *ctx, const double *d_stat3, int64_t nwin, int span, double delta, double *d_more, void *stream);
 
+/* ---- Symbol timing for the generic CPM chains (ARTM multi-h, PCM/FM) --------------------------------------------------------
+ * (waveforms_amd/sync/timing_cpm.py restates each in numpy: cpm_mf_rows_resample_host, llr_stat_host; the trajectory stages
+ * are wf_timing_track and wf_timing_refine above, untouched.)
+ * wf_cpm_mf_rows_resample_c128: the rows of wf_cpm_mf_rows_c128 at fractional, time-varying instants, in one pass over the
+ * samples.  Row n < ncalls is taken at start0 + n sps + t_n:
+ *   t_n = tau0 + τ_n, τ_n interpolated from d_tau[nwin] exactly as wf_mf_bank_resample_c128 interpolates it (d_tau NULL: τ = 0,
+ *   W and nwin are then not read);   b = floor(t_n);   μ = t_n - b   (exact);   c_i = the Lagrange weights above at μ
+ *   x_n[k] = fma(c_2, r[g+2], fma(c_1, r[g+1], fma(c_0, r[g], c_-1 * r[g-1])))   per component,  g = start0 + n sps + b + k,  k < ntm,
+ *            a sample outside [0, nsamp) counting as zero
+ *   rows[n][f] = Σ_k x_n[k] conj(T[n % nh][f][k]),  k ascending from zr = zi = +0:
+ *            zr = fma(x.re, t.re, fma(x.im, t.im, zr));   zi = fma(-x.re, t.im, fma(x.im, t.re, zi))
+ * The order of operations is part of the definition: a C restatement with explicit fma() agrees BITWISE.  For a finite whole
+ * t_n the weights are (-0, 1, 0, -0), x_n[k] = r[g], and the row EQUALS wf_cpm_mf_rows_c128's at start0 + t_n.  A t_n that is not
+ * finite, or at or beyond 2^62 in magnitude, writes a zero row, and so does a row all of whose samples lie outside the burst.
+ * Any finite trajectory is served: rows may fall before sample 0 or behind the end, and neighbouring rows may be any distance
+ * apart (a tile of rows whose samples span more than the staged window reads them from global memory, with the same
+ * arithmetic).  d_templates_ri: nh x nfilt x ntm complex128, the templates (not reversed, not conjugated); d_rows_ri:
+ * ncalls x nfilt complex128.  nh outside {1, 2}, nfilt outside {2, 4, 8, 16, 64}, ntm outside 1 .. 257, sps outside 1 .. 256 (or
+ * a combination whose tile does not fit LDS), nsamp or ncalls outside 1 .. 2^40, |start0| > 2^40, tau0 not finite, (with d_tau)
+ * W outside 64 .. 8192 in steps of 64 or nwin < 1, a NULL ctx / samples / templates / rows, data not 16-byte or d_tau not
+ * 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_cpm_mf_rows_resample_c128(wf_ctx *ctx, const double *d_r_ri, int64_t nsamp, const double *d_templates_ri, int nh, int nfilt,
+                                 int ntm, int64_t start0, int sps, int64_t ncalls, int W, const double *d_tau, int64_t nwin,
+                                 double tau0, double *d_rows_ri, void *stream);
+/* What wf_cpm_mf_rows_resample_c128 launches for these shapes: h_geom[0] rows per tile (one workgroup serves a tile at a time),
+ * [1] the most workgroups a launch has (bursts with more tiles walk them in a grid-stride loop), [2] bytes of LDS per workgroup.
+ * Host only.  The shapes' refusals are wf_cpm_mf_rows_resample_c128's. */
+int wf_cpm_mf_rows_resample_geometry(int nh, int nfilt, int ntm, int sps, int64_t *h_geom);
+/* The timing statistic of the CPM chains: the summed LLR magnitude per window of W calls of bits_per_call values each (a wrong
+ * sampling instant makes ambiguous decisions).  nwin = ceil(ncalls / W); window w holds the values
+ * λ[bits_per_call W w .. min(bits_per_call W (w + 1), bits_per_call ncalls) - 1]; in exactly wf_carrier_stat's order of additions:
+ *   p_l = sum_i |λ[base + 64 i + l]|   (i increasing, started from +0; indices beyond the window contribute nothing), l < 64
+ *   for d = 32, 16, .., 1:  p_l = p_l + p_{l+d}  for l < d;      d_stat[2w] = -p_0;   d_stat[2w + 1] = +0
+ * so wf_timing_track and wf_timing_refine take the table as it is (they read X only).  d_llr: bits_per_call ncalls float64 as
+ * wf_cpm_soft writes them.  ncalls outside 1 .. 2^40, bits_per_call outside 1 .. 8, W outside 64 .. 8192 in steps of 64, a NULL
+ * pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
+int wf_llr_stat(wf_ctx *ctx, const double *d_llr, int64_t ncalls, int bits_per_call, int W, double *d_stat, void *stream);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

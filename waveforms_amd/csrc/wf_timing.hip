@@ -22,10 +22,9 @@
 //
 // The instants' arithmetic is written one operation per statement where the host statement must see the same roundings
 // (-ffp-contract=on fuses within an expression only).
-#include "wf_common.h"
+#include "wf_timing.h"
 
 #include <climits>
-#include <cmath>
 
 #define TIMING_THREADS 256
 #define RS_THREADS 256
@@ -34,17 +33,6 @@
 #define RS_EXTRA 64           // samples of room for the trajectory to move inside one tile before the tile leaves LDS
 #define RS_MAX_TAPS 255
 #define TTRACK_THREADS 1024   // timing_track_kernel: ONE workgroup (its loops are latency-bound)
-static constexpr double kTimingHuge = 4611686018427387904.0;   // 2^62: an instant at or beyond it has no sample near it
-
-// cubic Lagrange weights of the nodes -1, 0, 1, 2 at the fraction mu (products and one division each: nothing to contract)
-__device__ __forceinline__ void timing_lagrange(double mu, double c[4])
-{
-    const double p1 = mu + 1.0, m1 = mu - 1.0, m2 = mu - 2.0;
-    c[0] = -(mu * m1 * m2) / 6.0;
-    c[1] = (p1 * m1 * m2) / 2.0;
-    c[2] = -(p1 * mu * m2) / 2.0;
-    c[3] = (p1 * mu * m1) / 6.0;
-}
 
 __global__ __launch_bounds__(TIMING_THREADS) void timing_offset_kernel(const double2 *__restrict__ in, int64_t n, double tau0, double eps, int64_t first_index,
                                                                        double2 *__restrict__ out)
@@ -146,28 +134,13 @@ __global__ __launch_bounds__(RS_THREADS) void mf_resample_kernel(const double2 *
     const int step = P.step, pad = P.pad, ntaps = P.ntaps;
     double2 *s_taps = s_rs + P.taps_slot;
     for (int k = t; k < 3 * ntaps; k += RS_THREADS) s_taps[k] = taps[k];      // (first read behind the loop's barriers)
-    const double c0 = 0.5 * (double)(P.W - 1);
     for (int64_t blk = blockIdx.x; blk < P.nblk; blk += gridDim.x) {
         const int64_t k = blk * P.ob + t;
         const bool row = t < P.ob && k < P.ncols;
         // the row's instant: tau0 + τ_k, τ interpolated between the window centres as rows_derotate_kernel interpolates its phase
         double tk = P.tau0;
         if (row && P.tau) {
-            double phi;
-            const double tt = ((double)k - c0) / (double)P.W;
-            if (tt <= 0.0) {
-                phi = P.tau[0];
-            } else if (tt >= (double)(P.nwin - 1)) {
-                phi = P.tau[P.nwin - 1];
-            } else {
-                const double fl = floor(tt);
-                const int64_t w = (int64_t)fl;
-                const double f = tt - fl;
-                const double p0 = P.tau[w];
-                const double d = P.tau[w + 1] - p0;
-                const double fd = f * d;
-                phi = p0 + fd;
-            }
+            const double phi = timing_tau_at(P.tau, P.nwin, P.W, k);
             tk = P.tau0 + phi;
         }
         bool live = row && fabs(tk) < kTimingHuge;             // (false for a NaN)
@@ -342,9 +315,6 @@ __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const doub
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-static bool timing_mis(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-static bool timing_window_ok(int W) { return W >= 64 && W <= 8192 && W % 64 == 0; }
-static constexpr int64_t kTimingMaxN = (int64_t)1 << 40;
 
 extern "C" int wf_timing_offset_c128(wf_ctx *ctx, const double *d_in_ri, int64_t n, double tau0, double eps, int64_t first_index, double *d_out_ri,
                                      void *stream)

@@ -449,6 +449,60 @@ def timing_refine(stat3, delta: float, span: int = 1, ctx=None):
     return more[:nwin]
 
 
+def cpm_mf_rows_resample(received, templates, start0: int, sps: int, ncalls: int, window: int = 64, tau=None, tau0: float = 0.0, out=None,
+                         ctx=None):
+    """``cpm_mf_rows`` at the instants start0 + n sps + tau0 + τ_n (``wf_cpm_mf_rows_resample_c128``; include/wfhip.h states the
+    definition) -> device float64[ncalls, nfilt, 2].  ``received``: contiguous device float64[nsamp, 2]; ``templates``:
+    float64[nh, nfilt, ntm, 2]; ``tau``: device float64[nwin] in samples, interpolated between the centres of the windows of
+    ``window`` rows as ``mf_bank_resample`` interpolates it (None: τ = 0).  Rows may fall before sample 0 or behind the end."""
+    torch = _hip.torch()
+    if received.dtype != torch.float64 or not received.is_contiguous() or received.numel() % 2 or received.numel() == 0:
+        raise ValueError("received must be contiguous float64[nsamp, 2]")
+    if templates.dtype != torch.float64 or not templates.is_contiguous() or templates.dim() != 4 or templates.shape[3] != 2:
+        raise ValueError("templates must be contiguous float64[nh, nfilt, ntm, 2]")
+    nsamp, ncalls = received.numel() // 2, int(ncalls)
+    nh, nfilt, ntm = (int(v) for v in templates.shape[:3])
+    nwin = 0
+    if tau is not None:
+        if tau.dtype != torch.float64 or not tau.is_contiguous() or tau.numel() < 1:
+            raise ValueError("tau must be contiguous float64[nwin]")
+        nwin = int(tau.numel())
+    if out is None:
+        out = _hip.empty((max(ncalls, 1), nfilt, 2), "float64")[:max(ncalls, 0)]
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nfilt * ncalls:
+        raise ValueError(f"out must be contiguous float64[{ncalls}, {nfilt}, 2]")
+    _hip.check(_hip.lib().wf_cpm_mf_rows_resample_c128(_ctx(ctx), _hip.ptr(received), nsamp, _hip.ptr(templates), nh, nfilt, ntm, int(start0),
+                                                       int(sps), ncalls, int(window), _hip.ptr(tau), nwin, float(tau0), _hip.ptr(out),
+                                                       _hip.stream()))
+    return out
+
+
+def cpm_mf_rows_resample_geometry(nh: int, nfilt: int, ntm: int, sps: int) -> tuple[int, int, int]:
+    """(rows per tile, the most workgroups of a launch, bytes of LDS per workgroup) of ``cpm_mf_rows_resample`` for these
+    shapes (``wf_cpm_mf_rows_resample_geometry``) - host only."""
+    geom = (ctypes.c_int64 * 3)()
+    _hip.check(_hip.lib().wf_cpm_mf_rows_resample_geometry(int(nh), int(nfilt), int(ntm), int(sps), geom))
+    return int(geom[0]), int(geom[1]), int(geom[2])
+
+
+def llr_stat(llr, bits_per_call: int, window: int, out=None, ctx=None):
+    """The timing statistic of the CPM chains per window of ``window`` calls (``wf_llr_stat``; include/wfhip.h states the
+    definition) -> device float64[nwin, 2] = (-Σ |λ|, +0).  ``llr``: contiguous device float64[ncalls bits_per_call] as
+    ``cpm_soft`` writes it.  ``out``: where to write (a row of the H x nwin x 2 table ``timing_track`` reads)."""
+    torch = _hip.torch()
+    bits_per_call = int(bits_per_call)
+    if bits_per_call < 1 or llr.dtype != torch.float64 or not llr.is_contiguous() or llr.numel() == 0 or llr.numel() % bits_per_call:
+        raise ValueError("llr must be contiguous float64, bits_per_call values for each of at least one call")
+    ncalls = llr.numel() // bits_per_call
+    nwin = -(-ncalls // int(window))
+    if out is None:
+        out = _hip.empty((nwin, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
+        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    _hip.check(_hip.lib().wf_llr_stat(_ctx(ctx), _hip.ptr(llr), ncalls, bits_per_call, int(window), _hip.ptr(out), _hip.stream()))
+    return out
+
+
 def idd_windows(state, nrows: int, n_tx: int, period: int | None = None, row_offset: int = 1, lock=None, marker_bits: int = 0,
                 guard: int = 128, out=None, ctx=None):
     """The live windows of a burst from the decoder's freeze states (``wf_idd_windows``; include/wfhip.h states the definition,

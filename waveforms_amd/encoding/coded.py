@@ -35,6 +35,13 @@ signal (``timing_offset``: the signal read at n + tau0 + eps n) in front of the 
 same noise coordinates as the fused front end's) and the recovery makes the detector's rows from them.  It needs a ``framing``
 (the instant comes back modulo two symbols: the rows may be two early or late) and excludes ``carrier`` and ``recovery``.  Both
 default to None: the same calls as before.
+
+The two CPM classes take ``clock=(tau0, eps)``, the same impairment behind the carrier offset and in front of the channel, and
+``clock_recovery``, a :class:`waveforms_amd.sync.timing_cpm.CPMTimingRecovery` that makes the rows from the noisy samples in
+place of ``cpm_mf_rows``.  (The names are not ``timing`` / ``timing_recovery``: those stay a TypeError on the CPM classes, and a
+``TimingRecovery`` passed as ``clock_recovery`` is refused.)  ``clock_recovery`` needs a ``framing`` (the rows come back shifted
+by a whole number of periods of nh symbols, which the frame search absorbs), excludes ``carrier`` and ``recovery`` and must be
+for the link's design and sps.  Both default to None: the same calls as before.
 """
 from __future__ import annotations
 
@@ -138,6 +145,37 @@ class _Framed:
         if self.timing_recovery is None or self._timing_tau is None:
             raise RuntimeError("timing_result needs a timing_recovery and a block that ran")
         return _hip.to_host(self._timing_tau), _hip.to_host(self._timing_choice)
+
+    def _clock_init(self, clock, clock_recovery, spec, sps: int, framing, carrier, recovery) -> None:
+        """``clock=(tau0, eps)`` and ``clock_recovery`` of the CPM links: ``_timing_init``'s pair for the generic CPM trellis, with
+        a ``waveforms_amd.sync.timing_cpm.CPMTimingRecovery``.  Checked before anything touches the device."""
+        if clock is not None:
+            tau0, eps = (float(v) for v in clock)
+            if not (math.isfinite(tau0) and math.isfinite(eps)):
+                raise ValueError("clock = (tau0, eps) must be finite")
+            clock = (tau0, eps)
+        if clock_recovery is not None:
+            from ..sync.timing_cpm import CPMTimingRecovery
+
+            if not isinstance(clock_recovery, CPMTimingRecovery):
+                raise ValueError("clock_recovery is a waveforms_amd.sync.timing_cpm.CPMTimingRecovery")
+            if recovery is not None or carrier is not None:
+                raise ValueError("clock_recovery excludes carrier and recovery: joint timing and carrier acquisition is not implemented")
+            if clock_recovery.spec != spec:
+                raise ValueError("the clock recovery is for another design than the link's full-phase trellis")
+            if clock_recovery.sps != sps:
+                raise ValueError(f"the clock recovery is for sps = {clock_recovery.sps}, the link has {sps}")
+            if framing is None:
+                raise ValueError("clock_recovery needs a framing: the instant is recovered modulo nh symbols and the frame search absorbs the shift")
+        self.clock, self.clock_recovery = clock, clock_recovery
+        self._clock_tau = self._clock_choice = self._clock_grid = None
+
+    def clock_result(self):
+        """(tau float64[nwin] in samples, modulo nh symbols; choice uint8[nwin]; grid 0 / 1) of the last block's clock recovery -
+        synchronises."""
+        if self.clock_recovery is None or self._clock_tau is None:
+            raise RuntimeError("clock_result needs a clock_recovery and a block that ran")
+        return _hip.to_host(self._clock_tau), _hip.to_host(self._clock_choice), int(self._clock_grid.cpu())
 
     def _rate_db(self) -> float:
         """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""
@@ -346,7 +384,7 @@ class _CPM(_Link):
     _lam0 = 0
     bits_per_symbol = property(lambda self: self.spec.bits_per_symbol)
 
-    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, **burst) -> None:
+    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, *, clock=None, clock_recovery=None, **burst) -> None:
         from ..viterbi import cpm
 
         if waveform not in CPM_WAVEFORMS:
@@ -354,6 +392,7 @@ class _CPM(_Link):
         if waveform == "multih" and code.n_tx % 2:
             raise ValueError(f"ARTM sends two bits per symbol: a code with an odd n_tx = {code.n_tx} is refused")
         self.waveform, self.spec = waveform, cpm.ARTM_64 if waveform == "multih" else cpm.PCMFM_20
+        self._clock_init(clock, clock_recovery, self.spec, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -391,7 +430,13 @@ class _CPM(_Link):
         sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
         if self.carrier is not None:
             dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
+        if self.clock is not None:
+            sig = dev.timing_offset(sig, self.clock[0], self.clock[1], 0)
         received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
+        if self.clock_recovery is not None:
+            rows, self._clock_tau, self._clock_choice, self._clock_grid = self.clock_recovery.recover(received, self._d_templates, self.start0,
+                                                                                                     self.ncalls)
+            return rows, syms
         rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
         return rows, syms
 
@@ -413,8 +458,16 @@ class _CPM(_Link):
         return dev.cpm_soft_apriori(rows, self.spec, prior, self.damping, 0, 0 if prior is None else self.prior_warmup, d_rot=self._d_rot)
 
     def count_uncoded(self, hard, tx, syms=None) -> None:
+        if self.clock_recovery is not None:         # (recovered rows may sit a period from the sent bits: nothing to compare at)
+            return
         flat = tx.reshape(-1) if self.framing is None else self.sent
         dev.count_errors(hard, flat, hard, flat, self.nch, self.uncoded)     # (bits in both pairs: [1] is what is read)
+
+    def uncoded_result(self) -> tuple[int, int]:
+        if self.clock_recovery is not None:
+            raise RuntimeError("uncoded_result: a clock recovery leaves the rows a whole number of periods early or late in some "
+                               "bursts; the channel bits are not counted (the decoder's counts hold)")
+        return super().uncoded_result()
 
 
 class _LDPC:
@@ -478,9 +531,10 @@ class CodedCPMLink(_LDPC, _CPM):
     first codeword at most lgM channel errors (one decoder iteration when there is no noise)."""
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0, carrier=None, recovery=None) -> None:
+                 lead_bits: int = 0, clock=None, clock_recovery=None, carrier=None, recovery=None) -> None:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
-        super().__init__(code, ncw, waveform, sps, framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
+        super().__init__(code, ncw, waveform, sps, framing=framing, lead_bits=lead_bits, clock=clock, clock_recovery=clock_recovery,
+                         carrier=carrier, recovery=recovery)
 
 
 class _LDPCLoop:
@@ -673,14 +727,14 @@ class IterativeCPMLink(_LDPCLoop, CodedCPMLink):
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False,
-                 prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None, carrier=None,
-                 recovery=None) -> None:
+                 prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None, clock=None,
+                 clock_recovery=None, carrier=None, recovery=None) -> None:
         if prior_warmup < 0:
             raise ValueError("prior_warmup must not be negative")
         self.prior_warmup = int(prior_warmup)
         super().__init__(code, ncw, waveform=waveform, sps=sps, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
-                         ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, carrier=carrier,
-                         recovery=recovery)
+                         ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, clock=clock,
+                         clock_recovery=clock_recovery, carrier=carrier, recovery=recovery)
 
     def begin(self, ncalls: int | None = None) -> None:
         """Fresh loop state of one block: prior 0 on every bit of every call, every codeword open, no iterations."""
