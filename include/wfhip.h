@@ -1082,6 +1082,31 @@ int wf_timing_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, in
  * delta not finite or not positive, a NULL pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
 int wf_timing_refine(wf_ctx *ctx, const double *d_stat3, int64_t nwin, int span, double delta, double *d_more, void *stream);
 
+/* ---- Joint carrier and timing acquisition for the SOQPSK-TG receiver: all carrier hypotheses of a pass in one set of launches --
+ * (waveforms_amd/sync/joint.py composes the search from the stages above; these two entry points stack its hypotheses.)
+ * wf_rows_derotate_hyp: H rotated copies of ncalls 48-byte rows, d_out[h][k], h < H, k < stride (H stride rows in all):
+ *   k < ncalls:   d_out[h][k] = d_rows[k] exp(-j ((double)h * π) / H), all three values of the row, BITWISE what
+ *                 wf_rows_derotate writes with d_phase NULL and phase0 = ((double)h * π) / H (the same operations);
+ *   otherwise:    zero rows (+0.0), so that wf_carrier_stat over the whole buffer with a W that divides stride is H x
+ *                 (stride / W) x 2 and no window takes rows of two copies.
+ * Every input row is read once.  OUT OF PLACE only.  H outside 1 .. 256, ncalls < 1, stride < ncalls or not a multiple of
+ * 64, H stride beyond 2^40, a NULL pointer, rows not 16-byte aligned or an output that overlaps the input: WF_ERR_VALUE before
+ * the context is touched. */
+int wf_rows_derotate_hyp(wf_ctx *ctx, const double *d_rows, int64_t ncalls, int H, int64_t stride, double *d_out, void *stream);
+/* wf_viterbi4_soft (d_branch NULL) or wf_viterbi4_soft_branch (d_branch given: 48-byte rows only) over nseg INDEPENDENT trellis
+ * segments of one buffer, in ONE set of launches (bounds, two fix-ups, last).  Segment s < nseg is rows s stride .. s stride +
+ * seglen - 1, detected from a free start and to a free end as a burst of its own: its λ, bits and branches are BITWISE what
+ * the burst entry point gives for those rows alone, whatever warm-up and chunk length (no chunk crosses a segment, no warm-up
+ * leaves one, a segment's first chunk starts exactly as chunk 0 of a burst does, and every other chunk start is proven or
+ * repaired).  stride is even, so row k of the buffer is trellis column k % 2 in its segment too.  Outputs are addressed as the
+ * rows are and hold nseg stride values each: those of the pad rows s stride + seglen .. (s + 1) stride - 1, which are never
+ * read, are written as 0.  d_rows holds (nseg - 1) stride + seglen rows at least.  The chunk length is wf_viterbi4_soft's for a
+ * burst of nseg seglen rows (WF_OPT_SOFT_CHUNK_CALLS); options, counters and scratch as wf_viterbi4_soft.  nseg < 1 or beyond
+ * 2^20, seglen < 1, stride odd or < seglen, nseg stride beyond 2^40, a packed d_rows with a d_branch, or any argument
+ * wf_viterbi4_soft refuses: WF_ERR_VALUE before the context is touched. */
+int wf_viterbi4_soft_branch_segments(wf_ctx *ctx, const double *d_rows, int64_t nseg, int64_t seglen, int64_t stride, int row_bytes,
+                                     int differential, int warmup, double *d_llr, uint8_t *d_bits, uint8_t *d_branch, void *stream);
+
 /* ---- Symbol timing for the generic CPM chains (ARTM multi-h, PCM/FM) --------------------------------------------------------
  * (waveforms_amd/sync/timing_cpm.py restates each in numpy: cpm_mf_rows_resample_host, llr_stat_host; the trajectory stages
  * are wf_timing_track and wf_timing_refine above, untouched.)

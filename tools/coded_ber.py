@@ -8,6 +8,8 @@ decoder's speed; prints ONE JSON line.
     python tools/coded_ber.py --code conv-k3|conv-k7 --rs 16|8 [--rs-depth I] [--rs-n N] [--rs-erasures F [--rs-erase-below X]] ...
     python tools/coded_ber.py --carrier-phase DEG --carrier-freq NU --recover [--carrier-window W --carrier-hyp H] [--ebn0 ...]
     python tools/coded_ber.py [--waveform multih|pcmfm] --timing-offset TAU --timing-drift EPS --recover-timing [--timing-window W --timing-hyp H --timing-refine R]
+    python tools/coded_ber.py --carrier-phase DEG --carrier-freq NU --timing-offset TAU --timing-drift EPS --acquire
+                              [--acq-timing-hyp Ht --acq-carrier-hyp Hc [Hc2 ...] --acq-stack N --acq-time-rows N1 N2 --acq-out PATH]
 
 ``--waveform soqpsk`` (default) is CodedSOQPSKLink / IterativeSOQPSKLink with ``--detector``; ``multih`` and ``pcmfm`` are
 CodedCPMLink / IterativeCPMLink on the full-phase trellis (``--detector`` is not used).
@@ -73,6 +75,15 @@ and ``recovered`` (the offset and ``TimingRecovery`` with ``--timing-window``, `
 soft detection, and the same ``loss_db_at_fer_1e-2``.  With ``--waveform multih|pcmfm`` the three links are ``CodedCPMLink``s with
 ``clock=(TAU, EPS)`` and a ``CPMTimingRecovery`` whose window, hypotheses and delta default per waveform; the front end beside
 the recovery is then ``awgn`` + ``cpm_mf_rows``, the detection ``cpm_soft``, and every point also has the ``grid`` decision.
+
+With ``--acquire`` both impairments are applied at once (``--carrier-*`` and ``--timing-*``) and the third link runs a
+``JointAcquisition`` (``--acq-timing-hyp`` instants over one symbol, ``--acq-carrier-hyp`` rotations; window, span, refine and
+delta from the ``--timing-*`` flags): ``genie``, ``impaired`` and ``acquired`` on the same blocks, one more acquired curve per
+further value of ``--acq-carrier-hyp``, ``loss_db_at_fer_1e-2`` per acquired curve, and under ``one_acquisition`` the time of
+one acquisition of a burst of each ``--acq-time-rows`` length - device events around the whole call after a warm-up, ``stack=1``
+(the existing entry points per hypothesis) against the default stacking, with the launch counts, the stage times and the
+time in units of one plain soft detection of as many rows.  The result is also written to ``--acq-out``
+(profiles/joint_acquisition.json).
 """
 import argparse
 import json
@@ -339,6 +350,123 @@ def main_timing(args) -> None:
     print(json.dumps(out))
 
 
+def _time_acquisition(lk, acq_kw, stacks, nrows, carrier, timing, ebn0, steps):
+    """One acquisition of a burst of about ``nrows`` rows (PN bits, the links' own impairment and channel) per entry of
+    ``stacks``: device events around the whole call, ``steps`` calls after one warm-up, beside one plain soft detection of as
+    many rows -> {"rows", "soft_detector_ms", name: {"stack", "ms", "launches", "in_soft_detections", "stages_ms"}}."""
+    import torch
+
+    from waveforms_amd import device as dev
+    from waveforms_amd.encoding.coded import TIMING_OFFSET
+    from waveforms_amd.sync.joint import JointAcquisition
+
+    sps = lk.sps
+    bits = dev.lfsr_bits(23, lk._mask, (1 << 23) - 1, int(nrows))[0]
+    sig = dev.cpm_modulate(dev.fsm_encode(*lk._tables, bits)[0], lk._d_h, lk._d_pulse, sps)
+    dev.carrier_offset(sig, carrier[0], carrier[1], 0, out=sig)
+    sig = dev.timing_offset(sig, timing[0], timing[1], 0)
+    first, ncols = dev.decimation(int(sig.shape[0]), sps, 2, TIMING_OFFSET[lk.detector])
+    received = dev.awgn(sig, int(sig.shape[0]), lk.sigma(ebn0), 1, 0, 0, np.exp(-1j * np.pi / 4))
+    del sig
+    plain = dev.mf_bank(received, lk._d_taps, first, sps, ncols)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    soft_ms = 0.0
+    for s in range(steps + 1):
+        ev[0].record()
+        dev.viterbi_soft(plain, True)
+        ev[1].record()
+        torch.cuda.synchronize()
+        soft_ms += ev[0].elapsed_time(ev[1]) if s else 0.0
+    del plain
+    n = max(steps, 1)
+    out = {"rows": int(ncols), "soft_detector_ms": round(soft_ms / n, 4)}
+    for name, stack in stacks.items():
+        acq = JointAcquisition(sps, stack=stack, **acq_kw)
+        ms, stages = 0.0, {}
+        for s in range(steps + 1):
+            acq.times = False
+            ev[0].record()
+            res = acq.recover(received, lk._d_taps, first, ncols, True)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms += ev[0].elapsed_time(ev[1]) if s else 0.0
+            del res
+        acq.times = True                                                  # (the stages from a call of their own: the events cost time)
+        acq.recover(received, lk._d_taps, first, ncols, True)
+        stages = {k: round(v, 4) for k, v in acq.stage_times().items()}
+        out[name] = {"stack": acq.stack_for(ncols), "ms": round(ms / n, 4), "launches": acq.launches,
+                     "in_soft_detections": round(ms / n / (soft_ms / n), 2), "stages_ms": stages}
+    return out
+
+
+def main_acquire(args) -> None:
+    """The ``--acquire`` form: genie, impaired and acquired FRAMED CodedSOQPSKLink on the same blocks under a carrier offset AND a
+    timing offset (``JointAcquisition``), one more acquired curve per further value of ``--acq-carrier-hyp``, and the time of one
+    acquisition, unstacked and stacked, on bursts of ``--acq-time-rows`` rows."""
+    import math
+
+    import torch
+
+    from waveforms_amd.encoding import ldpc
+    from waveforms_amd.encoding.coded import CodedSOQPSKLink
+    from waveforms_amd.encoding.framing import Framing
+    from waveforms_amd.sync.joint import MAX_DRIFT_SAMPLES, MAX_DRIFT_TURNS, STACK_BYTES, JointAcquisition
+
+    torch.cuda.set_device(0)
+    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
+    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
+    carrier, timing = (math.radians(args.carrier_phase), args.carrier_freq), (args.timing_offset, args.timing_drift)
+    fr = Framing(code)
+    sps = 8
+    common = dict(window=args.timing_window or 256, span=args.timing_span, timing_hypotheses=args.acq_timing_hyp, refine=args.timing_refine,
+                  delta=args.timing_delta or 2.0)
+    kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
+    links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, **kw)}
+    acqs = {}
+    for i, hc in enumerate(args.acq_carrier_hyp):
+        name = "acquired" if i == 0 else f"acquired_hc{hc}"
+        acqs[name] = JointAcquisition(sps, carrier_hypotheses=hc, stack=args.acq_stack or None, **common)
+        links[name] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=acqs[name], **kw)
+    W = common["window"]
+    out = {"tool": "coded_ber", "form": "acquire", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
+           "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
+           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
+                       "drift_turns_per_window": abs(args.carrier_freq) * sps * W, "documented_limit_turns_per_window": MAX_DRIFT_TURNS},
+           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * sps * W,
+                      "documented_limit_samples_per_window": MAX_DRIFT_SAMPLES},
+           "acquisition": {**common, "carrier_hypotheses": args.acq_carrier_hyp, "stack": args.acq_stack or None, "stack_bytes": STACK_BYTES}, "points": []}
+    for e in args.ebn0:
+        point = {"ebn0_info_db": e}
+        b = 0
+        for name, lk in links.items():
+            lk.reset_counts()
+            b = 0
+            while b * per < args.codewords:
+                lk.run_block(e, seed=1, stream_id=b)
+                b += 1
+            be, fe, nc, m, mean_it = lk.result()
+            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
+                           "mean_iters": round(mean_it, 3), "wrong_locks": lk.sync_result()[1], "last_lock": lk.sync_result()[2][0]}
+        point["codewords"] = b * per
+        out["points"].append(point)
+    g = _ebn0_at_fer(out["points"], "genie")
+    out["ebn0_at_fer_1e-2"] = {"genie": g}
+    out["loss_db_at_fer_1e-2"] = {}
+    for name in acqs:
+        r = _ebn0_at_fer(out["points"], name)
+        out["ebn0_at_fer_1e-2"][name] = r
+        out["loss_db_at_fer_1e-2"][name] = None if g is None or r is None else round(r - g, 3)
+    # one acquisition, unstacked (the existing entry points per hypothesis) and stacked, in units of one plain soft detection
+    acq_kw = dict(common, carrier_hypotheses=args.acq_carrier_hyp[0])
+    stacks = {"stack_1": 1, "stack_default": args.acq_stack or None}
+    out["one_acquisition"] = [_time_acquisition(links["acquired"], acq_kw, stacks, n, carrier, timing, args.ebn0[-1], args.steps) for n in args.acq_time_rows]
+    text = json.dumps(out)
+    if args.acq_out:
+        Path(args.acq_out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.acq_out).write_text(json.dumps(out, indent=1) + "\n")
+    print(text)
+
+
 def main_conv(args) -> None:
     """The ``--code conv-*`` form: ConvSOQPSKLink."""
     import torch
@@ -520,7 +648,17 @@ def main() -> None:
     ap.add_argument("--timing-span", type=int, default=5, help="--recover-timing: windows of the centred mean")
     ap.add_argument("--timing-refine", type=int, default=1, help="--recover-timing: refinement rounds")
     ap.add_argument("--timing-delta", type=float, default=None, help="--recover-timing: spacing of a refinement's three points, samples (default: 2.0; the class's for ARTM and PCM/FM)")
+    ap.add_argument("--acquire", action="store_true", help="genie, impaired and acquired framed links on the same blocks under --carrier-* AND --timing-* (JointAcquisition)")
+    ap.add_argument("--acq-timing-hyp", type=int, default=4, help="--acquire: timing hypotheses over one symbol")
+    ap.add_argument("--acq-carrier-hyp", type=int, nargs="+", default=[8], help="--acquire: carrier hypotheses over [0, pi); further values add a curve each")
+    ap.add_argument("--acq-stack", type=int, default=0, help="--acquire: carrier hypotheses per stacked launch set (0: all that fit the byte budget; 1: unstacked)")
+    ap.add_argument("--acq-time-rows", type=int, nargs="*", default=[211_252, 10_000_000], help="--acquire: burst lengths one acquisition is timed at")
+    ap.add_argument("--acq-out", default=str(ROOT / "profiles" / "joint_acquisition.json"), help="--acquire: where the result is also written ('' : nowhere)")
     args = ap.parse_args()
+    if args.acquire:
+        if args.code.startswith("conv") or args.outer or args.live_only or args.recover or args.recover_timing or args.waveform != "soqpsk":
+            ap.error("--acquire is the framed CodedSOQPSKLink's: an LDPC code, no --outer / --live-only / --recover / --recover-timing / --waveform")
+        return main_acquire(args)
     if args.recover_timing or args.timing_offset or args.timing_drift:
         if not args.recover_timing:
             ap.error("--timing-offset / --timing-drift go with --recover-timing")

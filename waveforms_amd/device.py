@@ -381,6 +381,51 @@ def rows_derotate(rows, window: int = 64, phase=None, phase0: float = 0.0, out=N
     return out
 
 
+def rows_derotate_hyp(rows, hypotheses: int, stride: int | None = None, out=None, ctx=None):
+    """The ``hypotheses`` rotated copies of 48-byte rows a coarse carrier search detects, in one pass over the rows
+    (``wf_rows_derotate_hyp``; include/wfhip.h states the definition) -> device float64[H stride, 3, 2]: copy h at rows h stride ..,
+    bitwise ``rows_derotate(rows, phase0=(h * pi) / H)``, then zero rows up to ``stride`` (a multiple of 64, at least the number
+    of rows; None: that number rounded up to 64).  Out of place only."""
+    torch = _hip.torch()
+    ncalls, H = _rows48(rows), int(hypotheses)
+    stride = -(-ncalls // 64) * 64 if stride is None else int(stride)
+    if not 1 <= H <= 256:
+        raise ValueError(f"hypotheses = {hypotheses} outside 1 .. 256")
+    if stride < ncalls or stride % 64:
+        raise ValueError(f"stride = {stride} must be a multiple of 64 and at least {ncalls}")
+    if out is None:
+        out = _hip.empty((H * stride, 3, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 6 * H * stride:
+        raise ValueError(f"out must be contiguous float64[{H * stride}, 3, 2]")
+    _hip.check(_hip.lib().wf_rows_derotate_hyp(_ctx(ctx), _hip.ptr(rows), ncalls, H, stride, _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def viterbi_soft_branch_segments(rows, nseg: int, seglen: int, stride: int, differential: bool = True, warmup: int = 0, row_bytes: int = 48,
+                                 branch: bool = True, ctx=None):
+    """``viterbi_soft_branch`` over ``nseg`` independent trellis segments of one buffer in one set of launches
+    (``wf_viterbi4_soft_branch_segments``; include/wfhip.h states the definition) -> (llr f64, bits u8, branch u8), each of
+    nseg stride values addressed as the rows are.  Segment s is rows s stride .. s stride + seglen - 1 (``stride`` even, at least
+    ``seglen``) and comes out bitwise as ``viterbi_soft_branch`` of those rows alone; the outputs of the pad rows are 0.  ``rows``
+    holds (nseg - 1) stride + seglen rows at least.  ``row_bytes=32`` (packed rows) or ``branch=False``: ``viterbi_soft`` per
+    segment, and None in place of the branches."""
+    nseg, seglen, stride, row_bytes = int(nseg), int(seglen), int(stride), int(row_bytes)
+    have = _rows(rows, row_bytes, allow_empty=False)
+    if nseg < 1 or seglen < 1 or stride < seglen or stride % 2:
+        raise ValueError("nseg and seglen must be at least 1, stride even and at least seglen")
+    if have < (nseg - 1) * stride + seglen:
+        raise ValueError(f"{have} rows are fewer than the {(nseg - 1) * stride + seglen} that {nseg} segments at stride {stride} take")
+    if branch and row_bytes != 48:
+        raise ValueError("the branches need 48-byte rows")
+    n = nseg * stride
+    llr = _hip.empty(n, "float64")
+    bits = _hip.empty(n + 16, "uint8")
+    br = _hip.empty(n + 16, "uint8") if branch else None
+    _hip.check(_hip.lib().wf_viterbi4_soft_branch_segments(_ctx(ctx), _hip.ptr(rows), nseg, seglen, stride, row_bytes, int(bool(differential)),
+                                                           int(warmup), _hip.ptr(llr), _hip.ptr(bits), _hip.ptr(br), _hip.stream()))
+    return llr, bits[:n], (br[:n] if branch else None)
+
+
 def timing_offset(signal, tau0: float, eps: float, first_index: int = 0, out=None):
     """The timing impairment at sample rate (``wf_timing_offset_c128``; include/wfhip.h states the definition): the signal read
     at n + tau0 + eps (first_index + n) by cubic Lagrange interpolation, samples outside the burst counting as zero.

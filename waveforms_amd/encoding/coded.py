@@ -36,6 +36,12 @@ same noise coordinates as the fused front end's) and the recovery makes the dete
 (the instant comes back modulo two symbols: the rows may be two early or late) and excludes ``carrier`` and ``recovery``.  Both
 default to None: the same calls as before.
 
+``CodedSOQPSKLink`` and ``IterativeSOQPSKLink`` also take ``acquisition``, a :class:`waveforms_amd.sync.joint.JointAcquisition`
+that makes the rows from the noisy samples under BOTH impairments (``carrier=`` and ``timing=`` may be given beside it; the
+order is ``carrier_offset``, then ``timing_offset``, then the channel).  It needs a ``framing`` (the pair comes back modulo
+(sps, π/2) and (0, π): the rows may be a few rows early or late, and inverted) and excludes ``recovery`` and
+``timing_recovery``.  Default None: the same calls as before.
+
 The two CPM classes take ``clock=(tau0, eps)``, the same impairment behind the carrier offset and in front of the channel, and
 ``clock_recovery``, a :class:`waveforms_amd.sync.timing_cpm.CPMTimingRecovery` that makes the rows from the noisy samples in
 place of ``cpm_mf_rows``.  (The names are not ``timing`` / ``timing_recovery``: those stay a TypeError on the CPM classes, and a
@@ -145,6 +151,32 @@ class _Framed:
         if self.timing_recovery is None or self._timing_tau is None:
             raise RuntimeError("timing_result needs a timing_recovery and a block that ran")
         return _hip.to_host(self._timing_tau), _hip.to_host(self._timing_choice)
+
+    def _acquisition_init(self, acquisition, sps: int, framing, recovery, timing_recovery) -> None:
+        """``acquisition``: a ``waveforms_amd.sync.joint.JointAcquisition`` that makes the detector's rows from the noisy samples
+        under a carrier AND a timing offset (``carrier=`` and ``timing=`` may both be given beside it).  None: nothing is added to
+        the chain.  Checked against the link's other keywords before anything touches the device."""
+        if acquisition is not None:
+            from ..sync.joint import JointAcquisition
+
+            if not isinstance(acquisition, JointAcquisition):
+                raise ValueError("acquisition is a waveforms_amd.sync.joint.JointAcquisition")
+            if recovery is not None or timing_recovery is not None:
+                raise ValueError("acquisition excludes recovery and timing_recovery: it recovers the carrier and the timing itself")
+            if acquisition.sps != sps:
+                raise ValueError(f"the acquisition is for sps = {acquisition.sps}, the link has {sps}")
+            if framing is None:
+                raise ValueError("acquisition needs a framing: the instant and the phase are recovered modulo (sps, π/2) and (0, π), "
+                                 "and the frame search absorbs the shift and the polarity")
+        self.acquisition = acquisition
+        self._acq = None
+
+    def acquisition_result(self):
+        """(tau float64[nwin] in samples, phase float64[nwin] in radians - both modulo the lattice of waveforms_amd/sync/joint.py;
+        timing choice uint8[nwin]; carrier choice uint8[nwin]) of the last block's acquisition - synchronises."""
+        if self.acquisition is None or self._acq is None:
+            raise RuntimeError("acquisition_result needs an acquisition and a block that ran")
+        return tuple(_hip.to_host(v) for v in self._acq)
 
     def _clock_init(self, clock, clock_recovery, spec, sps: int, framing, carrier, recovery) -> None:
         """``clock=(tau0, eps)`` and ``clock_recovery`` of the CPM links: ``_timing_init``'s pair for the generic CPM trellis, with
@@ -306,11 +338,12 @@ class _SOQPSK(_Link):
 
     bits_per_symbol, _lam0 = 1, 1
 
-    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", *, timing=None, timing_recovery=None, **burst) -> None:
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", *, timing=None, timing_recovery=None, acquisition=None, **burst) -> None:
         if detector not in TIMING_OFFSET:
             raise ValueError(f"unknown detector {detector!r}")
         self.detector = detector
         self._timing_init(timing, timing_recovery, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
+        self._acquisition_init(acquisition, int(sps), burst.get("framing"), burst.get("recovery"), timing_recovery)
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -345,6 +378,10 @@ class _SOQPSK(_Link):
             received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
             rows, self._timing_tau, self._timing_choice = self.timing_recovery.recover(received, self._d_taps, first, ncols, True)
             return rows, syms
+        if self.acquisition is not None:
+            received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
+            rows, *self._acq = self.acquisition.recover(received, self._d_taps, first, ncols, True)
+            return rows, syms
         rows = dev.awgn_mf_bank(sig, self._d_taps, first, self.sps, ncols, self.sigma(ebn0_db), seed, stream_id, 0,
                                 np.exp(-1j * np.pi / 4))
         return rows, syms
@@ -367,12 +404,15 @@ class _SOQPSK(_Link):
         return dev.viterbi_soft_apriori(rows, prior, self.damping)
 
     def count_uncoded(self, hard, tx, syms) -> None:
-        if self.timing_recovery is None:            # (recovered rows may sit two rows from the sent bits: nothing to compare at)
+        if self.timing_recovery is None and self.acquisition is None:      # (recovered rows may sit a row or two from the sent bits: nothing to compare at)
             dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
 
     def uncoded_result(self) -> tuple[int, int]:
         if self.timing_recovery is not None:
             raise RuntimeError("uncoded_result: a timing recovery leaves the rows two rows early or late in some bursts; "
+                               "the channel bits are not counted (the decoder's counts hold)")
+        if self.acquisition is not None:
+            raise RuntimeError("uncoded_result: an acquisition leaves the rows a few rows early or late, and inverted, in some bursts; "
                                "the channel bits are not counted (the decoder's counts hold)")
         return super().uncoded_result()
 
@@ -508,10 +548,10 @@ class CodedSOQPSKLink(_LDPC, _SOQPSK):
     is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0, carrier=None, recovery=None, timing=None, timing_recovery=None) -> None:
+                 lead_bits: int = 0, carrier=None, recovery=None, timing=None, timing_recovery=None, acquisition=None) -> None:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
-        super().__init__(code, ncw, sps, detector, timing=timing, timing_recovery=timing_recovery, framing=framing, lead_bits=lead_bits,
-                         carrier=carrier, recovery=recovery)
+        super().__init__(code, ncw, sps, detector, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition, framing=framing,
+                         lead_bits=lead_bits, carrier=carrier, recovery=recovery)
 
 
 class CodedCPMLink(_LDPC, _CPM):
@@ -643,13 +683,13 @@ class IterativeSOQPSKLink(_LDPCLoop, CodedSOQPSKLink):
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
                  lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD, carrier=None,
-                 recovery=None, timing=None, timing_recovery=None) -> None:
+                 recovery=None, timing=None, timing_recovery=None, acquisition=None) -> None:
         if int(guard) < 0:
             raise ValueError(f"guard = {guard} must not be negative")
         self.live_only, self.guard = bool(live_only), int(guard)
         super().__init__(code, ncw, sps=sps, detector=detector, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
                          ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, carrier=carrier,
-                         recovery=recovery, timing=timing, timing_recovery=timing_recovery)
+                         recovery=recovery, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition)
         self.live_counts = _hip.zeros((self.outer, 3), "int64") if self.live_only else None
         self.windows = _hip.zeros(4 + 2 * self.ncw, "int64") if self.live_only else None
         self._live_out, self._live_first = None, 0          # the block's ext / bits buffers; first passes run

@@ -16,7 +16,7 @@ the pass whose Σ Re q is most negative.  The trellis is symmetric under a rotat
 
 Limits.  The phase must stay within the decision-directed pull-in across one window: the supported frequency offset is
 |nu| sps W <= ``MAX_DRIFT_TURNS`` turns per window (nu in cycles per sample), measured on ``recover_host``
-(tests/test_carrier.py).  No timing recovery; the hypothesis rotation is a pass of its own over the rows (not fused into
+(tests/test_carrier.py).  No timing recovery here (both at once: ``waveforms_amd.sync.joint.JointAcquisition``); the hypothesis rotation is a pass of its own over the rows (not fused into
 the detector's row load); the recovery passes carry no prior.  H hypotheses cost H detections: the price of needing no
 sequential loop.  The CPM detectors (ARTM, PCM/FM) have the same scheme in ``waveforms_amd.sync.carrier_cpm``, which shares
 ``carrier_track_host`` (with its period) and ``interpolate_phase_host`` with this module.

@@ -31,8 +31,8 @@ as it absorbs the carrier recovery's π.
 Limits.  The instant must stay within the pull-in of one hypothesis across a window: the supported drift is
 |eps| sps W <= ``MAX_DRIFT_SAMPLES`` samples per window.  The statistic's minimum is not the reference's hand-tuned offset
 (``BIAS_SAMPLES``); the recovery goes to the minimum.  The drift is taken as ONE rate over the burst (``rescale_host`` below).
-No carrier recovery at the same time (a two-dimensional search), SOQPSK-TG
-only, and the interpolation is a pass of its own over the samples per hypothesis (not fused into the detector's row load).
+No carrier recovery at the same time here: the two-dimensional search is ``waveforms_amd.sync.joint.JointAcquisition``.
+SOQPSK-TG only, and the interpolation is a pass of its own over the samples per hypothesis (not fused into the detector's row load).
 """
 from __future__ import annotations
 
