@@ -8,16 +8,20 @@
 //                           its fraction in float64 before the multiply by 2π, one fp64 sincos per sample.
 //   carrier_stat_kernel     one WAVE per window of W rows: lane l adds the rows wW + 64 i + l (i increasing), so a wave's
 //                           loads are one row apart across lanes; the 64 partials are folded by a shuffle-down butterfly
-//                           (d = 32 .. 1) in the order the header states.  q = state_exp_term[start] z[idx] is a signed
-//                           pick of z's components: no product, nothing rounded but the sums.
+//                           (d = 32 .. 1, wf_sync.h) in the order the header states.  ONE body for both statistics: the
+//                           row's term comes from a fetch.  q = state_exp_term[start] z[idx] is a signed pick of z's
+//                           components (no product, nothing rounded but the sums), or the term wf_cpm_soft_branch wrote.
 //   carrier_track_kernel    ONE workgroup: per window the best hypothesis and its phase (threads in parallel), the
 //                           unwrapping modulo the period (π, or 2π/p for CPM) as a blocked scan (a segment of windows per thread, the 1024 segment sums
 //                           added in order: the definition's running sum to rounding), the centred mean (threads in
-//                           parallel).  The unwrapped phases pass through the context's detector scratch.
-//   rows_derotate_kernel    a thread per row of nvals values (3: the 48-byte rows; 4 / 16: PCM/FM / ARTM): one fp64 sincos a row.
+//                           parallel).  The unwrapped phases pass through the context's detector scratch.  The argmin, the
+//                           scan and the mean are wf_sync.h's, shared with timing_track_kernel.
+//   rows_derotate_kernel    a thread per row of nvals values (3: the 48-byte rows; 4 / 16: PCM/FM / ARTM): one fp64 sincos a row;
+//                           the row's phase is wf_sync.h's trajectory value, the rotation its sync_rotate.
 //
 // The phase arithmetic is written one operation per statement where the host statement must see the same roundings
 // (-ffp-contract=on fuses within an expression only).
+#include "wf_sync.h"
 #include "wf_viterbi4.h"
 
 #include <cmath>
@@ -49,79 +53,51 @@ __device__ __forceinline__ double2 carrier_q(int start, double2 z)
     return start == 0 ? make_double2(-z.y, z.x) : start == 1 ? make_double2(-z.x, -z.y) : start == 2 ? z : make_double2(z.y, -z.x);
 }
 
-// the 64 lane partials of a window folded by a shuffle-down butterfly, d = 32 .. 1; lane 0 writes (X_w, Y_w)
-__device__ __forceinline__ void carrier_fold(double px, double py, int lane, double *__restrict__ out)
-{
-#pragma unroll
-    for (int d = WF_WAVE / 2; d >= 1; d >>= 1) {        // p_l + p_{l+d} is what lanes l < d keep; the others' sums are never read
-        px += __shfl_down(px, d, WF_WAVE);
-        py += __shfl_down(py, d, WF_WAVE);
+// a row's term q_k = (x, y) formed from the row and its decided branch
+struct carrier_term_of_rows {
+    const double *__restrict__ rows;
+    const uint8_t *__restrict__ branch;
+    __device__ __forceinline__ double2 operator()(int64_t k) const
+    {
+        const int b = branch[k] & 7;
+        const double2 z = reinterpret_cast<const double2 *>(rows)[3 * k + br_out_idx((int)(k & 1), b)];
+        return carrier_q(b >> 1, z);
     }
+};
+
+// the same term as wf_cpm_soft_branch wrote it: q_k = (x_k, y_k) is read, not formed
+struct carrier_term_read {
+    const double2 *__restrict__ term;
+    __device__ __forceinline__ double2 operator()(int64_t k) const { return term[k]; }
+};
+
+template <class FETCH>
+__global__ __launch_bounds__(CARRIER_THREADS) void carrier_stat_kernel(const FETCH fetch, int64_t n, int W, int64_t nwin, double *__restrict__ stat)
+{
+    const int64_t w = (int64_t)blockIdx.x * CARRIER_WAVES + threadIdx.x / WF_WAVE;      // wave-uniform
+    if (w >= nwin) return;
+    const int lane = wf_lane();
+    double px = 0.0, py = 0.0;
+    for (int i = 0; i < W / WF_WAVE; ++i) {
+        const int64_t k = w * W + (int64_t)i * WF_WAVE + lane;
+        if (k < n) {
+            const double2 q = fetch(k);
+            px += q.x;
+            py += q.y;
+        }
+    }
+    px = sync_wave_fold(px);
+    py = sync_wave_fold(py);
     if (lane == 0) {
-        out[0] = px;
-        out[1] = py;
+        stat[2 * w] = px;
+        stat[2 * w + 1] = py;
     }
-}
-
-__global__ __launch_bounds__(CARRIER_THREADS) void carrier_stat_kernel(const double *__restrict__ rows, const uint8_t *__restrict__ branch, int64_t n, int W,
-                                                                       int64_t nwin, double *__restrict__ stat)
-{
-    const int64_t w = (int64_t)blockIdx.x * CARRIER_WAVES + threadIdx.x / WF_WAVE;      // wave-uniform
-    if (w >= nwin) return;
-    const int lane = wf_lane();
-    double px = 0.0, py = 0.0;
-    for (int i = 0; i < W / WF_WAVE; ++i) {
-        const int64_t k = w * W + (int64_t)i * WF_WAVE + lane;
-        if (k < n) {
-            const int b = branch[k] & 7;
-            const double2 z = reinterpret_cast<const double2 *>(rows)[3 * k + br_out_idx((int)(k & 1), b)];
-            const double2 q = carrier_q(b >> 1, z);
-            px += q.x;
-            py += q.y;
-        }
-    }
-    carrier_fold(px, py, lane, stat + 2 * w);
-}
-
-// the same statistic from the terms wf_cpm_soft_branch wrote: q_k = (x_k, y_k) is read, not formed
-__global__ __launch_bounds__(CARRIER_THREADS) void carrier_stat_terms_kernel(const double2 *__restrict__ term, int64_t n, int W, int64_t nwin,
-                                                                             double *__restrict__ stat)
-{
-    const int64_t w = (int64_t)blockIdx.x * CARRIER_WAVES + threadIdx.x / WF_WAVE;      // wave-uniform
-    if (w >= nwin) return;
-    const int lane = wf_lane();
-    double px = 0.0, py = 0.0;
-    for (int i = 0; i < W / WF_WAVE; ++i) {
-        const int64_t k = w * W + (int64_t)i * WF_WAVE + lane;
-        if (k < n) {
-            const double2 q = term[k];
-            px += q.x;
-            py += q.y;
-        }
-    }
-    carrier_fold(px, py, lane, stat + 2 * w);
-}
-
-// x - P ceil(x / P - 1/2): into (-P/2, P/2], P the period (π for SOQPSK-TG)
-__device__ __forceinline__ double carrier_wrap(double x, double period)
-{
-    const double r = x / period;
-    const double c = ceil(r - 0.5);
-    const double m = period * c;
-    return x - m;
 }
 
 __device__ __forceinline__ double carrier_psi(const double *stat, int H, int64_t nwin, double period, int64_t w, uint8_t *choice)
 {
-    int best = 0;
-    double bx = stat[2 * w];
-    for (int h = 1; h < H; ++h) {
-        const double x = stat[2 * ((int64_t)h * nwin + w)];
-        if (x < bx) {
-            bx = x;
-            best = h;
-        }
-    }
+    double bx;
+    const int best = sync_argmin(stat, H, nwin, w, &bx);
     if (choice) choice[w] = (uint8_t)best;
     const double by = stat[2 * ((int64_t)best * nwin + w) + 1];
     const double base = (double)best * period;
@@ -136,91 +112,30 @@ __global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const doub
     __shared__ double s_seg[TRACK_THREADS];
     for (int64_t w = threadIdx.x; w < nwin; w += TRACK_THREADS) tmp[w] = carrier_psi(stat, H, nwin, period, w, choice);      // ψ_w, once per window
     __syncthreads();
-    // u_w = ψ_0 + Σ_{j <= w} wrap(ψ_j - ψ_{j-1}) as a blocked scan: thread t owns the windows [a, e), adds its own steps, thread 0
-    // adds the 1024 segment sums in order, and every thread rewrites its ψ_w as offset + its running sum (ψ_{a-1}, the one value it
-    // needs of its neighbour's, is read before anybody writes)
-    const int64_t seg = (nwin + TRACK_THREADS - 1) / TRACK_THREADS;
-    const int64_t a = threadIdx.x * seg < nwin ? threadIdx.x * seg : nwin, e = a + seg < nwin ? a + seg : nwin;
-    const double before = a > 0 && a < nwin ? tmp[a - 1] : 0.0;
-    double sum = 0.0, prev = before;
-    for (int64_t w = a; w < e; ++w) {
-        const double psi = tmp[w];
-        sum += w == 0 ? psi : carrier_wrap(psi - prev, period);
-        prev = psi;
-    }
-    s_seg[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double off = 0.0;
-        for (int t = 0; t < TRACK_THREADS; ++t) {
-            const double v = s_seg[t];
-            s_seg[t] = off;
-            off += v;
-        }
-    }
-    __syncthreads();
-    const double off = s_seg[threadIdx.x];
-    sum = 0.0;
-    prev = before;
-    for (int64_t w = a; w < e; ++w) {
-        const double psi = tmp[w];
-        sum += w == 0 ? psi : carrier_wrap(psi - prev, period);
-        prev = psi;
-        tmp[w] = off + sum;
-    }
-    __syncthreads();
-    const int64_t r = span / 2;
-    for (int64_t w = threadIdx.x; w < nwin; w += TRACK_THREADS) {
-        const int64_t lo = w - r > 0 ? w - r : 0, hi = w + r < nwin - 1 ? w + r : nwin - 1;
-        double s = 0.0;
-        for (int64_t j = lo; j <= hi; ++j) s += tmp[j];
-        phase[w] = s / (double)(hi - lo + 1);
-    }
+    sync_unwrap_scan<TRACK_THREADS>(tmp, nwin, period, s_seg);
+    sync_centred_mean<TRACK_THREADS>(tmp, nwin, span, phase);
 }
 
 __global__ __launch_bounds__(CARRIER_THREADS) void rows_derotate_kernel(const double2 *rows, int64_t n, int nvals, int W, const double *__restrict__ phase,
                                                                         int64_t nwin, double phase0, double2 *out)
 {
-    const double c0 = 0.5 * (double)(W - 1);
     for (int64_t k = (int64_t)blockIdx.x * CARRIER_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * CARRIER_THREADS) {
-        double phi = 0.0;
-        if (phase) {
-            const double t = ((double)k - c0) / (double)W;      // window centres sit at the integers (W a power-of-two multiple or not: one division)
-            if (t <= 0.0) {
-                phi = phase[0];
-            } else if (t >= (double)(nwin - 1)) {
-                phi = phase[nwin - 1];
-            } else {
-                const double fl = floor(t);
-                const int64_t w = (int64_t)fl;
-                const double f = t - fl;
-                const double p0 = phase[w];
-                const double d = phase[w + 1] - p0;
-                const double fd = f * d;
-                phi = p0 + fd;
-            }
-        }
+        const double phi = phase ? sync_traj_at(phase, nwin, W, k) : 0.0;
         const double tot = phase0 + phi;
         double sn, cs;
         sincos(-tot, &sn, &cs);
-        for (int j = 0; j < nvals; ++j) {
-            const double2 z = rows[(int64_t)nvals * k + j];
-            out[(int64_t)nvals * k + j] = make_double2(z.x * cs - z.y * sn, z.x * sn + z.y * cs);
-        }
+        for (int j = 0; j < nvals; ++j) out[(int64_t)nvals * k + j] = sync_rotate(rows[(int64_t)nvals * k + j], cs, sn);
     }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-static bool carrier_mis(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-static bool carrier_window_ok(int W) { return W >= 64 && W <= 8192 && W % 64 == 0; }
-
 extern "C" int wf_carrier_offset_c128(wf_ctx *ctx, const double *d_in_ri, int64_t n, double theta0, double nu, int64_t first_index, double *d_out_ri,
                                       void *stream)
 {
     WF_REQUIRE(ctx && d_in_ri && d_out_ri, "wf_carrier_offset_c128: NULL argument");
     WF_REQUIRE(n >= 1 && first_index >= 0 && n <= ((int64_t)1 << 53) - first_index, "wf_carrier_offset_c128: n must be at least 1 and first_index + n at most 2^53");
     WF_REQUIRE(std::isfinite(theta0) && std::isfinite(nu), "wf_carrier_offset_c128: theta0 and nu must be finite");
-    WF_REQUIRE(!carrier_mis(d_in_ri, 15) && !carrier_mis(d_out_ri, 15), "wf_carrier_offset_c128: samples must be 16-byte aligned");
+    WF_REQUIRE(!sync_mis(d_in_ri, 15) && !sync_mis(d_out_ri, 15), "wf_carrier_offset_c128: samples must be 16-byte aligned");
     WF_HIP(hipSetDevice(ctx->device));
     hipLaunchKernelGGL(carrier_offset_kernel, dim3(wf_grid_for(n, CARRIER_THREADS, 1 << 16)), dim3(CARRIER_THREADS), 0, wf_stream(stream),
                        reinterpret_cast<const double2 *>(d_in_ri), n, theta0, nu, first_index, reinterpret_cast<double2 *>(d_out_ri));
@@ -232,12 +147,12 @@ extern "C" int wf_carrier_stat(wf_ctx *ctx, const double *d_rows, const uint8_t 
 {
     WF_REQUIRE(ctx && d_rows && d_branch && d_stat, "wf_carrier_stat: NULL argument");
     WF_REQUIRE(ncalls >= 1, "wf_carrier_stat: ncalls must be at least 1");
-    WF_REQUIRE(carrier_window_ok(W), "wf_carrier_stat: W must be a multiple of 64 from 64 to 8192");
-    WF_REQUIRE(!carrier_mis(d_rows, 15) && !carrier_mis(d_stat, 7), "wf_carrier_stat: rows must be 16-byte and stat 8-byte aligned");
+    WF_REQUIRE(sync_window_ok(W), "wf_carrier_stat: W must be a multiple of 64 from 64 to 8192");
+    WF_REQUIRE(!sync_mis(d_rows, 15) && !sync_mis(d_stat, 7), "wf_carrier_stat: rows must be 16-byte and stat 8-byte aligned");
     const int64_t nwin = (ncalls + W - 1) / W;
     WF_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(carrier_stat_kernel, dim3((unsigned)((nwin + CARRIER_WAVES - 1) / CARRIER_WAVES)), dim3(CARRIER_THREADS), 0, wf_stream(stream), d_rows,
-                       d_branch, ncalls, W, nwin, d_stat);
+    hipLaunchKernelGGL(carrier_stat_kernel<carrier_term_of_rows>, dim3((unsigned)((nwin + CARRIER_WAVES - 1) / CARRIER_WAVES)), dim3(CARRIER_THREADS), 0,
+                       wf_stream(stream), carrier_term_of_rows{d_rows, d_branch}, ncalls, W, nwin, d_stat);
     WF_LAUNCH_CHECK();
     return WF_OK;
 }
@@ -246,12 +161,12 @@ extern "C" int wf_carrier_stat_terms(wf_ctx *ctx, const double *d_term, int64_t 
 {
     WF_REQUIRE(ctx && d_term && d_stat, "wf_carrier_stat_terms: NULL argument");
     WF_REQUIRE(ncalls >= 1, "wf_carrier_stat_terms: ncalls must be at least 1");
-    WF_REQUIRE(carrier_window_ok(W), "wf_carrier_stat_terms: W must be a multiple of 64 from 64 to 8192");
-    WF_REQUIRE(!carrier_mis(d_term, 15) && !carrier_mis(d_stat, 7), "wf_carrier_stat_terms: terms must be 16-byte and stat 8-byte aligned");
+    WF_REQUIRE(sync_window_ok(W), "wf_carrier_stat_terms: W must be a multiple of 64 from 64 to 8192");
+    WF_REQUIRE(!sync_mis(d_term, 15) && !sync_mis(d_stat, 7), "wf_carrier_stat_terms: terms must be 16-byte and stat 8-byte aligned");
     const int64_t nwin = (ncalls + W - 1) / W;
     WF_HIP(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(carrier_stat_terms_kernel, dim3((unsigned)((nwin + CARRIER_WAVES - 1) / CARRIER_WAVES)), dim3(CARRIER_THREADS), 0, wf_stream(stream),
-                       reinterpret_cast<const double2 *>(d_term), ncalls, W, nwin, d_stat);
+    hipLaunchKernelGGL(carrier_stat_kernel<carrier_term_read>, dim3((unsigned)((nwin + CARRIER_WAVES - 1) / CARRIER_WAVES)), dim3(CARRIER_THREADS), 0,
+                       wf_stream(stream), carrier_term_read{reinterpret_cast<const double2 *>(d_term)}, ncalls, W, nwin, d_stat);
     WF_LAUNCH_CHECK();
     return WF_OK;
 }
@@ -264,7 +179,7 @@ static int carrier_track_run(const char *who, wf_ctx *ctx, const double *d_stat_
     WF_REQUIRE(nwin >= 1 && nwin <= ((int64_t)1 << 40), "%s: nwin must be at least 1", who);
     WF_REQUIRE(span >= 1 && span % 2 == 1, "%s: span must be odd and at least 1", who);
     WF_REQUIRE(std::isfinite(period) && period > 0.0 && period <= kCarrierTwoPi, "%s: period must be in (0, 2 pi]", who);
-    WF_REQUIRE(!carrier_mis(d_stat_h, 7) && !carrier_mis(d_phase, 7), "%s: stat and phase must be 8-byte aligned", who);
+    WF_REQUIRE(!sync_mis(d_stat_h, 7) && !sync_mis(d_phase, 7), "%s: stat and phase must be 8-byte aligned", who);
     WF_HIP(hipSetDevice(ctx->device));
     const int rc = wf_ctx_reserve_vit(ctx, (size_t)nwin);
     if (rc) return rc;
@@ -292,8 +207,8 @@ static int rows_derotate_run(const char *who, wf_ctx *ctx, const double *d_rows,
     WF_REQUIRE(ncalls >= 1, "%s: ncalls must be at least 1", who);
     WF_REQUIRE(nvals >= 1 && nvals <= 64, "%s: nvals must be 1 .. 64", who);
     WF_REQUIRE(std::isfinite(phase0), "%s: phase0 must be finite", who);
-    WF_REQUIRE(!d_phase || (carrier_window_ok(W) && nwin >= 1), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
-    WF_REQUIRE(!carrier_mis(d_rows, 15) && !carrier_mis(d_out, 15) && !carrier_mis(d_phase, 7), "%s: rows must be 16-byte and phase 8-byte aligned", who);
+    WF_REQUIRE(!d_phase || (sync_window_ok(W) && nwin >= 1), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
+    WF_REQUIRE(!sync_mis(d_rows, 15) && !sync_mis(d_out, 15) && !sync_mis(d_phase, 7), "%s: rows must be 16-byte and phase 8-byte aligned", who);
     WF_HIP(hipSetDevice(ctx->device));
     hipLaunchKernelGGL(rows_derotate_kernel, dim3(wf_grid_for(ncalls, CARRIER_THREADS, 1 << 16)), dim3(CARRIER_THREADS), 0, wf_stream(stream),
                        reinterpret_cast<const double2 *>(d_rows), ncalls, nvals, d_phase ? W : 64, d_phase, nwin, phase0, reinterpret_cast<double2 *>(d_out));

@@ -16,8 +16,8 @@
 //                                 __launch_bounds__(256, 4) and three taps' loads in flight in phase C: 128 VGPRs, no spill, four
 //                                 waves a SIMD; at 130 VGPRs and three waves the kernel took 1.2 times as long on 1e7 calls
 //                                 (profiles/timing_recovery_cpm.json).
-//   llr_stat_kernel               one WAVE per window: carrier_stat_kernel's order of additions on |λ|.
-#include "wf_timing.h"
+//   llr_stat_kernel               one WAVE per window: carrier_stat_kernel's order of additions on |λ| (the fold is wf_sync.h's).
+#include "wf_sync.h"
 
 #include <climits>
 
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(CRS_THREADS, 4) void cpm_mf_rows_resample_kernel(co
         const bool row = t < P.syms && n < P.ncalls;
         double tk = P.tau0;
         if (row && P.tau) {
-            const double phi = timing_tau_at(P.tau, P.nwin, P.W, n);
+            const double phi = sync_traj_at(P.tau, P.nwin, P.W, n);
             tk = P.tau0 + phi;
         }
         bool live = row && fabs(tk) < kTimingHuge;             // (false for a NaN)
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(CRS_THREADS, 4) void cpm_mf_rows_resample_kernel(co
 }
 
 // d_stat[2w] = -Σ |λ| over the window's values in carrier_stat_kernel's order (64 lane partials from +0, index increasing, then
-// the shuffle-down butterfly d = 32 .. 1); d_stat[2w + 1] = +0
+// sync_wave_fold's butterfly d = 32 .. 1); d_stat[2w + 1] = +0
 __global__ __launch_bounds__(LSTAT_THREADS) void llr_stat_kernel(const double *__restrict__ llr, int64_t nvals, int64_t per, int64_t nwin,
                                                                  double *__restrict__ stat)
 {
@@ -191,8 +191,7 @@ __global__ __launch_bounds__(LSTAT_THREADS) void llr_stat_kernel(const double *_
         const int64_t end = base + per < nvals ? base + per : nvals;
         double p = 0.0;
         for (int64_t i = base + lane; i < end; i += WF_WAVE) p += fabs(llr[i]);
-#pragma unroll
-        for (int d = WF_WAVE / 2; d >= 1; d >>= 1) p += __shfl_down(p, d, WF_WAVE);
+        p = sync_wave_fold(p);
         if (lane == 0) {
             stat[2 * w] = -p;
             stat[2 * w + 1] = 0.0;
@@ -254,8 +253,8 @@ extern "C" int wf_cpm_mf_rows_resample_c128(wf_ctx *ctx, const double *d_r_ri, i
     WF_REQUIRE(nsamp >= 1 && nsamp <= kTimingMaxN && ncalls >= 1 && ncalls <= kTimingMaxN && start0 >= -kTimingMaxN && start0 <= kTimingMaxN,
                "%s: nsamp and ncalls must be 1 .. 2^40 and |start0| at most 2^40", who);
     WF_REQUIRE(std::isfinite(tau0), "%s: tau0 must be finite", who);
-    WF_REQUIRE(!d_tau || (timing_window_ok(W) && nwin >= 1 && nwin <= kTimingMaxN), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
-    WF_REQUIRE(!timing_mis(d_r_ri, 15) && !timing_mis(d_templates_ri, 15) && !timing_mis(d_rows_ri, 15) && !timing_mis(d_tau, 7),
+    WF_REQUIRE(!d_tau || (sync_window_ok(W) && nwin >= 1 && nwin <= kTimingMaxN), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
+    WF_REQUIRE(!sync_mis(d_r_ri, 15) && !sync_mis(d_templates_ri, 15) && !sync_mis(d_rows_ri, 15) && !sync_mis(d_tau, 7),
                "%s: samples, templates and rows must be 16-byte and tau 8-byte aligned", who);
     crs_params P;
     size_t lds = 0;
@@ -296,8 +295,8 @@ extern "C" int wf_llr_stat(wf_ctx *ctx, const double *d_llr, int64_t ncalls, int
     WF_REQUIRE(ctx && d_llr && d_stat, "wf_llr_stat: NULL argument");
     WF_REQUIRE(ncalls >= 1 && ncalls <= kTimingMaxN, "wf_llr_stat: ncalls must be 1 .. 2^40");
     WF_REQUIRE(bits_per_call >= 1 && bits_per_call <= 8, "wf_llr_stat: bits_per_call must be 1 .. 8, not %d", bits_per_call);
-    WF_REQUIRE(timing_window_ok(W), "wf_llr_stat: W must be a multiple of 64 from 64 to 8192");
-    WF_REQUIRE(!timing_mis(d_llr, 7) && !timing_mis(d_stat, 7), "wf_llr_stat: llr and stat must be 8-byte aligned");
+    WF_REQUIRE(sync_window_ok(W), "wf_llr_stat: W must be a multiple of 64 from 64 to 8192");
+    WF_REQUIRE(!sync_mis(d_llr, 7) && !sync_mis(d_stat, 7), "wf_llr_stat: llr and stat must be 8-byte aligned");
     WF_HIP(hipSetDevice(ctx->device));
     const int64_t nwin = (ncalls + W - 1) / W;
     hipLaunchKernelGGL(llr_stat_kernel, dim3(wf_grid_for(nwin, LSTAT_WAVES, 1 << 16)), dim3(LSTAT_THREADS), 0, wf_stream(stream), d_llr,

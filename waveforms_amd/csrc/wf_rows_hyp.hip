@@ -5,13 +5,13 @@
 // reads its row once (three 16-byte loads) and writes its H rotated copies.
 //
 // The values are bitwise wf_rows_derotate's at phase0 = ((double)h * π) / H: the same quotient, the same sum with the absent
-// trajectory's +0.0, the same device sincos of the same argument, and the same products written as the same expressions
-// (-ffp-contract=on fuses within an expression only, so both files contract alike).
+// trajectory's +0.0, the same device sincos of the same argument, and the same rotation: wf_sync.h's sync_rotate, one text for
+// both files (-ffp-contract=on fuses within an expression only, so both contract alike).
 //
 // Launch shape: memory-bound (48 B in, 48 H B out per row), a thread per row and a grid-stride loop as wf_rows_derotate;
 // across a wave the stores of one copy are 48 bytes apart, which the three 16-byte stores of neighbouring lanes fill without
 // gaps.  LDS: H <= 256 rotations of 16 bytes = 4 KiB.
-#include "wf_common.h"
+#include "wf_sync.h"
 
 #include <cmath>
 
@@ -37,9 +37,9 @@ __global__ __launch_bounds__(HYP_THREADS) void rows_derotate_hyp_kernel(const do
             for (int h = 0; h < H; ++h) {
                 const double cs = s_cs[h].x, sn = s_cs[h].y;
                 double2 *o = out + 3 * ((int64_t)h * stride + k);
-                o[0] = make_double2(z0.x * cs - z0.y * sn, z0.x * sn + z0.y * cs);
-                o[1] = make_double2(z1.x * cs - z1.y * sn, z1.x * sn + z1.y * cs);
-                o[2] = make_double2(z2.x * cs - z2.y * sn, z2.x * sn + z2.y * cs);
+                o[0] = sync_rotate(z0, cs, sn);
+                o[1] = sync_rotate(z1, cs, sn);
+                o[2] = sync_rotate(z2, cs, sn);
             }
         } else {
             for (int h = 0; h < H; ++h) {

@@ -6,7 +6,7 @@
 //   timing_offset_kernel    elementwise, out of place: four neighbours of one input sample, cubic Lagrange weights of the
 //                           fraction of tau0 + eps (first_index + n).
 //   mf_resample_kernel      a thread per output row, a workgroup per tile of rows.  Every thread forms its row's instant (the
-//                           interpolated trajectory, as rows_derotate_kernel forms its phase), the workgroup takes the smallest
+//                           interpolated trajectory, wf_sync.h's sync_traj_at), the workgroup takes the smallest
 //                           and the largest integer instant of the tile and stages that span of samples ONCE in LDS (coalesced
 //                           16 B loads, one pad slot per `step` samples for an even step so that the rows' ds_read_b128 walk
 //                           distinct banks: the layout of wf_mfbank.hip), zeros outside the burst.  A row then walks its
@@ -16,13 +16,14 @@
 //                           staged region (a trajectory that jumps by more than RS_EXTRA samples inside a tile) reads its
 //                           samples from global memory instead, bounds-checked, with the same arithmetic: nothing is read
 //                           from LDS that was not staged.
-//   timing_track_kernel     ONE workgroup, the structure of carrier_track_kernel: per window a value (threads in parallel) — the
-//                           argmin over the hypotheses and its guarded parabola vertex, or the vertex of a refinement's three
-//                           points —, for the track the unwrapping modulo the period as a blocked scan, then the centred mean.
+//   timing_track_kernel     ONE workgroup: per window a value (threads in parallel) — the argmin over the hypotheses and its
+//                           guarded parabola vertex, or the vertex of a refinement's three points —, for the track the
+//                           unwrapping modulo the period as a blocked scan, then the centred mean: the argmin, the scan and the
+//                           mean are wf_sync.h's, shared with carrier_track_kernel.
 //
 // The instants' arithmetic is written one operation per statement where the host statement must see the same roundings
 // (-ffp-contract=on fuses within an expression only).
-#include "wf_timing.h"
+#include "wf_sync.h"
 
 #include <climits>
 
@@ -137,10 +138,10 @@ __global__ __launch_bounds__(RS_THREADS) void mf_resample_kernel(const double2 *
     for (int64_t blk = blockIdx.x; blk < P.nblk; blk += gridDim.x) {
         const int64_t k = blk * P.ob + t;
         const bool row = t < P.ob && k < P.ncols;
-        // the row's instant: tau0 + τ_k, τ interpolated between the window centres as rows_derotate_kernel interpolates its phase
+        // the row's instant: tau0 + τ_k, τ interpolated between the window centres
         double tk = P.tau0;
         if (row && P.tau) {
-            const double phi = timing_tau_at(P.tau, P.nwin, P.W, k);
+            const double phi = sync_traj_at(P.tau, P.nwin, P.W, k);
             tk = P.tau0 + phi;
         }
         bool live = row && fabs(tk) < kTimingHuge;             // (false for a NaN)
@@ -231,14 +232,6 @@ __device__ __forceinline__ double timing_vertex(double a, double b, double c, do
     return v > lim ? lim : (v < -lim ? -lim : v);
 }
 
-__device__ __forceinline__ double timing_wrap(double x, double period)
-{
-    const double r = x / period;
-    const double c = ceil(r - 0.5);
-    const double m = period * c;
-    return x - m;
-}
-
 // TRACK: ψ_w of H hypotheses, unwrapped modulo the period; otherwise scale * V of the three points of a refinement.  Then the mean.
 template <bool TRACK>
 __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const double *__restrict__ stat, int H, int64_t nwin, int span, double scale, double *tmp,
@@ -247,15 +240,8 @@ __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const doub
     __shared__ double s_seg[TTRACK_THREADS];
     for (int64_t w = threadIdx.x; w < nwin; w += TTRACK_THREADS) {
         if (TRACK) {
-            int best = 0;
-            double bx = stat[2 * w];
-            for (int h = 1; h < H; ++h) {
-                const double x = stat[2 * ((int64_t)h * nwin + w)];
-                if (x < bx) {
-                    bx = x;
-                    best = h;
-                }
-            }
+            double bx;
+            const int best = sync_argmin(stat, H, nwin, w, &bx);
             choice[w] = (uint8_t)best;
             const double a = stat[2 * ((int64_t)(best == 0 ? H - 1 : best - 1) * nwin + w)];
             const double c = stat[2 * ((int64_t)(best == H - 1 ? 0 : best + 1) * nwin + w)];
@@ -272,46 +258,8 @@ __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const doub
         }
     }
     __syncthreads();
-    if (TRACK) {
-        // u_w = ψ_0 + Σ_{j <= w} wrap(ψ_j - ψ_{j-1}) as carrier_track_kernel's blocked scan: thread t owns the windows [a, e)
-        const int64_t seg = (nwin + TTRACK_THREADS - 1) / TTRACK_THREADS;
-        const int64_t a = threadIdx.x * seg < nwin ? threadIdx.x * seg : nwin, e = a + seg < nwin ? a + seg : nwin;
-        const double before = a > 0 && a < nwin ? tmp[a - 1] : 0.0;
-        double sum = 0.0, prev = before;
-        for (int64_t w = a; w < e; ++w) {
-            const double psi = tmp[w];
-            sum += w == 0 ? psi : timing_wrap(psi - prev, scale);
-            prev = psi;
-        }
-        s_seg[threadIdx.x] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double off = 0.0;
-            for (int t = 0; t < TTRACK_THREADS; ++t) {
-                const double v = s_seg[t];
-                s_seg[t] = off;
-                off += v;
-            }
-        }
-        __syncthreads();
-        const double off = s_seg[threadIdx.x];
-        sum = 0.0;
-        prev = before;
-        for (int64_t w = a; w < e; ++w) {
-            const double psi = tmp[w];
-            sum += w == 0 ? psi : timing_wrap(psi - prev, scale);
-            prev = psi;
-            tmp[w] = off + sum;
-        }
-        __syncthreads();
-    }
-    const int64_t r = span / 2;
-    for (int64_t w = threadIdx.x; w < nwin; w += TTRACK_THREADS) {
-        const int64_t lo = w - r > 0 ? w - r : 0, hi = w + r < nwin - 1 ? w + r : nwin - 1;
-        double s = 0.0;
-        for (int64_t j = lo; j <= hi; ++j) s += tmp[j];
-        tau[w] = s / (double)(hi - lo + 1);
-    }
+    if (TRACK) sync_unwrap_scan<TTRACK_THREADS>(tmp, nwin, scale, s_seg);
+    sync_centred_mean<TTRACK_THREADS>(tmp, nwin, span, tau);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -322,7 +270,7 @@ extern "C" int wf_timing_offset_c128(wf_ctx *ctx, const double *d_in_ri, int64_t
     WF_REQUIRE(ctx && d_in_ri && d_out_ri, "wf_timing_offset_c128: NULL argument");
     WF_REQUIRE(n >= 1 && first_index >= 0 && n <= ((int64_t)1 << 53) - first_index, "wf_timing_offset_c128: n must be at least 1 and first_index + n at most 2^53");
     WF_REQUIRE(std::isfinite(tau0) && std::isfinite(eps), "wf_timing_offset_c128: tau0 and eps must be finite");
-    WF_REQUIRE(!timing_mis(d_in_ri, 15) && !timing_mis(d_out_ri, 15), "wf_timing_offset_c128: samples must be 16-byte aligned");
+    WF_REQUIRE(!sync_mis(d_in_ri, 15) && !sync_mis(d_out_ri, 15), "wf_timing_offset_c128: samples must be 16-byte aligned");
     {
         const uintptr_t a = reinterpret_cast<uintptr_t>(d_in_ri), b = reinterpret_cast<uintptr_t>(d_out_ri), bytes = (uintptr_t)n * 16;
         WF_REQUIRE(a + bytes <= b || b + bytes <= a, "wf_timing_offset_c128: out of place only (the output overlaps the input)");
@@ -345,8 +293,8 @@ extern "C" int wf_mf_bank_resample_c128(wf_ctx *ctx, const double *d_r_ri, int64
     WF_REQUIRE(nsamp >= 1 && nsamp <= kTimingMaxN && ncols >= 1 && ncols <= kTimingMaxN && first >= -kTimingMaxN && first <= kTimingMaxN,
                "%s: nsamp and ncols must be 1 .. 2^40 and |first| at most 2^40", who);
     WF_REQUIRE(std::isfinite(tau0), "%s: tau0 must be finite", who);
-    WF_REQUIRE(!d_tau || (timing_window_ok(W) && nwin >= 1 && nwin <= kTimingMaxN), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
-    WF_REQUIRE(!timing_mis(d_r_ri, 15) && !timing_mis(d_taps_ri, 15) && !timing_mis(d_out_ri, 15) && !timing_mis(d_tau, 7),
+    WF_REQUIRE(!d_tau || (sync_window_ok(W) && nwin >= 1 && nwin <= kTimingMaxN), "%s: W must be a multiple of 64 from 64 to 8192 and nwin at least 1", who);
+    WF_REQUIRE(!sync_mis(d_r_ri, 15) && !sync_mis(d_taps_ri, 15) && !sync_mis(d_out_ri, 15) && !sync_mis(d_tau, 7),
                "%s: samples, taps and rows must be 16-byte and tau 8-byte aligned", who);
     WF_HIP(hipSetDevice(ctx->device));
     rs_params P;
@@ -392,7 +340,7 @@ extern "C" int wf_timing_track(wf_ctx *ctx, const double *d_stat_h, int H, int64
     WF_REQUIRE(nwin >= 1 && nwin <= kTimingMaxN, "wf_timing_track: nwin must be at least 1");
     WF_REQUIRE(span >= 1 && span % 2 == 1, "wf_timing_track: span must be odd and at least 1");
     WF_REQUIRE(std::isfinite(period) && period > 0.0, "wf_timing_track: period must be finite and positive");
-    WF_REQUIRE(!timing_mis(d_stat_h, 7) && !timing_mis(d_tau, 7), "wf_timing_track: stat and tau must be 8-byte aligned");
+    WF_REQUIRE(!sync_mis(d_stat_h, 7) && !sync_mis(d_tau, 7), "wf_timing_track: stat and tau must be 8-byte aligned");
     WF_HIP(hipSetDevice(ctx->device));
     const int rc = wf_ctx_reserve_vit(ctx, (size_t)nwin);
     if (rc) return rc;
@@ -408,7 +356,7 @@ extern "C" int wf_timing_refine(wf_ctx *ctx, const double *d_stat3, int64_t nwin
     WF_REQUIRE(nwin >= 1 && nwin <= kTimingMaxN, "wf_timing_refine: nwin must be at least 1");
     WF_REQUIRE(span >= 1 && span % 2 == 1, "wf_timing_refine: span must be odd and at least 1");
     WF_REQUIRE(std::isfinite(delta) && delta > 0.0, "wf_timing_refine: delta must be finite and positive");
-    WF_REQUIRE(!timing_mis(d_stat3, 7) && !timing_mis(d_more, 7), "wf_timing_refine: stat and more must be 8-byte aligned");
+    WF_REQUIRE(!sync_mis(d_stat3, 7) && !sync_mis(d_more, 7), "wf_timing_refine: stat and more must be 8-byte aligned");
     WF_HIP(hipSetDevice(ctx->device));
     const int rc = wf_ctx_reserve_vit(ctx, (size_t)nwin);
     if (rc) return rc;

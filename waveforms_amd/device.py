@@ -255,6 +255,24 @@ def _rows48(rows) -> int:
     return nbytes // 48
 
 
+def _trajectory(name: str, traj) -> int:
+    """nwin of a per-window trajectory argument (``phase`` or ``tau``: contiguous device float64[nwin]); None: 0."""
+    if traj is None:
+        return 0
+    if traj.dtype != _hip.torch().float64 or not traj.is_contiguous() or traj.numel() < 1:
+        raise ValueError(f"{name} must be contiguous float64[nwin]")
+    return int(traj.numel())
+
+
+def _stat_out(out, nwin: int):
+    """Where a statistic goes: ``out`` checked as contiguous float64[nwin, 2], or a new table."""
+    if out is None:
+        return _hip.empty((nwin, 2), "float64")
+    if out.dtype != _hip.torch().float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
+        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    return out
+
+
 def carrier_offset(signal, theta0: float, nu: float, first_index: int = 0, out=None):
     """The carrier impairment at sample rate (``wf_carrier_offset_c128``; include/wfhip.h states the definition): out_k = in_k
     exp(j (theta0 + 2π frac(nu (first_index + k)))), ``nu`` in cycles per sample.  ``signal``: contiguous device float64[n, 2];
@@ -294,10 +312,7 @@ def carrier_stat(rows, branch, window: int, out=None, ctx=None):
     if branch.dtype != torch.uint8 or not branch.is_contiguous() or branch.numel() != ncalls:
         raise ValueError(f"branch must be {ncalls} contiguous bytes (one per row)")
     nwin = -(-ncalls // int(window))
-    if out is None:
-        out = _hip.empty((nwin, 2), "float64")
-    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
-        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    out = _stat_out(out, nwin)
     _hip.check(_hip.lib().wf_carrier_stat(_ctx(ctx), _hip.ptr(rows), _hip.ptr(branch), ncalls, int(window), _hip.ptr(out),
                                           _hip.stream()))
     return out
@@ -329,56 +344,39 @@ def carrier_stat_terms(term, window: int, out=None, ctx=None):
         raise ValueError("term must be contiguous float64[ncalls, 2]")
     ncalls = term.numel() // 2
     nwin = -(-ncalls // int(window))
-    if out is None:
-        out = _hip.empty((nwin, 2), "float64")
-    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
-        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    out = _stat_out(out, nwin)
     _hip.check(_hip.lib().wf_carrier_stat_terms(_ctx(ctx), _hip.ptr(term), ncalls, int(window), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def _derotate(c_fn: str, nvals, rows, ncalls: int, window: int, phase, phase0: float, out, ctx):
+    """``wf_rows_derotate`` (``nvals`` = (): its rows hold 3 values) or ``wf_rows_derotate_n`` (``nvals`` = (n,)) on checked rows."""
+    nwin = _trajectory("phase", phase)
+    if out is None:
+        out = _hip.empty(tuple(rows.shape), "float64")
+    elif out.dtype != _hip.torch().float64 or not out.is_contiguous() or out.numel() != rows.numel():
+        raise ValueError("out must be contiguous float64 of the rows' size")
+    _hip.check(getattr(_hip.lib(), c_fn)(_ctx(ctx), _hip.ptr(rows), ncalls, *nvals, int(window), _hip.ptr(phase), nwin, float(phase0), _hip.ptr(out),
+                                         _hip.stream()))
     return out
 
 
 def rows_derotate_n(rows, nvals: int, window: int = 64, phase=None, phase0: float = 0.0, out=None, ctx=None):
     """``rows_derotate`` for rows of ``nvals`` complex128 (``wf_rows_derotate_n``; include/wfhip.h states the definition): the
     rows ``cpm_mf_rows`` writes, float64[ncalls, nvals, 2] (ARTM 16, PCM/FM 4).  ``out=rows`` works in place."""
-    torch = _hip.torch()
     nvals = int(nvals)
     if not 1 <= nvals <= 64:
         raise ValueError(f"nvals = {nvals} outside 1 .. 64")
-    if rows.dtype != torch.float64 or not rows.is_contiguous() or rows.numel() == 0 or rows.numel() % (2 * nvals):
+    if rows.dtype != _hip.torch().float64 or not rows.is_contiguous() or rows.numel() == 0 or rows.numel() % (2 * nvals):
         raise ValueError(f"rows must be contiguous float64, a whole number of rows of {nvals} complex values")
-    ncalls = rows.numel() // (2 * nvals)
-    nwin = 0
-    if phase is not None:
-        if phase.dtype != torch.float64 or not phase.is_contiguous() or phase.numel() < 1:
-            raise ValueError("phase must be contiguous float64[nwin]")
-        nwin = int(phase.numel())
-    if out is None:
-        out = _hip.empty(tuple(rows.shape), "float64")
-    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows.numel():
-        raise ValueError("out must be contiguous float64 of the rows' size")
-    _hip.check(_hip.lib().wf_rows_derotate_n(_ctx(ctx), _hip.ptr(rows), ncalls, nvals, int(window), _hip.ptr(phase), nwin,
-                                             float(phase0), _hip.ptr(out), _hip.stream()))
-    return out
+    return _derotate("wf_rows_derotate_n", (nvals,), rows, rows.numel() // (2 * nvals), window, phase, phase0, out, ctx)
 
 
 def rows_derotate(rows, window: int = 64, phase=None, phase0: float = 0.0, out=None, ctx=None):
     """48-byte rows times exp(-j (phase0 + φ_k)) (``wf_rows_derotate``; include/wfhip.h states the definition), φ interpolated
     between the centres of the windows of ``window`` rows from ``phase`` (device float64[nwin]; None: φ = 0).  ``out=rows``
     works in place."""
-    torch = _hip.torch()
-    ncalls = _rows48(rows)
-    nwin = 0
-    if phase is not None:
-        if phase.dtype != torch.float64 or not phase.is_contiguous() or phase.numel() < 1:
-            raise ValueError("phase must be contiguous float64[nwin]")
-        nwin = int(phase.numel())
-    if out is None:
-        out = _hip.empty(tuple(rows.shape), "float64")
-    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != rows.numel():
-        raise ValueError("out must be contiguous float64 of the rows' size")
-    _hip.check(_hip.lib().wf_rows_derotate(_ctx(ctx), _hip.ptr(rows), ncalls, int(window), _hip.ptr(phase), nwin,
-                                           float(phase0), _hip.ptr(out), _hip.stream()))
-    return out
+    return _derotate("wf_rows_derotate", (), rows, _rows48(rows), window, phase, phase0, out, ctx)
 
 
 def rows_derotate_hyp(rows, hypotheses: int, stride: int | None = None, out=None, ctx=None):
@@ -455,11 +453,7 @@ def mf_bank_resample(received, taps, first: int, step: int, ncols: int, window: 
         raise ValueError("taps must be contiguous float64[3, ntaps, 2]")
     nsamp, ncols = received.numel() // 2, int(ncols)
     nfilt, ntaps = int(taps.shape[0]), int(taps.shape[1])
-    nwin = 0
-    if tau is not None:
-        if tau.dtype != torch.float64 or not tau.is_contiguous() or tau.numel() < 1:
-            raise ValueError("tau must be contiguous float64[nwin]")
-        nwin = int(tau.numel())
+    nwin = _trajectory("tau", tau)
     if out is None:
         out = _hip.empty((max(ncols, 1), 3, 2), "float64")[:max(ncols, 0)]
     elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 6 * ncols:
@@ -507,11 +501,7 @@ def cpm_mf_rows_resample(received, templates, start0: int, sps: int, ncalls: int
         raise ValueError("templates must be contiguous float64[nh, nfilt, ntm, 2]")
     nsamp, ncalls = received.numel() // 2, int(ncalls)
     nh, nfilt, ntm = (int(v) for v in templates.shape[:3])
-    nwin = 0
-    if tau is not None:
-        if tau.dtype != torch.float64 or not tau.is_contiguous() or tau.numel() < 1:
-            raise ValueError("tau must be contiguous float64[nwin]")
-        nwin = int(tau.numel())
+    nwin = _trajectory("tau", tau)
     if out is None:
         out = _hip.empty((max(ncalls, 1), nfilt, 2), "float64")[:max(ncalls, 0)]
     elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nfilt * ncalls:
@@ -540,10 +530,7 @@ def llr_stat(llr, bits_per_call: int, window: int, out=None, ctx=None):
         raise ValueError("llr must be contiguous float64, bits_per_call values for each of at least one call")
     ncalls = llr.numel() // bits_per_call
     nwin = -(-ncalls // int(window))
-    if out is None:
-        out = _hip.empty((nwin, 2), "float64")
-    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * nwin:
-        raise ValueError(f"out must be contiguous float64[{nwin}, 2]")
+    out = _stat_out(out, nwin)
     _hip.check(_hip.lib().wf_llr_stat(_ctx(ctx), _hip.ptr(llr), ncalls, bits_per_call, int(window), _hip.ptr(out), _hip.stream()))
     return out
 

@@ -27,6 +27,9 @@ import math
 
 import numpy as np
 
+from . import _stages
+from ._stages import _wrap, check_window as _check_window
+
 DEFAULT_WINDOW = 256
 DEFAULT_SPAN = 5
 DEFAULT_HYPOTHESES = 8
@@ -57,13 +60,6 @@ def _rows3(rows) -> np.ndarray:
     if z.dtype != np.complex128:
         z = np.ascontiguousarray(z, dtype=np.float64).reshape(-1, 3, 2).view(np.complex128)
     return np.ascontiguousarray(z).reshape(-1, 3)
-
-
-def _check_window(window: int) -> int:
-    window = int(window)
-    if not (64 <= window <= 8192 and window % 64 == 0):
-        raise ValueError(f"window = {window} must be a multiple of 64 from 64 to 8192")
-    return window
 
 
 def carrier_phase_host(n: int, theta0: float, nu: float, first_index: int = 0) -> np.ndarray:
@@ -153,26 +149,7 @@ def stat_terms_host(x, y, window: int = DEFAULT_WINDOW) -> np.ndarray:
     """(X_w, Y_w) from the terms themselves, in ``wf_carrier_stat``'s order of additions (``wf_carrier_stat_terms``)."""
     window = _check_window(window)
     x, y = np.asarray(x, dtype=np.float64).reshape(-1), np.asarray(y, dtype=np.float64).reshape(-1)
-    n = x.size
-    nwin = -(-n // window)
-    out = np.empty((nwin, 2))
-    for j, v in enumerate((x, y)):
-        pad = np.zeros(nwin * window)                      # a partial that starts from +0 is never -0: adding +0 adds nothing
-        pad[:n] = v
-        pad = pad.reshape(nwin, window // 64, 64)
-        p = np.zeros((nwin, 64))
-        for i in range(window // 64):
-            p = p + pad[:, i, :]
-        d = 32
-        while d >= 1:
-            p[:, :d] = p[:, :d] + p[:, d:2 * d]
-            d //= 2
-        out[:, j] = p[:, 0]
-    return out
-
-
-def _wrap(x, period):
-    return x - period * np.ceil(x / period - 0.5)
+    return np.stack((_stages.window_sum(x, window), _stages.window_sum(y, window)), axis=1)
 
 
 def _wrap_pi(x):
@@ -189,27 +166,12 @@ def carrier_track_host(stat, span: int = DEFAULT_SPAN, period: float = math.pi):
     if stat.ndim == 2:
         stat = stat[None]
     H, nwin = stat.shape[0], stat.shape[1]
-    span = int(span)
-    if span < 1 or span % 2 == 0:
-        raise ValueError(f"span = {span} must be odd and at least 1")
+    span = _stages.check_span(span)
     choice = np.argmin(stat[:, :, 0], axis=0)              # the first of equal minima
     w = np.arange(nwin)
     bx, by = stat[choice, w, 0], stat[choice, w, 1]
     psi = (choice.astype(np.float64) * period) / float(H) + np.arctan2(-by, -bx)
-    u = np.empty(nwin)
-    u[0] = psi[0]
-    delta = _wrap(psi[1:] - psi[:-1], period)
-    for j in range(1, nwin):
-        u[j] = u[j - 1] + delta[j - 1]
-    r = span // 2
-    phase = np.empty(nwin)
-    for j in range(nwin):
-        lo, hi = max(0, j - r), min(nwin - 1, j + r)
-        s = 0.0
-        for i in range(lo, hi + 1):
-            s += u[i]
-        phase[j] = s / float(hi - lo + 1)
-    return phase, choice.astype(np.uint8)
+    return _stages.centred_mean(_stages.unwrap(psi, period), span), choice.astype(np.uint8)
 
 
 def interpolate_phase_host(ncalls: int, window: int, phase) -> np.ndarray:
@@ -231,10 +193,7 @@ def interpolate_phase_host(ncalls: int, window: int, phase) -> np.ndarray:
 
 def derotate_host(rows, window: int = 64, phase=None, phase0: float = 0.0) -> np.ndarray:
     """``wf_rows_derotate``: complex128[n, 3] times exp(-j (phase0 + φ_k)); ``phase=None``: φ = 0."""
-    z = _rows3(rows)
-    phi = 0.0 if phase is None else interpolate_phase_host(z.shape[0], window, phase)
-    tot = -(float(phase0) + phi) + np.zeros(z.shape[0])
-    return z * (np.cos(tot) + 1j * np.sin(tot))[:, None]
+    return _stages.derotate(_rows3(rows), window, phase, phase0)
 
 
 def estimate_host(rows, differential: bool = True) -> float:
@@ -254,16 +213,11 @@ def recover_host(rows, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, h
     for h in range(H):
         zh = derotate_host(z, phase0=(float(h) * math.pi) / float(H))
         stats.append(carrier_stat_host(zh, map_branch_host(zh, differential)[2], window))
-    phase, choice = carrier_track_host(np.stack(stats), span)
-    out = derotate_host(z, window, phase)
-    for _ in range(int(refine)):
-        more, _c = carrier_track_host(carrier_stat_host(out, map_branch_host(out, differential)[2], window)[None], span)
-        phase = phase + more
-        out = derotate_host(z, window, phase)
-    return out, phase, choice
+    return _stages.carrier_recover_host(np.stack(stats), lambda out: carrier_stat_host(out, map_branch_host(out, differential)[2], window),
+                                        lambda phase: derotate_host(z, window, phase), span, refine, math.pi)
 
 
-class CarrierRecovery:
+class CarrierRecovery(_stages.Synchroniser):
     """Carrier phase and frequency recovery of a burst of 48-byte detector rows, everything on the device:
 
     1. ``hypotheses`` passes of ``rows_derotate`` by h π / H -> ``viterbi_soft_branch`` -> ``carrier_stat``,
@@ -277,24 +231,11 @@ class CarrierRecovery:
 
     def __init__(self, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
                  refine: int = DEFAULT_REFINE) -> None:
+        super().__init__()
         self.window = _check_window(window)
-        self.span, self.hypotheses, self.refine = int(span), int(hypotheses), int(refine)
-        if self.span < 1 or self.span % 2 == 0:
-            raise ValueError(f"span = {span} must be odd and at least 1")
-        if not 1 <= self.hypotheses <= 256:
-            raise ValueError(f"hypotheses = {hypotheses} outside 1 .. 256")
-        if self.refine < 0:
-            raise ValueError(f"refine = {refine} must not be negative")
-        self.times = False
-        self._events: list = []
-
-    def _mark(self, name: str) -> None:
-        if self.times:
-            from .. import _hip
-
-            ev = _hip.torch().cuda.Event(enable_timing=True)
-            ev.record()
-            self._events.append((name, ev))
+        self.span = _stages.check_span(span)
+        self.hypotheses = _stages.check_range("hypotheses", hypotheses, 1, 256)
+        self.refine = _stages.check_refine(refine)
 
     def recover(self, rows, differential: bool = True, ctx=None):
         from .. import _hip
@@ -314,27 +255,17 @@ class CarrierRecovery:
             self._mark("soft_branch")
             dev.carrier_stat(work, branch, W, out=stat[h], ctx=ctx)
             self._mark("stat")
-        phase, choice = dev.carrier_track(stat, self.span, ctx=ctx)
-        self._mark("track")
-        dev.rows_derotate(rows, W, phase, out=work, ctx=ctx)
-        self._mark("derotate")
-        for _ in range(self.refine):
+
+        def statistic():
             _llr, _bits, branch = dev.viterbi_soft_branch(work, differential, ctx=ctx)
             self._mark("soft_branch")
             one = dev.carrier_stat(work, branch, W, ctx=ctx)
             self._mark("stat")
-            more, _c = dev.carrier_track(one.view(1, nwin, 2), self.span, ctx=ctx)
-            self._mark("track")
-            phase = phase + more
-            self._mark("add")
+            return one
+
+        def derotate_by(phase):
             dev.rows_derotate(rows, W, phase, out=work, ctx=ctx)
             self._mark("derotate")
-        return work, phase, choice
 
-    def stage_times(self) -> dict[str, float]:
-        """Milliseconds per stage of the last ``recover`` (``times=True``), summed over its passes - synchronises."""
-        out: dict[str, float] = {}
-        for (_n0, e0), (name, e1) in zip(self._events, self._events[1:]):
-            e1.synchronize()
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        return out
+        phase, choice = _stages.carrier_recover(self, stat, statistic, derotate_by, nwin, ctx)
+        return work, phase, choice

@@ -35,7 +35,8 @@ import math
 
 import numpy as np
 
-from .carrier import DEFAULT_SPAN, DEFAULT_WINDOW, _check_window, carrier_track_host, interpolate_phase_host, stat_terms_host
+from . import _stages
+from .carrier import DEFAULT_SPAN, DEFAULT_WINDOW, _check_window, stat_terms_host
 
 DEFAULT_HYPOTHESES = 2
 DEFAULT_REFINE = 1
@@ -162,10 +163,7 @@ def carrier_stat_terms_host(x, y, window: int = DEFAULT_WINDOW) -> np.ndarray:
 
 def derotate_n_host(spec, rows, window: int = 64, phase=None, phase0: float = 0.0) -> np.ndarray:
     """``wf_rows_derotate_n``: complex128[n, nfilt] times exp(-j (phase0 + φ_k)); ``phase=None``: φ = 0."""
-    z = _rows(spec, rows)
-    phi = 0.0 if phase is None else interpolate_phase_host(z.shape[0], window, phase)
-    tot = -(float(phase0) + phi) + np.zeros(z.shape[0])
-    return z * (np.cos(tot) + 1j * np.sin(tot))[:, None]
+    return _stages.derotate(_rows(spec, rows), window, phase, phase0)
 
 
 def recover_cpm_host(spec, rows, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
@@ -177,17 +175,15 @@ def recover_cpm_host(spec, rows, window: int = DEFAULT_WINDOW, span: int = DEFAU
     for h in range(H):
         _l, _b, _br, x, y = cpm_map_branch_host(spec, z, first_call, hypothesis_table(spec, (float(h) * P) / float(H)))
         stats.append(carrier_stat_terms_host(x, y, window))
-    phase, choice = carrier_track_host(np.stack(stats), span, P)
-    out = derotate_n_host(spec, z, window, phase)
-    for _ in range(int(refine)):
+
+    def statistic(out):
         _l, _b, _br, x, y = cpm_map_branch_host(spec, out, first_call)
-        more, _c = carrier_track_host(carrier_stat_terms_host(x, y, window)[None], span, P)
-        phase = phase + more
-        out = derotate_n_host(spec, z, window, phase)
-    return out, phase, choice
+        return carrier_stat_terms_host(x, y, window)
+
+    return _stages.carrier_recover_host(np.stack(stats), statistic, lambda phase: derotate_n_host(spec, z, window, phase), span, refine, P)
 
 
-class CPMCarrierRecovery:
+class CPMCarrierRecovery(_stages.Synchroniser):
     """Carrier phase and frequency recovery of a burst of CPM detector rows (float64[ncalls, nfilt, 2], what ``cpm_mf_rows``
     writes), everything on the device:
 
@@ -204,27 +200,14 @@ class CPMCarrierRecovery:
 
     def __init__(self, spec, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
                  refine: int = DEFAULT_REFINE) -> None:
+        super().__init__()
         _check_spec(spec)
         self.spec = spec
         self.window = _check_window(window)
-        self.span, self.hypotheses, self.refine = int(span), int(hypotheses), int(refine)
-        if self.span < 1 or self.span % 2 == 0:
-            raise ValueError(f"span = {span} must be odd and at least 1")
-        if not 1 <= self.hypotheses <= 256:
-            raise ValueError(f"hypotheses = {hypotheses} outside 1 .. 256")
-        if self.refine < 0:
-            raise ValueError(f"refine = {refine} must not be negative")
-        self.times = False
-        self._events: list = []
+        self.span = _stages.check_span(span)
+        self.hypotheses = _stages.check_range("hypotheses", hypotheses, 1, 256)
+        self.refine = _stages.check_refine(refine)
         self._tables = None
-
-    def _mark(self, name: str) -> None:
-        if self.times:
-            from .. import _hip
-
-            ev = _hip.torch().cuda.Event(enable_timing=True)
-            ev.record()
-            self._events.append((name, ev))
 
     def recover(self, rows, ctx=None, first_call: int = 0):
         from .. import _hip
@@ -243,27 +226,19 @@ class CPMCarrierRecovery:
             self._mark("soft_branch")
             dev.carrier_stat_terms(term, W, out=stat[h], ctx=ctx)
             self._mark("stat")
-        phase, choice = dev.carrier_track(stat, self.span, ctx=ctx, period=P)
-        self._mark("track")
-        work = dev.rows_derotate_n(rows, spec.nfilt, W, phase, ctx=ctx)
-        self._mark("derotate")
-        for _ in range(self.refine):
+        work = None                                              # the first derotation makes it, the later ones write into it
+
+        def statistic():
             _llr, _bits, _branch, term = dev.cpm_soft_branch(work, spec, first_call, 0, ctx=ctx, d_rot=self._tables[0])
             self._mark("soft_branch")
             one = dev.carrier_stat_terms(term, W, ctx=ctx)
             self._mark("stat")
-            more, _c = dev.carrier_track(one.view(1, nwin, 2), self.span, ctx=ctx, period=P)
-            self._mark("track")
-            phase = phase + more
-            self._mark("add")
-            dev.rows_derotate_n(rows, spec.nfilt, W, phase, out=work, ctx=ctx)
-            self._mark("derotate")
-        return work, phase, choice
+            return one
 
-    def stage_times(self) -> dict[str, float]:
-        """Milliseconds per stage of the last ``recover`` (``times=True``), summed over its passes - synchronises."""
-        out: dict[str, float] = {}
-        for (_n0, e0), (name, e1) in zip(self._events, self._events[1:]):
-            e1.synchronize()
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        return out
+        def derotate_by(phase):
+            nonlocal work
+            work = dev.rows_derotate_n(rows, spec.nfilt, W, phase, out=work, ctx=ctx)
+            self._mark("derotate")
+
+        phase, choice = _stages.carrier_recover(self, stat, statistic, derotate_by, nwin, ctx, P)
+        return work, phase, choice

@@ -40,7 +40,9 @@ import math
 
 import numpy as np
 
-from .carrier import DEFAULT_SPAN, DEFAULT_WINDOW, _check_window, _wrap, carrier_stat_host, interpolate_phase_host, map_branch_host
+from . import _stages
+from ._stages import centred_mean as _centred_mean
+from .carrier import DEFAULT_SPAN, DEFAULT_WINDOW, _check_window, carrier_stat_host, interpolate_phase_host, map_branch_host
 
 DEFAULT_HYPOTHESES = 8
 DEFAULT_REFINE = 1
@@ -145,21 +147,6 @@ def hypothesis_instants(period: float, H: int) -> np.ndarray:
     return np.arange(int(H), dtype=np.float64) * dh - 0.5 * float(period)
 
 
-def _centred_mean(u, span: int) -> np.ndarray:
-    span = int(span)
-    if span < 1 or span % 2 == 0:
-        raise ValueError(f"span = {span} must be odd and at least 1")
-    nwin, r = u.size, span // 2
-    out = np.empty(nwin)
-    for j in range(nwin):
-        lo, hi = max(0, j - r), min(nwin - 1, j + r)
-        s = 0.0
-        for i in range(lo, hi + 1):
-            s += u[i]
-        out[j] = s / float(hi - lo + 1)
-    return out
-
-
 def timing_track_host(stat, period: float, span: int = 1):
     """``wf_timing_track``: float64[H, nwin, 2] -> (tau f64[nwin] in samples, choice u8[nwin])."""
     period = float(period)
@@ -174,12 +161,7 @@ def timing_track_host(stat, period: float, span: int = 1):
     v = vertex_host(X[(choice - 1) % H, w], X[choice, w], X[(choice + 1) % H, w], 0.5)
     dh = period / float(H)
     psi = (choice.astype(np.float64) * dh - 0.5 * period) + dh * v
-    u = np.empty(nwin)
-    u[0] = psi[0]
-    step = _wrap(psi[1:] - psi[:-1], period)
-    for j in range(1, nwin):
-        u[j] = u[j - 1] + step[j - 1]
-    return _centred_mean(u, span), choice.astype(np.uint8)
+    return _centred_mean(_stages.unwrap(psi, period), span), choice.astype(np.uint8)
 
 
 def rescale_host(tau, samples_per_window: float) -> np.ndarray:
@@ -188,12 +170,8 @@ def rescale_host(tau, samples_per_window: float) -> np.ndarray:
     with a = 2, b = nwin - 3 (inside the clipped mean's lag at the two ends) for nwin >= 8 and a = 0, b = nwin - 1 otherwise; one
     window: unchanged.  s is ONE rate for the burst: the impairment's model, a constant eps."""
     tau = np.asarray(tau, dtype=np.float64).reshape(-1)
-    nwin = tau.size
-    if nwin < 2:
-        return tau.copy()
-    a, b = (2, nwin - 3) if nwin >= 8 else (0, nwin - 1)
-    s = (tau[b] - tau[a]) / (float(b - a) * float(samples_per_window))
-    return tau[0] + (tau - tau[0]) / (1.0 - s)
+    out = _stages.rescale(tau, tau.size, samples_per_window)
+    return tau.copy() if out is tau else out
 
 
 def timing_refine_host(stat3, delta: float, span: int = 1) -> np.ndarray:
@@ -214,14 +192,11 @@ def recover_timing_host(received, taps, first: int, ncols: int, sps: int, window
         rows = mf_bank_resample_host(received, taps, first, sps, ncols, window, tau, tau0)[0]
         return carrier_stat_host(rows, map_branch_host(rows, differential)[2], window)
 
-    tau, choice = timing_track_host(np.stack([stat_at(None, s) for s in hypothesis_instants(period, hypotheses)]), period, span)
-    tau = rescale_host(tau, float(sps) * float(window))
-    for _ in range(int(refine)):
-        tau = tau + timing_refine_host(np.stack([stat_at(tau, d) for d in (-float(delta), 0.0, float(delta))]), delta, span)
+    tau, choice = _stages.timing_recover_host(stat_at, period, float(sps) * float(window), span, hypotheses, refine, float(delta))
     return mf_bank_resample_host(received, taps, first, sps, ncols, window, tau)[0], tau, choice
 
 
-class TimingRecovery:
+class TimingRecovery(_stages.Synchroniser):
     """Symbol timing recovery of a burst of noisy samples at ``sps`` samples per symbol, everything on the device:
 
     1. ``hypotheses`` passes of ``mf_bank_resample`` at tau0 = s_h -> ``viterbi_soft_branch`` -> ``carrier_stat``,
@@ -236,34 +211,19 @@ class TimingRecovery:
 
     def __init__(self, sps: int, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
                  refine: int = DEFAULT_REFINE, delta: float = DEFAULT_DELTA) -> None:
-        self.sps, self.window = int(sps), _check_window(window)
-        self.span, self.hypotheses, self.refine, self.delta = int(span), int(hypotheses), int(refine), float(delta)
-        if not 1 <= self.sps <= 64:
-            raise ValueError(f"sps = {sps} outside 1 .. 64")
-        if self.span < 1 or self.span % 2 == 0:
-            raise ValueError(f"span = {span} must be odd and at least 1")
-        if not 3 <= self.hypotheses <= 64:
-            raise ValueError(f"hypotheses = {hypotheses} outside 3 .. 64")
-        if self.refine < 0:
-            raise ValueError(f"refine = {refine} must not be negative")
-        if not (math.isfinite(self.delta) and self.delta > 0.0):
-            raise ValueError(f"delta = {delta} must be finite and positive")
-        self.times = False
-        self._events: list = []
-
-    def _mark(self, name: str) -> None:
-        if self.times:
-            from .. import _hip
-
-            ev = _hip.torch().cuda.Event(enable_timing=True)
-            ev.record()
-            self._events.append((name, ev))
+        super().__init__()
+        self.window = _check_window(window)
+        self.sps = _stages.check_range("sps", sps, 1, 64)
+        self.span = _stages.check_span(span)
+        self.hypotheses = _stages.check_range("hypotheses", hypotheses, 3, 64)
+        self.refine = _stages.check_refine(refine)
+        self.delta = _stages.check_delta(delta)
 
     def recover(self, received, taps, first: int, ncols: int, differential: bool = True, ctx=None):
         from .. import _hip
         from .. import device as dev
 
-        H, W, ncols = self.hypotheses, self.window, int(ncols)
+        W, ncols = self.window, int(ncols)
         nwin = -(-ncols // W)
         period = 2.0 * float(self.sps)
         work = _hip.empty((ncols, 3, 2), "float64")
@@ -278,32 +238,7 @@ class TimingRecovery:
             dev.carrier_stat(work, branch, W, out=out, ctx=ctx)
             self._mark("stat")
 
-        stat = _hip.empty((H, nwin, 2), "float64")
-        for h, s in enumerate(hypothesis_instants(period, H)):
-            stat_at(None, float(s), stat[h])
-        tau, choice = dev.timing_track(stat, period, self.span, ctx=ctx)
-        self._mark("track")
-        if nwin >= 2:                                            # rescale_host, operation for operation
-            a, b = (2, nwin - 3) if nwin >= 8 else (0, nwin - 1)
-            s = (tau[b] - tau[a]) / (float(b - a) * (float(self.sps) * float(W)))
-            tau = tau[0] + (tau - tau[0]) / (1.0 - s)
-        self._mark("rescale")
-        for _ in range(self.refine):
-            stat3 = _hip.empty((3, nwin, 2), "float64")
-            for j, d in enumerate((-self.delta, 0.0, self.delta)):
-                stat_at(tau, d, stat3[j])
-            more = dev.timing_refine(stat3, self.delta, self.span, ctx=ctx)
-            self._mark("track")
-            tau = tau + more
-            self._mark("add")
+        tau, choice = _stages.timing_recover(self, stat_at, period, nwin, ctx)
         dev.mf_bank_resample(received, taps, first, self.sps, ncols, W, tau, 0.0, out=work, ctx=ctx)
         self._mark("resample")
         return work, tau, choice
-
-    def stage_times(self) -> dict[str, float]:
-        """Milliseconds per stage of the last ``recover`` (``times=True``), summed over its passes - synchronises."""
-        out: dict[str, float] = {}
-        for (_n0, e0), (name, e1) in zip(self._events, self._events[1:]):
-            e1.synchronize()
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        return out

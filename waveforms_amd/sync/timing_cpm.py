@@ -59,9 +59,10 @@ import math
 
 import numpy as np
 
+from . import _stages
 from .carrier import DEFAULT_SPAN, _check_window
 from .carrier_cpm import _check_spec, cpm_map_branch_host, hypothesis_table, period as grid_period
-from .timing import _split, hypothesis_instants, instants_host, lagrange_host, rescale_host, timing_refine_host, timing_track_host
+from .timing import _split, instants_host, lagrange_host
 
 DEFAULT_REFINE = 1
 # per waveform (by nh: 1 = PCM/FM, 2 = ARTM): hypotheses over one period of nh sps samples, the refinement's δ, the window
@@ -149,19 +150,9 @@ def llr_stat_host(llr, bits_per_call: int, window: int) -> np.ndarray:
     per = int(bits_per_call) * _check_window(window)
     if not 1 <= int(bits_per_call) <= 8 or lam.size == 0 or lam.size % int(bits_per_call):
         raise ValueError("llr must hold bits_per_call (1 .. 8) values for each of at least one call")
-    nwin = -(-lam.size // per)
-    a = np.zeros(nwin * per)
-    a[:lam.size] = lam                                       # (+0 beyond the burst: adding it changes nothing)
-    a = a.reshape(nwin, per // 64, 64)
-    p = np.zeros((nwin, 64))
-    for i in range(per // 64):
-        p = p + a[:, i, :]
-    d = 32
-    while d >= 1:
-        p[:, :d] = p[:, :d] + p[:, d:2 * d]
-        d //= 2
-    out = np.zeros((nwin, 2))
-    out[:, 0] = -p[:, 0]
+    total = _stages.window_sum(lam, per)
+    out = np.zeros((total.size, 2))
+    out[:, 0] = -total
     return out
 
 
@@ -196,10 +187,7 @@ def recover_cpm_timing_host(spec, received, templates, start0: int, sps: int, nc
         rows = cpm_mf_rows_resample_host(received, templates, start0, sps, ncalls, W, tau, tau0)[0]
         return llr_stat_host(soft(rows, rot), lg, W)
 
-    tau, choice = timing_track_host(np.stack([stat_at(None, s) for s in hypothesis_instants(per, H)]), per, span)
-    tau = rescale_host(tau, float(sps) * float(W))
-    for _ in range(int(refine)):
-        tau = tau + timing_refine_host(np.stack([stat_at(tau, d) for d in (-delta, 0.0, delta)]), delta, span)
+    tau, choice = _stages.timing_recover_host(stat_at, per, float(sps) * float(W), span, H, refine, delta)
     plain = stat_at(tau, 0.0)[:, 0].sum()
     turned = stat_at(tau, 0.0, hypothesis_table(spec, 0.5 * grid_period(spec)))[:, 0].sum()
     grid = 1 if turned < plain else 0
@@ -207,7 +195,7 @@ def recover_cpm_timing_host(spec, received, templates, start0: int, sps: int, nc
     return rows, tau, choice, grid
 
 
-class CPMTimingRecovery:
+class CPMTimingRecovery(_stages.Synchroniser):
     """Symbol timing recovery of a burst of noisy CPM samples at ``sps`` samples per symbol, everything on the device:
 
     1. ``hypotheses`` passes of ``cpm_mf_rows_resample`` at tau0 = s_h = h period / H - period / 2 -> ``cpm_soft`` ->
@@ -225,34 +213,17 @@ class CPMTimingRecovery:
 
     def __init__(self, spec, sps: int, window: int | None = None, span: int = DEFAULT_SPAN, hypotheses: int | None = None,
                  refine: int = DEFAULT_REFINE, delta: float | None = None) -> None:
+        super().__init__()
         _check_spec(spec)
         dflt = defaults(spec)
-        self.spec, self.sps = spec, int(sps)
+        self.spec = spec
         self.window = _check_window(dflt["window"] if window is None else window)
-        self.span, self.refine = int(span), int(refine)
-        self.hypotheses = int(dflt["hypotheses"] if hypotheses is None else hypotheses)
-        self.delta = float(dflt["delta"] if delta is None else delta)
-        if not 1 <= self.sps <= 256:
-            raise ValueError(f"sps = {sps} outside 1 .. 256")
-        if self.span < 1 or self.span % 2 == 0:
-            raise ValueError(f"span = {span} must be odd and at least 1")
-        if not 3 <= self.hypotheses <= 64:
-            raise ValueError(f"hypotheses = {hypotheses} outside 3 .. 64")
-        if self.refine < 0:
-            raise ValueError(f"refine = {refine} must not be negative")
-        if not (math.isfinite(self.delta) and self.delta > 0.0):
-            raise ValueError(f"delta = {delta} must be finite and positive")
-        self.times = False
-        self._events: list = []
+        self.sps = _stages.check_range("sps", sps, 1, 256)
+        self.span = _stages.check_span(span)
+        self.hypotheses = _stages.check_range("hypotheses", dflt["hypotheses"] if hypotheses is None else hypotheses, 3, 64)
+        self.refine = _stages.check_refine(refine)
+        self.delta = _stages.check_delta(dflt["delta"] if delta is None else delta)
         self._tables = None
-
-    def _mark(self, name: str) -> None:
-        if self.times:
-            from .. import _hip
-
-            ev = _hip.torch().cuda.Event(enable_timing=True)
-            ev.record()
-            self._events.append((name, ev))
 
     def recover(self, received, templates, start0: int, ncalls: int, ctx=None):
         """``received``: device float64[nsamp, 2]; ``templates``: device float64[nh, nfilt, ntm, 2] of ``spec`` ->
@@ -260,7 +231,7 @@ class CPMTimingRecovery:
         from .. import _hip
         from .. import device as dev
 
-        spec, H, W, ncalls = self.spec, self.hypotheses, self.window, int(ncalls)
+        spec, W, ncalls = self.spec, self.window, int(ncalls)
         lg, nwin = spec.bits_per_symbol, -(-ncalls // W)
         per = float(len(spec.K) * self.sps)
         half = 0.5 * grid_period(spec)
@@ -278,24 +249,7 @@ class CPMTimingRecovery:
             dev.llr_stat(llr, lg, W, out=out, ctx=ctx)
             self._mark("stat")
 
-        stat = _hip.empty((H, nwin, 2), "float64")
-        for h, s in enumerate(hypothesis_instants(per, H)):
-            stat_at(None, float(s), stat[h])
-        tau, choice = dev.timing_track(stat, per, self.span, ctx=ctx)
-        self._mark("track")
-        if nwin >= 2:                                            # rescale_host, operation for operation
-            a, b = (2, nwin - 3) if nwin >= 8 else (0, nwin - 1)
-            s = (tau[b] - tau[a]) / (float(b - a) * (float(self.sps) * float(W)))
-            tau = tau[0] + (tau - tau[0]) / (1.0 - s)
-        self._mark("rescale")
-        for _ in range(self.refine):
-            stat3 = _hip.empty((3, nwin, 2), "float64")
-            for j, d in enumerate((-self.delta, 0.0, self.delta)):
-                stat_at(tau, d, stat3[j])
-            more = dev.timing_refine(stat3, self.delta, self.span, ctx=ctx)
-            self._mark("track")
-            tau = tau + more
-            self._mark("add")
+        tau, choice = _stages.timing_recover(self, stat_at, per, nwin, ctx)
         both = _hip.empty((2, nwin, 2), "float64")
         for table in (0, 1):
             stat_at(tau, 0.0, both[table], table)
@@ -309,11 +263,3 @@ class CPMTimingRecovery:
         dev.cpm_mf_rows_resample(received, final, start0, self.sps, ncalls, W, tau, 0.0, out=work, ctx=ctx)
         self._mark("resample")
         return work, tau, choice, grid
-
-    def stage_times(self) -> dict[str, float]:
-        """Milliseconds per stage of the last ``recover`` (``times=True``), summed over its passes - synchronises."""
-        out: dict[str, float] = {}
-        for (_n0, e0), (name, e1) in zip(self._events, self._events[1:]):
-            e1.synchronize()
-            out[name] = out.get(name, 0.0) + e0.elapsed_time(e1)
-        return out
