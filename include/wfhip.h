@@ -1082,6 +1082,41 @@ int wf_timing_track(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, in
  * delta not finite or not positive, a NULL pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
 int wf_timing_refine(wf_ctx *ctx, const double *d_stat3, int64_t nwin, int span, double delta, double *d_more, void *stream);
 
+/* ---- The anchored unwrapping: both trackers without cycle slips (opt-in; the entry points above are untouched) --------------
+ * (waveforms_amd/sync/_stages.py restates it in numpy: anchored_unwrap.)  The running unwrap of wf_timing_track and
+ * wf_carrier_track follows every ψ_w: one window whose estimate errs by more than P/2 minus the drift leaves the trajectory a
+ * whole period off for the rest of the burst.  The anchored form smooths on the circle first and unwraps second.  With ψ_w
+ * (w < nwin) what the tracker forms before unwrapping, P its period, K = anchor (odd, 3 .. 1023), D = max_drift (ψ's unit per
+ * window, 0 <= D < P/2) and ρ = reject (0 < ρ <= P/2):
+ *   1. z_w = exp(j 2π frac(ψ_w / P))   (the quotient, t - floor(t), the product with 2π, then cos and sin); ψ_w not finite: z_w = 0
+ *   2. candidates f_i = i / (4K) cycles per window, |i| <= n = ceil(((double)(4K) * D) / P); segments of K windows starting at
+ *      s = 0, 2K, 4K, .. (the last may be short):
+ *        score_i = Σ_segments |Σ_{j < K} z_{s+j} exp(-j 2π ((i j) mod 4K) / (4K))|²
+ *      the inner sum with j increasing from +0, |.|² as re re + im im, the segments added in increasing order from +0;
+ *      f̂ = the first candidate of the largest score
+ *   3. y_w = z_w exp(-j 2π ((î w) mod 4K) / (4K))   (i j and î w are reduced as integers: no angle grows with the burst)
+ *      a_w = Σ y_j, j = max(0, w - K/2) .. min(nwin - 1, w + K/2) increasing, from +0 (K/2 rounded down);  α_w = atan2(Im a_w, Re a_w)
+ *      (a window with no finite ψ within K/2 of it has a_w = +0 and α_w = 0: it has no anchor, and comes back marked)
+ *      u = the running unwrap of α modulo 2π, exactly wf_carrier_track's u;   r_w = ((P / 2π) * u_w) + ((P * f̂) * (double)w)
+ *   4. d_w = wrap(ψ_w - r_w) modulo P;  ψ'_w = r_w + d_w;  if ψ_w is not finite or |d_w| > ρ: ψ'_w = r_w and d_marks[w] = 1 (else 0)
+ *   5. the output = the centred mean of ψ' over span windows, exactly as wf_carrier_track takes it;  d_drift[0] = P * f̂
+ * nwin = 1: the output is ψ_0 (0 if it is not finite), d_drift[0] = 0.  Two launches: the drift search runs as a grid over
+ * (segments, candidates) and writes per-segment scores, one workgroup adds them in segment order and does steps 3 to 5; z, ψ,
+ * α and the scores (4 nwin + ceil(nwin / 2K) (2n + 1) float64) pass through the context's detector scratch.  sincos and atan2 are
+ * the device library's and the complex products contract: the scores agree with the host statement to rounding, so f̂ and
+ * the marks equal the host's wherever the host's best score leads and no |d_w| sits at ρ, and the output then agrees to the
+ * rounding of its own magnitude (a few ulp of the largest |r_w|), as the plain entry point's.
+ * wf_timing_track_anchored: ψ_w of wf_timing_track (H, period as there);  wf_carrier_track_anchored: ψ_w of wf_carrier_track_mod
+ * (H, period as there; period = π is wf_carrier_track's).  d_drift: one float64; d_marks: nwin bytes.  anchor, max_drift or
+ * reject outside the ranges above, nwin > 2^31, a NULL pointer, or any argument the plain entry point refuses: WF_ERR_VALUE
+ * before the context is touched. */
+int wf_timing_track_anchored(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, int anchor,
+                             double max_drift, double reject, double *d_tau, uint8_t *d_choice, double *d_drift, uint8_t *d_marks,
+                             void *stream);
+int wf_carrier_track_anchored(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, int anchor,
+                              double max_drift, double reject, double *d_phase, uint8_t *d_choice, double *d_drift, uint8_t *d_marks,
+                              void *stream);
+
 /* ---- Joint carrier and timing acquisition for the SOQPSK-TG receiver: all carrier hypotheses of a pass in one set of launches --
  * (waveforms_amd/sync/joint.py composes the search from the stages above; these two entry points stack its hypotheses.)
  * wf_rows_derotate_hyp: H rotated copies of ncalls 48-byte rows, d_out[h][k], h < H, k < stride (H stride rows in all):

@@ -84,6 +84,10 @@ one acquisition of a burst of each ``--acq-time-rows`` length - device events ar
 (the existing entry points per hypothesis) against the default stacking, with the launch counts, the stage times and the
 time in units of one plain soft detection of as many rows.  The result is also written to ``--acq-out``
 (profiles/joint_acquisition.json).
+
+``--anchor K`` (with ``--recover-timing`` or ``--acquire``) adds an ``anchored`` link whose synchroniser has ``anchor=K`` (the
+anchored unwrapping of include/wfhip.h) beside the unanchored one on the same blocks: its curve, the windows its coarse tracks
+rejected per point, its loss, and with ``--acquire`` one more timed acquisition (``stack_default_anchored``).
 """
 import argparse
 import json
@@ -259,38 +263,49 @@ def main_timing(args) -> None:
         from waveforms_amd.viterbi import cpm as vc
 
         spec = vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
-        rec = CPMTimingRecovery(spec, sps, args.timing_window, args.timing_span, args.timing_hyp, args.timing_refine, args.timing_delta)
+        rec_args = (spec, sps, args.timing_window, args.timing_span, args.timing_hyp, args.timing_refine, args.timing_delta)
+        rec = CPMTimingRecovery(*rec_args)
         kw = dict(waveform=args.waveform, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
         links = {"genie": CodedCPMLink(code, per, **kw), "impaired": CodedCPMLink(code, per, clock=timing, **kw),
                  "recovered": CodedCPMLink(code, per, clock=timing, clock_recovery=rec, **kw)}
+        if args.anchor:
+            links["anchored"] = CodedCPMLink(code, per, clock=timing, clock_recovery=CPMTimingRecovery(*rec_args, anchor=args.anchor), **kw)
         limit = MAX_DRIFT_SAMPLES[args.waveform]
     else:
         from waveforms_amd.sync.timing import MAX_DRIFT_SAMPLES as limit, TimingRecovery
 
         kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
-        rec = TimingRecovery(sps, args.timing_window or 256, args.timing_span, args.timing_hyp or 8, args.timing_refine, args.timing_delta or 2.0)
+        rec_args = (sps, args.timing_window or 256, args.timing_span, args.timing_hyp or 8, args.timing_refine, args.timing_delta or 2.0)
+        rec = TimingRecovery(*rec_args)
         links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, timing=timing, **kw),
                  "recovered": CodedSOQPSKLink(code, per, timing=timing, timing_recovery=rec, **kw)}
+        if args.anchor:
+            links["anchored"] = CodedSOQPSKLink(code, per, timing=timing, timing_recovery=TimingRecovery(*rec_args, anchor=args.anchor), **kw)
     out = {"tool": "coded_ber", "form": "timing", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
            "detector": None if cpm else args.detector, "block_codewords": per,
            "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
            "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * sps * rec.window,
                       "documented_limit_samples_per_window": limit},
-           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine, "delta": rec.delta}, "points": []}
+           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine, "delta": rec.delta,
+                        "anchor": args.anchor}, "points": []}
     for e in args.ebn0:
         point = {"ebn0_info_db": e}
         b = 0
         for name, lk in links.items():
             lk.reset_counts()
-            b = 0
+            b, rejected = 0, 0
             while b * per < args.codewords:
                 lk.run_block(e, seed=1, stream_id=b)
+                if name == "anchored":
+                    rejected += (lk.clock_result() if cpm else lk.timing_result())[-1]
                 b += 1
             be, fe, nc, m, mean_it = lk.result()
-            ue, um = (None, None) if name == "recovered" else lk.uncoded_result()     # (a recovered link does not count channel bits)
+            ue, um = (None, None) if name in ("recovered", "anchored") else lk.uncoded_result()     # (a recovered link does not count channel bits)
             point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
                            "mean_iters": round(mean_it, 3), "uncoded_ber": None if um is None else ue / um, "wrong_locks": lk.sync_result()[1],
                            "last_lock": lk.sync_result()[2][0]}
+            if name == "anchored":
+                point[name]["rejected_windows"] = rejected
         point["codewords"] = b * per
         # the recovery's stages on one burst's noisy samples, each bracketed by device events, beside the fused front end
         # (channel + bank, what the genie link runs) and one plain soft detection of its rows
@@ -347,12 +362,16 @@ def main_timing(args) -> None:
     g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
     out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
     out["loss_db_at_fer_1e-2"] = None if g is None or r is None else round(r - g, 3)
+    if args.anchor:
+        a = _ebn0_at_fer(out["points"], "anchored")
+        out["ebn0_at_fer_1e-2"]["anchored"] = a
+        out["anchored_loss_db_at_fer_1e-2"] = None if g is None or a is None else round(a - g, 3)
     print(json.dumps(out))
 
 
 def _time_acquisition(lk, acq_kw, stacks, nrows, carrier, timing, ebn0, steps):
     """One acquisition of a burst of about ``nrows`` rows (PN bits, the links' own impairment and channel) per entry of
-    ``stacks``: device events around the whole call, ``steps`` calls after one warm-up, beside one plain soft detection of as
+    ``stacks`` (name -> (stack, anchor)): device events around the whole call, ``steps`` calls after one warm-up, beside one plain soft detection of as
     many rows -> {"rows", "soft_detector_ms", name: {"stack", "ms", "launches", "in_soft_detections", "stages_ms"}}."""
     import torch
 
@@ -380,8 +399,8 @@ def _time_acquisition(lk, acq_kw, stacks, nrows, carrier, timing, ebn0, steps):
     del plain
     n = max(steps, 1)
     out = {"rows": int(ncols), "soft_detector_ms": round(soft_ms / n, 4)}
-    for name, stack in stacks.items():
-        acq = JointAcquisition(sps, stack=stack, **acq_kw)
+    for name, (stack, anchor) in stacks.items():
+        acq = JointAcquisition(sps, stack=stack, anchor=anchor, **acq_kw)
         ms, stages = 0.0, {}
         for s in range(steps + 1):
             acq.times = False
@@ -427,6 +446,9 @@ def main_acquire(args) -> None:
         name = "acquired" if i == 0 else f"acquired_hc{hc}"
         acqs[name] = JointAcquisition(sps, carrier_hypotheses=hc, stack=args.acq_stack or None, **common)
         links[name] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=acqs[name], **kw)
+    if args.anchor:                                                       # the anchored curve beside the first acquired one, on the same blocks
+        acqs["anchored"] = JointAcquisition(sps, carrier_hypotheses=args.acq_carrier_hyp[0], stack=args.acq_stack or None, anchor=args.anchor, **common)
+        links["anchored"] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=acqs["anchored"], **kw)
     W = common["window"]
     out = {"tool": "coded_ber", "form": "acquire", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
            "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
@@ -434,19 +456,25 @@ def main_acquire(args) -> None:
                        "drift_turns_per_window": abs(args.carrier_freq) * sps * W, "documented_limit_turns_per_window": MAX_DRIFT_TURNS},
            "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * sps * W,
                       "documented_limit_samples_per_window": MAX_DRIFT_SAMPLES},
-           "acquisition": {**common, "carrier_hypotheses": args.acq_carrier_hyp, "stack": args.acq_stack or None, "stack_bytes": STACK_BYTES}, "points": []}
+           "acquisition": {**common, "carrier_hypotheses": args.acq_carrier_hyp, "stack": args.acq_stack or None, "stack_bytes": STACK_BYTES,
+                           "anchor": args.anchor}, "points": []}
     for e in args.ebn0:
         point = {"ebn0_info_db": e}
         b = 0
         for name, lk in links.items():
             lk.reset_counts()
-            b = 0
+            b, rejected = 0, [0, 0]
             while b * per < args.codewords:
                 lk.run_block(e, seed=1, stream_id=b)
+                if name == "anchored":
+                    found = lk.acquisition_result()[4:]
+                    rejected = [rejected[0] + found[1], rejected[1] + found[3]]
                 b += 1
             be, fe, nc, m, mean_it = lk.result()
             point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
                            "mean_iters": round(mean_it, 3), "wrong_locks": lk.sync_result()[1], "last_lock": lk.sync_result()[2][0]}
+            if name == "anchored":
+                point[name]["rejected_windows"] = {"timing": rejected[0], "carrier": rejected[1]}
         point["codewords"] = b * per
         out["points"].append(point)
     g = _ebn0_at_fer(out["points"], "genie")
@@ -458,7 +486,9 @@ def main_acquire(args) -> None:
         out["loss_db_at_fer_1e-2"][name] = None if g is None or r is None else round(r - g, 3)
     # one acquisition, unstacked (the existing entry points per hypothesis) and stacked, in units of one plain soft detection
     acq_kw = dict(common, carrier_hypotheses=args.acq_carrier_hyp[0])
-    stacks = {"stack_1": 1, "stack_default": args.acq_stack or None}
+    stacks = {"stack_1": (1, 0), "stack_default": (args.acq_stack or None, 0)}
+    if args.anchor:
+        stacks["stack_default_anchored"] = (args.acq_stack or None, args.anchor)
     out["one_acquisition"] = [_time_acquisition(links["acquired"], acq_kw, stacks, n, carrier, timing, args.ebn0[-1], args.steps) for n in args.acq_time_rows]
     text = json.dumps(out)
     if args.acq_out:
@@ -648,6 +678,8 @@ def main() -> None:
     ap.add_argument("--timing-span", type=int, default=5, help="--recover-timing: windows of the centred mean")
     ap.add_argument("--timing-refine", type=int, default=1, help="--recover-timing: refinement rounds")
     ap.add_argument("--timing-delta", type=float, default=None, help="--recover-timing: spacing of a refinement's three points, samples (default: 2.0; the class's for ARTM and PCM/FM)")
+    ap.add_argument("--anchor", type=int, default=0, help="--recover-timing / --acquire: K of the anchored unwrapping (odd, 3 .. 1023); adds the "
+                    "anchored curve beside the unanchored one on the same blocks (0: none)")
     ap.add_argument("--acquire", action="store_true", help="genie, impaired and acquired framed links on the same blocks under --carrier-* AND --timing-* (JointAcquisition)")
     ap.add_argument("--acq-timing-hyp", type=int, default=4, help="--acquire: timing hypotheses over one symbol")
     ap.add_argument("--acq-carrier-hyp", type=int, nargs="+", default=[8], help="--acquire: carrier hypotheses over [0, pi); further values add a curve each")

@@ -143,6 +143,8 @@ SIGNATURES = {
     "wf_mf_bank_resample_c128": (c_int, [_P, _P, c_int64, _P, c_int, c_int, c_int64, c_int, c_int64, c_int, _P, c_int64, c_double, _P, _P]),
     "wf_timing_track": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, _P, _P, _P]),
     "wf_timing_refine": (c_int, [_P, _P, c_int64, c_int, c_double, _P, _P]),
+    "wf_timing_track_anchored": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P]),
+    "wf_carrier_track_anchored": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P]),
     "wf_rows_derotate_hyp": (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
     "wf_viterbi4_soft_branch_segments": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
     "wf_cpm_mf_rows_resample_c128": (c_int, [_P, _P, c_int64, _P, c_int, c_int, c_int, c_int64, c_int, c_int64, c_int, _P, c_int64, c_double, _P, _P]),

@@ -116,6 +116,31 @@ __global__ __launch_bounds__(TRACK_THREADS) void carrier_track_kernel(const doub
     sync_centred_mean<TRACK_THREADS>(tmp, nwin, span, phase);
 }
 
+// The anchored track (wf_sync.h): the drift search over (segments, candidates), then the one workgroup behind it
+struct carrier_psi_of {
+    const double *stat;
+    int H;
+    int64_t nwin;
+    double period;
+    uint8_t *choice;
+    __device__ __forceinline__ double operator()(int64_t w, bool keep) const { return carrier_psi(stat, H, nwin, period, w, keep ? choice : nullptr); }
+};
+
+__global__ __launch_bounds__(ANCHOR_THREADS) void carrier_anchor_score_kernel(carrier_psi_of psi_of, int K, int n, double *psi, double2 *z, double *score)
+{
+    __shared__ double2 s_z[ANCHOR_MAX_K];
+    sync_anchor_score<ANCHOR_THREADS>(psi_of, psi_of.nwin, psi_of.period, K, n, psi, z, score, s_z);
+}
+
+__global__ __launch_bounds__(TRACK_THREADS) void carrier_anchor_tail_kernel(int64_t nwin, int span, double period, double reject, int K, int n, int64_t nseg,
+                                                                            double *psi, double2 *z, double *alpha, const double *score,
+                                                                            double *__restrict__ phase, double *__restrict__ drift, uint8_t *__restrict__ marks)
+{
+    __shared__ double s_seg[TRACK_THREADS];
+    __shared__ int s_idx[TRACK_THREADS];
+    sync_anchor_tail<TRACK_THREADS>(nwin, span, period, reject, K, n, nseg, psi, z, alpha, score, phase, drift, marks, s_seg, s_idx);
+}
+
 __global__ __launch_bounds__(CARRIER_THREADS) void rows_derotate_kernel(const double2 *rows, int64_t n, int nvals, int W, const double *__restrict__ phase,
                                                                         int64_t nwin, double phase0, double2 *out)
 {
@@ -198,6 +223,20 @@ extern "C" int wf_carrier_track_mod(wf_ctx *ctx, const double *d_stat_h, int H, 
                                     void *stream)
 {
     return carrier_track_run("wf_carrier_track_mod", ctx, d_stat_h, H, nwin, span, period, d_phase, d_choice, stream);
+}
+
+extern "C" int wf_carrier_track_anchored(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, int anchor, double max_drift,
+                                         double reject, double *d_phase, uint8_t *d_choice, double *d_drift, uint8_t *d_marks, void *stream)
+{
+    const char *who = "wf_carrier_track_anchored";
+    WF_REQUIRE(ctx && d_stat_h && d_phase && d_choice && d_drift && d_marks, "%s: NULL argument", who);
+    WF_REQUIRE(H >= 1 && H <= 256, "%s: H must be 1 .. 256", who);
+    WF_REQUIRE(nwin >= 1, "%s: nwin must be at least 1", who);
+    WF_REQUIRE(span >= 1 && span % 2 == 1, "%s: span must be odd and at least 1", who);
+    WF_REQUIRE(std::isfinite(period) && period > 0.0 && period <= kCarrierTwoPi, "%s: period must be in (0, 2 pi]", who);
+    WF_REQUIRE(!sync_mis(d_stat_h, 7) && !sync_mis(d_phase, 7) && !sync_mis(d_drift, 7), "%s: stat, phase and drift must be 8-byte aligned", who);
+    return sync_anchor_run(who, ctx, carrier_anchor_score_kernel, carrier_anchor_tail_kernel, TRACK_THREADS, carrier_psi_of{d_stat_h, H, nwin, period, d_choice}, nwin, span, period,
+                           anchor, max_drift, reject, d_phase, d_drift, d_marks, stream);
 }
 
 static int rows_derotate_run(const char *who, wf_ctx *ctx, const double *d_rows, int64_t ncalls, int nvals, int W, const double *d_phase, int64_t nwin,

@@ -1,5 +1,6 @@
 // wf_timing.hip — symbol timing: the impairment (wf_timing_offset_c128), the resampling matched-filter bank
-// (wf_mf_bank_resample_c128) and the two trajectory stages of the feed-forward recovery (wf_timing_track, wf_timing_refine).
+// (wf_mf_bank_resample_c128) and the trajectory stages of the feed-forward recovery (wf_timing_track, wf_timing_track_anchored,
+// wf_timing_refine).
 // include/wfhip.h states every definition; waveforms_amd/sync/timing.py restates them in numpy.  The reference has no
 // synchroniser: these are the build's own.  The statistic the trajectory stages read is wf_carrier_stat's X (wf_carrier.hip).
 //
@@ -20,6 +21,8 @@
 //                           guarded parabola vertex, or the vertex of a refinement's three points —, for the track the
 //                           unwrapping modulo the period as a blocked scan, then the centred mean: the argmin, the scan and the
 //                           mean are wf_sync.h's, shared with carrier_track_kernel.
+//   timing_anchor_score_kernel / timing_anchor_tail_kernel   the track with wf_sync.h's anchored unwrapping: a grid over the
+//                           drift search's segments (a thread per candidate), then ONE workgroup for the rest.
 //
 // The instants' arithmetic is written one operation per statement where the host statement must see the same roundings
 // (-ffp-contract=on fuses within an expression only).
@@ -232,6 +235,23 @@ __device__ __forceinline__ double timing_vertex(double a, double b, double c, do
     return v > lim ? lim : (v < -lim ? -lim : v);
 }
 
+// ψ_w of H hypotheses a period / H apart: the best one's instant moved by its guarded vertex; choice (or null): the best one
+__device__ __forceinline__ double timing_psi(const double *__restrict__ stat, int H, int64_t nwin, double period, int64_t w, uint8_t *__restrict__ choice)
+{
+    double bx;
+    const int best = sync_argmin(stat, H, nwin, w, &bx);
+    if (choice) choice[w] = (uint8_t)best;
+    const double a = stat[2 * ((int64_t)(best == 0 ? H - 1 : best - 1) * nwin + w)];
+    const double c = stat[2 * ((int64_t)(best == H - 1 ? 0 : best + 1) * nwin + w)];
+    const double v = timing_vertex(a, bx, c, 0.5);
+    const double dh = period / (double)H;
+    const double ih = (double)best * dh;
+    const double hp = 0.5 * period;
+    const double s = ih - hp;
+    const double sv = dh * v;
+    return s + sv;
+}
+
 // TRACK: ψ_w of H hypotheses, unwrapped modulo the period; otherwise scale * V of the three points of a refinement.  Then the mean.
 template <bool TRACK>
 __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const double *__restrict__ stat, int H, int64_t nwin, int span, double scale, double *tmp,
@@ -240,18 +260,7 @@ __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const doub
     __shared__ double s_seg[TTRACK_THREADS];
     for (int64_t w = threadIdx.x; w < nwin; w += TTRACK_THREADS) {
         if (TRACK) {
-            double bx;
-            const int best = sync_argmin(stat, H, nwin, w, &bx);
-            choice[w] = (uint8_t)best;
-            const double a = stat[2 * ((int64_t)(best == 0 ? H - 1 : best - 1) * nwin + w)];
-            const double c = stat[2 * ((int64_t)(best == H - 1 ? 0 : best + 1) * nwin + w)];
-            const double v = timing_vertex(a, bx, c, 0.5);
-            const double dh = scale / (double)H;                // scale: the period
-            const double ih = (double)best * dh;
-            const double hp = 0.5 * scale;
-            const double s = ih - hp;
-            const double sv = dh * v;
-            tmp[w] = s + sv;
+            tmp[w] = timing_psi(stat, H, nwin, scale, w, choice);      // scale: the period
         } else {
             const double v = timing_vertex(stat[2 * w], stat[2 * (nwin + w)], stat[2 * (2 * nwin + w)], 1.0);
             tmp[w] = scale * v;                                 // scale: δ
@@ -260,6 +269,31 @@ __global__ __launch_bounds__(TTRACK_THREADS) void timing_track_kernel(const doub
     __syncthreads();
     if (TRACK) sync_unwrap_scan<TTRACK_THREADS>(tmp, nwin, scale, s_seg);
     sync_centred_mean<TTRACK_THREADS>(tmp, nwin, span, tau);
+}
+
+// The anchored track (wf_sync.h): the drift search over (segments, candidates), then the one workgroup behind it
+struct timing_psi_of {
+    const double *stat;
+    int H;
+    int64_t nwin;
+    double period;
+    uint8_t *choice;
+    __device__ __forceinline__ double operator()(int64_t w, bool keep) const { return timing_psi(stat, H, nwin, period, w, keep ? choice : nullptr); }
+};
+
+__global__ __launch_bounds__(ANCHOR_THREADS) void timing_anchor_score_kernel(timing_psi_of psi_of, int K, int n, double *psi, double2 *z, double *score)
+{
+    __shared__ double2 s_z[ANCHOR_MAX_K];
+    sync_anchor_score<ANCHOR_THREADS>(psi_of, psi_of.nwin, psi_of.period, K, n, psi, z, score, s_z);
+}
+
+__global__ __launch_bounds__(TTRACK_THREADS) void timing_anchor_tail_kernel(int64_t nwin, int span, double period, double reject, int K, int n, int64_t nseg,
+                                                                            double *psi, double2 *z, double *alpha, const double *score,
+                                                                            double *__restrict__ tau, double *__restrict__ drift, uint8_t *__restrict__ marks)
+{
+    __shared__ double s_seg[TTRACK_THREADS];
+    __shared__ int s_idx[TTRACK_THREADS];
+    sync_anchor_tail<TTRACK_THREADS>(nwin, span, period, reject, K, n, nseg, psi, z, alpha, score, tau, drift, marks, s_seg, s_idx);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -348,6 +382,20 @@ extern "C" int wf_timing_track(wf_ctx *ctx, const double *d_stat_h, int H, int64
                        d_choice);
     WF_LAUNCH_CHECK();
     return WF_OK;
+}
+
+extern "C" int wf_timing_track_anchored(wf_ctx *ctx, const double *d_stat_h, int H, int64_t nwin, int span, double period, int anchor, double max_drift,
+                                        double reject, double *d_tau, uint8_t *d_choice, double *d_drift, uint8_t *d_marks, void *stream)
+{
+    const char *who = "wf_timing_track_anchored";
+    WF_REQUIRE(ctx && d_stat_h && d_tau && d_choice && d_drift && d_marks, "%s: NULL argument", who);
+    WF_REQUIRE(H >= 3 && H <= 64, "%s: H must be 3 .. 64", who);
+    WF_REQUIRE(nwin >= 1, "%s: nwin must be at least 1", who);
+    WF_REQUIRE(span >= 1 && span % 2 == 1, "%s: span must be odd and at least 1", who);
+    WF_REQUIRE(std::isfinite(period) && period > 0.0, "%s: period must be finite and positive", who);
+    WF_REQUIRE(!sync_mis(d_stat_h, 7) && !sync_mis(d_tau, 7) && !sync_mis(d_drift, 7), "%s: stat, tau and drift must be 8-byte aligned", who);
+    return sync_anchor_run(who, ctx, timing_anchor_score_kernel, timing_anchor_tail_kernel, TTRACK_THREADS, timing_psi_of{d_stat_h, H, nwin, period, d_choice}, nwin, span, period,
+                           anchor, max_drift, reject, d_tau, d_drift, d_marks, stream);
 }
 
 extern "C" int wf_timing_refine(wf_ctx *ctx, const double *d_stat3, int64_t nwin, int span, double delta, double *d_more, void *stream)

@@ -318,13 +318,35 @@ def carrier_stat(rows, branch, window: int, out=None, ctx=None):
     return out
 
 
-def carrier_track(stat, span: int = 1, ctx=None, period=None):
+def _track_anchored(c_fn: str, stat, H: int, nwin: int, span: int, period: float, K: int, D: float, rho: float, ctx):
+    """``wf_timing_track_anchored`` / ``wf_carrier_track_anchored`` -> (trajectory f64[nwin], choice u8[nwin], drift f64[1],
+    marks u8[nwin]), all on the device."""
+    traj = _hip.empty(max(nwin, 1), "float64")
+    choice = _hip.empty(max(nwin, 1) + 16, "uint8")
+    drift = _hip.empty(1, "float64")
+    marks = _hip.empty(max(nwin, 1) + 16, "uint8")
+    _hip.check(getattr(_hip.lib(), c_fn)(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), float(period), K, D, rho, _hip.ptr(traj), _hip.ptr(choice),
+                                         _hip.ptr(drift), _hip.ptr(marks), _hip.stream()))
+    return traj[:nwin], choice[:nwin], drift, marks[:nwin]
+
+
+def carrier_track(stat, span: int = 1, ctx=None, period=None, anchor: int = 0, max_drift=None, reject=None):
     """Statistics of H hypothesis passes -> (phase f64[nwin], choice u8[nwin]) on device (``wf_carrier_track``; include/wfhip.h
     states the definition).  ``stat``: contiguous device float64[H, nwin, 2], pass h over rows derotated by h π / H.
-    ``period``: the symmetry of the trellis in radians in place of π (``wf_carrier_track_mod``: 2π/p for the CPM detectors)."""
+    ``period``: the symmetry of the trellis in radians in place of π (``wf_carrier_track_mod``: 2π/p for the CPM detectors).
+    ``anchor`` = K > 0 (odd, 3 .. 1023): the anchored unwrapping (``wf_carrier_track_anchored``) -> (phase, choice, the drift
+    found in radians per window: device f64[1], the rejected windows: device u8[nwin]); ``max_drift`` in radians per window
+    (None: 1.25 * 2π ``sync.carrier.MAX_DRIFT_TURNS``), ``reject`` in radians (None: period / 4)."""
     if stat.dtype != _hip.torch().float64 or not stat.is_contiguous() or stat.dim() != 3 or stat.shape[2] != 2:
         raise ValueError("stat must be contiguous float64[H, nwin, 2]")
     H, nwin = int(stat.shape[0]), int(stat.shape[1])
+    if int(anchor):
+        from .sync import _stages
+        from .sync.carrier import MAX_DRIFT_TURNS
+
+        P = math.pi if period is None else float(period)
+        K, D, rho = _stages.anchor_args(anchor, max_drift, reject, P, 2.0 * math.pi * MAX_DRIFT_TURNS)
+        return _track_anchored("wf_carrier_track_anchored", stat, H, nwin, span, P, K, D, rho, ctx)
     phase = _hip.empty(max(nwin, 1), "float64")
     choice = _hip.empty(max(nwin, 1) + 16, "uint8")
     if period is None:
@@ -463,13 +485,22 @@ def mf_bank_resample(received, taps, first: int, step: int, ncols: int, window: 
     return out
 
 
-def timing_track(stat, period: float, span: int = 1, ctx=None):
+def timing_track(stat, period: float, span: int = 1, ctx=None, anchor: int = 0, max_drift=None, reject=None):
     """Statistics of H timing hypotheses -> (tau f64[nwin] in samples, choice u8[nwin]) on device (``wf_timing_track``;
     include/wfhip.h states the definition).  ``stat``: contiguous device float64[H, nwin, 2] as ``carrier_stat`` writes it, pass
-    h taken at the instant -period/2 + h period/H; only X is read."""
+    h taken at the instant -period/2 + h period/H; only X is read.  ``anchor`` = K > 0 (odd, 3 .. 1023): the anchored unwrapping
+    (``wf_timing_track_anchored``) -> (tau, choice, the drift found in samples per window: device f64[1], the rejected windows:
+    device u8[nwin]); ``max_drift`` in samples per window (None: 1.25 ``sync.timing.MAX_DRIFT_SAMPLES``), ``reject`` in samples
+    (None: period / 4)."""
     if stat.dtype != _hip.torch().float64 or not stat.is_contiguous() or stat.dim() != 3 or stat.shape[2] != 2:
         raise ValueError("stat must be contiguous float64[H, nwin, 2]")
     H, nwin = int(stat.shape[0]), int(stat.shape[1])
+    if int(anchor):
+        from .sync import _stages
+        from .sync.timing import MAX_DRIFT_SAMPLES
+
+        K, D, rho = _stages.anchor_args(anchor, max_drift, reject, float(period), MAX_DRIFT_SAMPLES)
+        return _track_anchored("wf_timing_track_anchored", stat, H, nwin, span, float(period), K, D, rho, ctx)
     tau = _hip.empty(max(nwin, 1), "float64")
     choice = _hip.empty(max(nwin, 1) + 16, "uint8")
     _hip.check(_hip.lib().wf_timing_track(_ctx(ctx), _hip.ptr(stat), H, nwin, int(span), float(period), _hip.ptr(tau), _hip.ptr(choice),

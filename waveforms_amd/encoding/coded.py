@@ -108,12 +108,19 @@ class _Framed:
         self.carrier, self.recovery = carrier, recovery
         self._carrier_phase = self._carrier_choice = None
 
+    @staticmethod
+    def _found(*found):
+        """What the anchored coarse tracks of a synchroniser's last ``recover`` found, for the ``*_result`` methods: per track
+        (the drift in the tracker's unit per window, the number of rejected windows); nothing without an anchor."""
+        return tuple(v for f in found if f is not None for v in (float(f[0].cpu()), int(f[1].sum().cpu())))
+
     def carrier_result(self):
         """(phase float64[nwin] in radians, modulo π - modulo 2π/p on the CPM links; choice uint8[nwin]) of the last block's
-        recovery - synchronises."""
+        recovery - synchronises.  A recovery with an ``anchor`` adds (the drift found in radians per window, the number of
+        rejected windows) of its coarse track."""
         if self.recovery is None or self._carrier_phase is None:
             raise RuntimeError("carrier_result needs a recovery and a block that ran")
-        return _hip.to_host(self._carrier_phase), _hip.to_host(self._carrier_choice)
+        return (_hip.to_host(self._carrier_phase), _hip.to_host(self._carrier_choice)) + self._found(self.recovery.carrier_found)
 
     def _recovered(self, rows):
         if self.recovery is None:
@@ -147,10 +154,11 @@ class _Framed:
 
     def timing_result(self):
         """(tau float64[nwin] in samples, modulo two symbols; choice uint8[nwin]) of the last block's timing recovery -
-        synchronises."""
+        synchronises.  A recovery with an ``anchor`` adds (the drift found in samples per window, the number of rejected windows)
+        of its coarse track."""
         if self.timing_recovery is None or self._timing_tau is None:
             raise RuntimeError("timing_result needs a timing_recovery and a block that ran")
-        return _hip.to_host(self._timing_tau), _hip.to_host(self._timing_choice)
+        return (_hip.to_host(self._timing_tau), _hip.to_host(self._timing_choice)) + self._found(self.timing_recovery.timing_found)
 
     def _acquisition_init(self, acquisition, sps: int, framing, recovery, timing_recovery) -> None:
         """``acquisition``: a ``waveforms_amd.sync.joint.JointAcquisition`` that makes the detector's rows from the noisy samples
@@ -173,10 +181,12 @@ class _Framed:
 
     def acquisition_result(self):
         """(tau float64[nwin] in samples, phase float64[nwin] in radians - both modulo the lattice of waveforms_amd/sync/joint.py;
-        timing choice uint8[nwin]; carrier choice uint8[nwin]) of the last block's acquisition - synchronises."""
+        timing choice uint8[nwin]; carrier choice uint8[nwin]) of the last block's acquisition - synchronises.  An acquisition with
+        an ``anchor`` adds (the timing drift found in samples per window, the rejected windows of the coarse timing track, the carrier
+        drift found in radians per window, the rejected windows of the coarse carrier track)."""
         if self.acquisition is None or self._acq is None:
             raise RuntimeError("acquisition_result needs an acquisition and a block that ran")
-        return tuple(_hip.to_host(v) for v in self._acq)
+        return tuple(_hip.to_host(v) for v in self._acq) + self._found(self.acquisition.timing_found, self.acquisition.carrier_found)
 
     def _clock_init(self, clock, clock_recovery, spec, sps: int, framing, carrier, recovery) -> None:
         """``clock=(tau0, eps)`` and ``clock_recovery`` of the CPM links: ``_timing_init``'s pair for the generic CPM trellis, with
@@ -204,10 +214,11 @@ class _Framed:
 
     def clock_result(self):
         """(tau float64[nwin] in samples, modulo nh symbols; choice uint8[nwin]; grid 0 / 1) of the last block's clock recovery -
-        synchronises."""
+        synchronises.  A recovery with an ``anchor`` adds (the drift found in samples per window, the number of rejected windows)
+        of its coarse track."""
         if self.clock_recovery is None or self._clock_tau is None:
             raise RuntimeError("clock_result needs a clock_recovery and a block that ran")
-        return _hip.to_host(self._clock_tau), _hip.to_host(self._clock_choice), int(self._clock_grid.cpu())
+        return (_hip.to_host(self._clock_tau), _hip.to_host(self._clock_choice), int(self._clock_grid.cpu())) + self._found(self.clock_recovery.timing_found)
 
     def _rate_db(self) -> float:
         """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""

@@ -156,9 +156,8 @@ def _wrap_pi(x):
     return _wrap(x, math.pi)
 
 
-def carrier_track_host(stat, span: int = DEFAULT_SPAN, period: float = math.pi):
-    """``wf_carrier_track``: float64[H, nwin, 2] -> (phase f64[nwin], choice u8[nwin]).  ``period``: the symmetry of the
-    trellis in place of π (``wf_carrier_track_mod``)."""
+def carrier_psi_host(stat, period: float = math.pi):
+    """What ``wf_carrier_track`` forms per window before it unwraps: float64[H, nwin, 2] -> (ψ f64[nwin], choice u8[nwin])."""
     period = float(period)
     if not (math.isfinite(period) and 0.0 < period <= 2.0 * math.pi):
         raise ValueError(f"period = {period} outside (0, 2π]")
@@ -166,12 +165,25 @@ def carrier_track_host(stat, span: int = DEFAULT_SPAN, period: float = math.pi):
     if stat.ndim == 2:
         stat = stat[None]
     H, nwin = stat.shape[0], stat.shape[1]
-    span = _stages.check_span(span)
     choice = np.argmin(stat[:, :, 0], axis=0)              # the first of equal minima
     w = np.arange(nwin)
     bx, by = stat[choice, w, 0], stat[choice, w, 1]
-    psi = (choice.astype(np.float64) * period) / float(H) + np.arctan2(-by, -bx)
-    return _stages.centred_mean(_stages.unwrap(psi, period), span), choice.astype(np.uint8)
+    return (choice.astype(np.float64) * period) / float(H) + np.arctan2(-by, -bx), choice.astype(np.uint8)
+
+
+def carrier_track_host(stat, span: int = DEFAULT_SPAN, period: float = math.pi, anchor: int = 0, max_drift=None, reject=None):
+    """``wf_carrier_track``: float64[H, nwin, 2] -> (phase f64[nwin], choice u8[nwin]).  ``period``: the symmetry of the
+    trellis in place of π (``wf_carrier_track_mod``).  ``anchor`` = K > 0: ``wf_carrier_track_anchored``, the anchored unwrapping
+    of ``_stages.anchored_unwrap`` in place of the running one -> (phase, choice, the drift found in radians per window, the
+    rejected windows u8[nwin]); ``max_drift`` in radians per window (None: 1.25 * 2π ``MAX_DRIFT_TURNS``), ``reject`` in radians
+    (None: period / 4)."""
+    psi, choice = carrier_psi_host(stat, period)
+    period, span = float(period), _stages.check_span(span)
+    K, D, rho = _stages.anchor_args(anchor, max_drift, reject, period, 2.0 * math.pi * MAX_DRIFT_TURNS)
+    if K:
+        kept, drift, marks = _stages.anchored_unwrap(psi, period, K, D, rho)
+        return _stages.centred_mean(kept, span), choice, drift, marks
+    return _stages.centred_mean(_stages.unwrap(psi, period), span), choice
 
 
 def interpolate_phase_host(ncalls: int, window: int, phase) -> np.ndarray:
@@ -227,11 +239,17 @@ class CarrierRecovery(_stages.Synchroniser):
        and the input rows are derotated by the sum.
 
     ``recover`` returns the derotated rows, the trajectory (radians per window, modulo π) and the coarse choices; nothing
-    comes back to the host.  ``times=True`` keeps device events around every stage of the last call (``stage_times``)."""
+    comes back to the host.  ``times=True`` keeps device events around every stage of the last call (``stage_times``).
+
+    ``anchor`` = K > 0 (odd, 3 .. 1023): the tracks use the anchored unwrapping of include/wfhip.h in place of the running one -
+    no cycle slips behind a bad window; ``max_drift`` and ``reject`` in radians (per window) (None: 1.25 times the documented drift limit and a
+    quarter of the period).  The last ``recover``'s coarse track leaves the drift found and the rejected windows on the device in
+    ``carrier_found``."""
 
     def __init__(self, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
-                 refine: int = DEFAULT_REFINE) -> None:
+                 refine: int = DEFAULT_REFINE, anchor: int = 0, max_drift=None, reject=None) -> None:
         super().__init__()
+        self._anchor_init("carrier", anchor, max_drift, reject, math.pi, 2.0 * math.pi * MAX_DRIFT_TURNS)
         self.window = _check_window(window)
         self.span = _stages.check_span(span)
         self.hypotheses = _stages.check_range("hypotheses", hypotheses, 1, 256)

@@ -196,12 +196,18 @@ class CPMCarrierRecovery(_stages.Synchroniser):
 
     ``recover`` returns the derotated rows, the trajectory (radians per window, modulo P = 2π / p) and the coarse choices;
     nothing comes back to the host.  ``times=True`` keeps device events around every stage of the last call (``stage_times``).
-    ``spec``: a full-phase design with at most 64 states (``viterbi.cpm.full_phase``: ARTM_64, PCMFM_20)."""
+    ``spec``: a full-phase design with at most 64 states (``viterbi.cpm.full_phase``: ARTM_64, PCMFM_20).
+
+    ``anchor`` = K > 0 (odd, 3 .. 1023): the tracks use the anchored unwrapping of include/wfhip.h in place of the running one -
+    no cycle slips behind a bad window; ``max_drift`` and ``reject`` in radians (per window) (None: 1.25 times the documented drift limit and a
+    quarter of the period).  The last ``recover``'s coarse track leaves the drift found and the rejected windows on the device in
+    ``carrier_found``."""
 
     def __init__(self, spec, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
-                 refine: int = DEFAULT_REFINE) -> None:
+                 refine: int = DEFAULT_REFINE, anchor: int = 0, max_drift=None, reject=None) -> None:
         super().__init__()
         _check_spec(spec)
+        self._anchor_init("carrier", anchor, max_drift, reject, period(spec), MAX_DRIFT_PERIODS * period(spec))
         self.spec = spec
         self.window = _check_window(window)
         self.span = _stages.check_span(span)

@@ -147,8 +147,9 @@ def hypothesis_instants(period: float, H: int) -> np.ndarray:
     return np.arange(int(H), dtype=np.float64) * dh - 0.5 * float(period)
 
 
-def timing_track_host(stat, period: float, span: int = 1):
-    """``wf_timing_track``: float64[H, nwin, 2] -> (tau f64[nwin] in samples, choice u8[nwin])."""
+def timing_psi_host(stat, period: float):
+    """What ``wf_timing_track`` forms per window before it unwraps: float64[H, nwin, 2] -> (ψ f64[nwin] in [-period/2, period/2),
+    choice u8[nwin])."""
     period = float(period)
     if not (math.isfinite(period) and period > 0.0):
         raise ValueError(f"period = {period} must be finite and positive")
@@ -160,8 +161,21 @@ def timing_track_host(stat, period: float, span: int = 1):
     w = np.arange(nwin)
     v = vertex_host(X[(choice - 1) % H, w], X[choice, w], X[(choice + 1) % H, w], 0.5)
     dh = period / float(H)
-    psi = (choice.astype(np.float64) * dh - 0.5 * period) + dh * v
-    return _centred_mean(_stages.unwrap(psi, period), span), choice.astype(np.uint8)
+    return (choice.astype(np.float64) * dh - 0.5 * period) + dh * v, choice.astype(np.uint8)
+
+
+def timing_track_host(stat, period: float, span: int = 1, anchor: int = 0, max_drift=None, reject=None):
+    """``wf_timing_track``: float64[H, nwin, 2] -> (tau f64[nwin] in samples, choice u8[nwin]).  ``anchor`` = K > 0:
+    ``wf_timing_track_anchored``, the anchored unwrapping of ``_stages.anchored_unwrap`` in place of the running one ->
+    (tau, choice, the drift found in samples per window, the rejected windows u8[nwin]); ``max_drift`` in samples per window
+    (None: 1.25 ``MAX_DRIFT_SAMPLES``), ``reject`` in samples (None: period / 4)."""
+    psi, choice = timing_psi_host(stat, period)
+    period = float(period)
+    K, D, rho = _stages.anchor_args(anchor, max_drift, reject, period, MAX_DRIFT_SAMPLES)
+    if K:
+        kept, drift, marks = _stages.anchored_unwrap(psi, period, K, D, rho)
+        return _centred_mean(kept, span), choice, drift, marks
+    return _centred_mean(_stages.unwrap(psi, period), span), choice
 
 
 def rescale_host(tau, samples_per_window: float) -> np.ndarray:
@@ -207,11 +221,17 @@ class TimingRecovery(_stages.Synchroniser):
     4. ``mf_bank_resample`` along τ: the rows the detector gets.
 
     ``recover`` returns those rows, the trajectory (samples per window, modulo two symbols) and the coarse choices; nothing
-    comes back to the host.  ``times=True`` keeps device events around every stage of the last call (``stage_times``)."""
+    comes back to the host.  ``times=True`` keeps device events around every stage of the last call (``stage_times``).
+
+    ``anchor`` = K > 0 (odd, 3 .. 1023): the tracks use the anchored unwrapping of include/wfhip.h in place of the running one -
+    no cycle slips behind a bad window; ``max_drift`` and ``reject`` in samples (per window) (None: 1.25 times the documented drift limit and a
+    quarter of the period).  The last ``recover``'s coarse track leaves the drift found and the rejected windows on the device in
+    ``timing_found``."""
 
     def __init__(self, sps: int, window: int = DEFAULT_WINDOW, span: int = DEFAULT_SPAN, hypotheses: int = DEFAULT_HYPOTHESES,
-                 refine: int = DEFAULT_REFINE, delta: float = DEFAULT_DELTA) -> None:
+                 refine: int = DEFAULT_REFINE, delta: float = DEFAULT_DELTA, anchor: int = 0, max_drift=None, reject=None) -> None:
         super().__init__()
+        self._anchor_init("timing", anchor, max_drift, reject, 2.0 * float(sps), MAX_DRIFT_SAMPLES)
         self.window = _check_window(window)
         self.sps = _stages.check_range("sps", sps, 1, 64)
         self.span = _stages.check_span(span)

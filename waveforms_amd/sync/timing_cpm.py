@@ -209,12 +209,18 @@ class CPMTimingRecovery(_stages.Synchroniser):
     ``recover`` returns those rows, the trajectory (samples per window, modulo nh symbols), the coarse choices and the grid
     (a device int64 scalar tensor); nothing comes back to the host.  ``times=True`` keeps device events around every stage of the
     last call (``stage_times``).  ``spec``: a full-phase design with at most 64 states (``viterbi.cpm.full_phase``: ARTM_64,
-    PCMFM_20); ``window``, ``hypotheses`` and ``delta`` default per waveform (``defaults``)."""
+    PCMFM_20); ``window``, ``hypotheses`` and ``delta`` default per waveform (``defaults``).
+
+    ``anchor`` = K > 0 (odd, 3 .. 1023): the tracks use the anchored unwrapping of include/wfhip.h in place of the running one -
+    no cycle slips behind a bad window; ``max_drift`` and ``reject`` in samples (per window) (None: 1.25 times the documented drift limit and a
+    quarter of the period).  The last ``recover``'s coarse track leaves the drift found and the rejected windows on the device in
+    ``timing_found``."""
 
     def __init__(self, spec, sps: int, window: int | None = None, span: int = DEFAULT_SPAN, hypotheses: int | None = None,
-                 refine: int = DEFAULT_REFINE, delta: float | None = None) -> None:
+                 refine: int = DEFAULT_REFINE, delta: float | None = None, anchor: int = 0, max_drift=None, reject=None) -> None:
         super().__init__()
         _check_spec(spec)
+        self._anchor_init("timing", anchor, max_drift, reject, float(len(spec.K) * int(sps)), MAX_DRIFT_SAMPLES["multih" if len(spec.K) == 2 else "pcmfm"])
         dflt = defaults(spec)
         self.spec = spec
         self.window = _check_window(dflt["window"] if window is None else window)
