@@ -1180,6 +1180,36 @@ int wf_cpm_mf_rows_resample_geometry(int nh, int nfilt, int ntm, int sps, int64_
  * pointer, a pointer not 8-byte aligned: WF_ERR_VALUE before the context is touched. */
 int wf_llr_stat(wf_ctx *ctx, const double *d_llr, int64_t ncalls, int bits_per_call, int W, double *d_stat, void *stream);
 
+/* ---- Joint carrier and timing acquisition for the generic CPM chains: the hypotheses of a pass in one set of launches -------
+ * (waveforms_amd/sync/joint_cpm.py composes the search from the stages above; this entry point stacks its detections.)
+ * wf_cpm_soft_branch over nseg INDEPENDENT segments in ONE set of launches (bounds, per direction one verify and three repair
+ * rounds, last).  Segment s < nseg is a burst of its own: seglen calls whose call indices start at first_call, from a free
+ * start to a free end;
+ *   its rows:    d_rows_ri + s row_stride rows (M^Lp complex128 each); row_stride = 0: every segment reads the same rows
+ *   its table:   d_rot_cs + s rot_stride tables of 2p (cos, sin) pairs; rot_stride is 0 or 1
+ *   its outputs: at call offset s out_stride - λ and bits lgM values per call, the branch one byte per call, the term two
+ *                float64 per call (d_term NULL: not written); the outputs of the calls s out_stride + seglen ..
+ *                (s + 1) out_stride - 1 are written as +0 / 0, so that wf_llr_stat and wf_carrier_stat_terms over all
+ *                nseg out_stride calls with a W that divides out_stride give the nseg separate tables.
+ * Every output of segment s is BITWISE what wf_cpm_soft_branch writes for those rows, that table and that first_call alone,
+ * whatever the warm-up and the chunk length: no chunk crosses a segment, no warm-up leaves one, a segment's first and last chunk
+ * start exactly as a burst's do, the proof chain of either direction never compares records of two segments, and every other
+ * chunk start is proven or repaired.  Two uses: row_stride 0 with rot_stride 1 - Hc carrier hypotheses of one set of rows (a
+ * CPM carrier hypothesis is a rotated table, not a pass over the rows) -, and row_stride >= seglen with rot_stride 0 - several
+ * sets of rows under one table.  The chunk length is wf_cpm_soft's for a burst of nseg seglen calls
+ * (WF_OPT_CPM_SOFT_CHUNK_CALLS); options and counters as wf_cpm_soft; scratch: wf_cpm_soft_segments_geometry [3] bytes.
+ * nseg outside 1 .. 2^20, seglen < 1, row_stride neither 0 nor >= seglen, rot_stride outside {0, 1}, out_stride < seglen or
+ * not a multiple of 64, nseg out_stride (or nseg row_stride, nseg seglen) beyond 2^40, or any argument wf_cpm_soft_branch
+ * refuses: WF_ERR_VALUE before the context is touched. */
+int wf_cpm_soft_branch_segments(wf_ctx *ctx, const wf_cpm_detector_config *det, const double *d_rot_cs, int64_t rot_stride,
+                                const double *d_rows_ri, int64_t nseg, int64_t seglen, int64_t row_stride, int64_t out_stride,
+                                int64_t first_call, int warmup, double *d_llr, uint8_t *d_bits, uint8_t *d_branch, double *d_term,
+                                void *stream);
+/* What wf_cpm_soft_branch_segments launches on this context: h_geom[0] calls per chunk, [1] chunks in all, [2] warm-up calls,
+ * [3] bytes of scratch, [4] chunks per segment.  Host only. */
+int wf_cpm_soft_segments_geometry(wf_ctx *ctx, const wf_cpm_detector_config *det, int64_t nseg, int64_t seglen, int warmup,
+                                  int64_t *h_geom);
+
 /* Device-resident link for these waveforms (one bench step / trial block):
  * PRBS -> mapper (wf_symbol_map kind) -> cpm_modulate -> *exp(-j pi/4) + AWGN -> matched-filter
  * rows -> detector -> error count over symbols [skip_head, ncalls - D].  Stage events as in

@@ -497,6 +497,142 @@ def main_acquire(args) -> None:
     print(text)
 
 
+def _time_acquisition_cpm(lk, acq_kw, stacks, ncalls, carrier, timing, ebn0, steps):
+    """``_time_acquisition`` for the CPM links: one ``CPMJointAcquisition`` of a burst of about ``ncalls`` calls per entry of
+    ``stacks`` (name -> (stack, anchor)), beside one plain ``cpm_soft`` of as many calls."""
+    import torch
+
+    from waveforms_amd import device as dev
+    from waveforms_amd.encoding.coded import CPM_WAVEFORMS
+    from waveforms_amd.sync.joint_cpm import CPMJointAcquisition
+    from waveforms_amd.viterbi import cpm as vc
+
+    sps, spec = lk.sps, lk.spec
+    nsym = int(ncalls)
+    bits = dev.lfsr_bits(23, lk._mask, (1 << 23) - 1, nsym * spec.bits_per_symbol)[0]
+    sig = dev.cpm_modulate(dev.symbol_map(CPM_WAVEFORMS[lk.waveform], bits), lk._d_h, lk._d_pulse, sps)
+    dev.carrier_offset(sig, carrier[0], carrier[1], 0, out=sig)
+    sig = dev.timing_offset(sig, timing[0], timing[1], 0)
+    geo = vc.filter_geometry(int(lk._d_pulse.numel()), sps, spec, nsym)
+    start0, ncalls = int(geo["start0"]), int(geo["ncalls"])
+    received = dev.awgn(sig, int(sig.shape[0]), lk.sigma(ebn0), 1, 0, 0, np.exp(-1j * np.pi / 4))
+    del sig
+    plain = dev.cpm_mf_rows(received, lk._d_templates, start0, sps, ncalls)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    soft_ms = 0.0
+    for s in range(steps + 1):
+        ev[0].record()
+        dev.cpm_soft(plain, spec, 0, 0, d_rot=lk._d_rot)
+        ev[1].record()
+        torch.cuda.synchronize()
+        soft_ms += ev[0].elapsed_time(ev[1]) if s else 0.0
+    del plain
+    n = max(steps, 1)
+    out = {"calls": ncalls, "soft_detector_ms": round(soft_ms / n, 4)}
+    for name, (stack, anchor) in stacks.items():
+        acq = CPMJointAcquisition(spec, sps, stack=stack, anchor=anchor, **acq_kw)
+        ms = 0.0
+        for s in range(steps + 1):
+            acq.times = False
+            ev[0].record()
+            res = acq.recover(received, lk._d_templates, start0, ncalls)
+            ev[1].record()
+            torch.cuda.synchronize()
+            ms += ev[0].elapsed_time(ev[1]) if s else 0.0
+            del res
+        acq.times = True                                                  # (the stages from a call of their own: the events cost time)
+        acq.recover(received, lk._d_templates, start0, ncalls)
+        stages = {k: round(v, 4) for k, v in acq.stage_times().items()}
+        out[name] = {"stack": stack, "ms": round(ms / n, 4), "launches": acq.launches, "in_soft_detections": round(ms / n / (soft_ms / n), 2),
+                     "stages_ms": stages}
+    return out
+
+
+def main_acquire_cpm(args) -> None:
+    """The ``--acquire`` form for ``--waveform multih|pcmfm``: genie, impaired and acquired FRAMED CodedCPMLink on the same blocks
+    under a carrier offset AND a clock offset (``CPMJointAcquisition``), the anchored curve with ``--anchor``, and the time of one
+    acquisition, unstacked and stacked, on the link's own burst and on bursts of ``--acq-time-rows`` calls.  The result goes
+    under the waveform's key of ``--acq-out``, beside what the file holds for the other waveform."""
+    import math
+
+    import torch
+
+    from waveforms_amd.encoding import ldpc
+    from waveforms_amd.encoding.coded import CodedCPMLink
+    from waveforms_amd.encoding.framing import Framing
+    from waveforms_amd.sync.joint_cpm import MAX_DRIFT_PERIODS, MAX_DRIFT_SAMPLES, CPMJointAcquisition
+    from waveforms_amd.viterbi import cpm as vc
+
+    torch.cuda.set_device(0)
+    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
+    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
+    carrier, timing = (math.radians(args.carrier_phase), args.carrier_freq), (args.timing_offset, args.timing_drift)
+    fr = Framing(code)
+    sps = 8
+    spec = vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
+    common = dict(timing_window=args.timing_window, carrier_window=args.carrier_window, span=args.timing_span, timing_hypotheses=args.timing_hyp,
+                  carrier_hypotheses=args.carrier_hyp or 2, refine=args.timing_refine, delta=args.timing_delta)
+    kw = dict(waveform=args.waveform, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
+    acqs = {"acquired": CPMJointAcquisition(spec, sps, stack=args.acq_stack or None, **common)}
+    if args.anchor:
+        acqs["anchored"] = CPMJointAcquisition(spec, sps, stack=args.acq_stack or None, anchor=args.anchor, **common)
+    links = {"genie": CodedCPMLink(code, per, **kw), "impaired": CodedCPMLink(code, per, carrier=carrier, clock=timing, **kw)}
+    for name, acq in acqs.items():
+        links[name] = CodedCPMLink(code, per, carrier=carrier, clock=timing, joint=acq, **kw)
+    a = acqs["acquired"]
+    out = {"tool": "coded_ber", "form": "acquire", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
+           "block_codewords": per, "burst_calls": links["genie"].ncalls, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
+           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
+                       "drift_turns_per_carrier_window": abs(args.carrier_freq) * sps * a.carrier_window,
+                       "documented_limit_turns_per_carrier_window": MAX_DRIFT_PERIODS / spec.p},
+           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_timing_window": abs(args.timing_drift) * sps * a.timing_window,
+                      "documented_limit_samples_per_timing_window": MAX_DRIFT_SAMPLES[args.waveform]},
+           "acquisition": {"timing_window": a.timing_window, "carrier_window": a.carrier_window, "span": a.span, "timing_hypotheses": a.timing_hypotheses,
+                           "carrier_hypotheses": a.carrier_hypotheses, "refine": a.refine, "delta": a.delta, "stack": a.stack, "anchor": args.anchor},
+           "points": []}
+    for e in args.ebn0:
+        point = {"ebn0_info_db": e}
+        b = 0
+        for name, lk in links.items():
+            lk.reset_counts()
+            b, rejected = 0, [0, 0]
+            while b * per < args.codewords:
+                lk.run_block(e, seed=1, stream_id=b)
+                if name == "anchored":
+                    found = lk.joint_result()[4:]
+                    rejected = [rejected[0] + found[1], rejected[1] + found[3]]
+                b += 1
+            be, fe, nc, m, mean_it = lk.result()
+            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
+                           "mean_iters": round(mean_it, 3), "wrong_locks": lk.sync_result()[1], "last_lock": lk.sync_result()[2][0]}
+            if name == "anchored":
+                point[name]["rejected_windows"] = {"timing": rejected[0], "carrier": rejected[1]}
+        point["codewords"] = b * per
+        out["points"].append(point)
+    g = _ebn0_at_fer(out["points"], "genie")
+    out["ebn0_at_fer_1e-2"] = {"genie": g}
+    out["loss_db_at_fer_1e-2"] = {}
+    for name in acqs:
+        r = _ebn0_at_fer(out["points"], name)
+        out["ebn0_at_fer_1e-2"][name] = r
+        out["loss_db_at_fer_1e-2"][name] = None if g is None or r is None else round(r - g, 3)
+    # one acquisition, unstacked (cpm_soft_branch per table and per buffer) and stacked, in units of one plain soft detection
+    stacks = {"stack_1": (1, 0), "stacked": (None, 0)}
+    if args.anchor:
+        stacks["stacked_anchored"] = (None, args.anchor)
+    lengths = [links["genie"].ncalls] + ([1_000_000] if args.acq_time_rows == [211_252, 10_000_000] else args.acq_time_rows)
+    out["one_acquisition"] = [_time_acquisition_cpm(links["acquired"], common, stacks, n, carrier, timing, args.ebn0[-1], args.steps) for n in lengths]
+    print(json.dumps(out))
+    if args.acq_out:
+        path = Path(args.acq_out)
+        if path.name == "joint_acquisition.json":                         # (the SOQPSK-TG form's default)
+            path = path.with_name("joint_acquisition_cpm.json")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        held = json.loads(path.read_text()) if path.exists() else {}
+        held[args.waveform] = out
+        path.write_text(json.dumps(held, indent=1) + "\n")
+
+
 def main_conv(args) -> None:
     """The ``--code conv-*`` form: ConvSOQPSKLink."""
     import torch
@@ -680,17 +816,18 @@ def main() -> None:
     ap.add_argument("--timing-delta", type=float, default=None, help="--recover-timing: spacing of a refinement's three points, samples (default: 2.0; the class's for ARTM and PCM/FM)")
     ap.add_argument("--anchor", type=int, default=0, help="--recover-timing / --acquire: K of the anchored unwrapping (odd, 3 .. 1023); adds the "
                     "anchored curve beside the unanchored one on the same blocks (0: none)")
-    ap.add_argument("--acquire", action="store_true", help="genie, impaired and acquired framed links on the same blocks under --carrier-* AND --timing-* (JointAcquisition)")
+    ap.add_argument("--acquire", action="store_true", help="genie, impaired and acquired framed links on the same blocks under --carrier-* AND --timing-* (JointAcquisition; "
+                    "--waveform multih|pcmfm: CPMJointAcquisition, with --timing-* / --carrier-window / --carrier-hyp as its arguments, into profiles/joint_acquisition_cpm.json)")
     ap.add_argument("--acq-timing-hyp", type=int, default=4, help="--acquire: timing hypotheses over one symbol")
     ap.add_argument("--acq-carrier-hyp", type=int, nargs="+", default=[8], help="--acquire: carrier hypotheses over [0, pi); further values add a curve each")
     ap.add_argument("--acq-stack", type=int, default=0, help="--acquire: carrier hypotheses per stacked launch set (0: all that fit the byte budget; 1: unstacked)")
-    ap.add_argument("--acq-time-rows", type=int, nargs="*", default=[211_252, 10_000_000], help="--acquire: burst lengths one acquisition is timed at")
+    ap.add_argument("--acq-time-rows", type=int, nargs="*", default=[211_252, 10_000_000], help="--acquire: burst lengths one acquisition is timed at (ARTM, PCM/FM: the link's own and 1e6 calls)")
     ap.add_argument("--acq-out", default=str(ROOT / "profiles" / "joint_acquisition.json"), help="--acquire: where the result is also written ('' : nowhere)")
     args = ap.parse_args()
     if args.acquire:
-        if args.code.startswith("conv") or args.outer or args.live_only or args.recover or args.recover_timing or args.waveform != "soqpsk":
-            ap.error("--acquire is the framed CodedSOQPSKLink's: an LDPC code, no --outer / --live-only / --recover / --recover-timing / --waveform")
-        return main_acquire(args)
+        if args.code.startswith("conv") or args.outer or args.live_only or args.recover or args.recover_timing:
+            ap.error("--acquire is the framed CodedSOQPSKLink's and CodedCPMLink's: an LDPC code, no --outer / --live-only / --recover / --recover-timing")
+        return main_acquire(args) if args.waveform == "soqpsk" else main_acquire_cpm(args)
     if args.recover_timing or args.timing_offset or args.timing_drift:
         if not args.recover_timing:
             ap.error("--timing-offset / --timing-drift go with --recover-timing")

@@ -150,6 +150,8 @@ SIGNATURES = {
     "wf_cpm_mf_rows_resample_c128": (c_int, [_P, _P, c_int64, _P, c_int, c_int, c_int, c_int64, c_int, c_int64, c_int, _P, c_int64, c_double, _P, _P]),
     "wf_cpm_mf_rows_resample_geometry": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
     "wf_llr_stat": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P]),
+    "wf_cpm_soft_branch_segments": (c_int, [_P, _P, _P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, _P, _P, _P, _P, _P]),
+    "wf_cpm_soft_segments_geometry": (c_int, [_P, _P, c_int64, c_int64, c_int, POINTER(c_int64)]),
     "wf_cpm_link_workspace_bytes": (c_int64, [_P]),
     "wf_cpm_link_run": (c_int, [_P, _P, _P, c_int64, _P, POINTER(c_int64), _P]),
     "wf_cpm_link_layout": (c_int, [_P, POINTER(c_int64)]),

@@ -39,6 +39,11 @@ struct cpm_soft_params {
     int dt[3];                  // tilt(n + 1) - tilt(n) mod 2p by the variant of call n's leaving symbol: (M - 1) K; 0 pre-start
     int ch, W;
     int64_t n, n0, nch, nsub;   // calls, global index of call 0, chunks, checkpoints per chunk
+    // SEG only (wf_cpm_segments.hip; a burst's kernels never read them): n is then a SEGMENT's calls and nch the launch's chunks,
+    // cps of them per segment; per segment the rows and the rotation table advance by row_stride / rot_stride double2, the
+    // outputs by out_stride calls
+    int64_t row_stride, out_stride;
+    int cps, rot_stride;
     // dest[kv][s][u] = 4 * end state + slot of branch (s, u); kv 0 / 1: the leaving symbol uses K[0] / K[1], 2: pre-start
     uint8_t dest[3][64][4];
 };
@@ -97,6 +102,62 @@ __device__ __forceinline__ void cs_stage_rot(const double2 *__restrict__ rot_cs,
         rot[k] = e.x;
         rot[CPM_ROT_SIN + k] = e.y;
     }
+}
+
+// SEG: the table of ONE wave's segment, staged by that wave into its own copy (waves of a workgroup may belong to different segments)
+__device__ __forceinline__ void cs_stage_rot_wave(const double2 *__restrict__ rot_cs, const cpm_soft_params &P, double *rot)
+{
+    wide_wave_sync();                                // (a repair's previous record has been read to its end)
+    for (int k = threadIdx.x & 63; k < 2 * P.p; k += 64) {
+        const double2 e = rot_cs[k];
+        rot[k] = e.x;
+        rot[CPM_ROT_SIN + k] = e.y;
+    }
+    wide_wave_sync();
+}
+
+// Chunk c of the launch: calls a .. e - 1 of segment seg.  A burst is segment 0 and c counts its chunks; with SEG every segment
+// is cut into cps chunks from its own start, so chunk c is (segment c / cps, index c % cps): no table, no search, and a chunk
+// never crosses a segment.  The calls are counted from the segment's start, and P.n is its length: the clamps of cs_sweep and
+// the warm-ups' limits are then the segment's, as they are the burst's.
+struct cs_chunk {
+    int64_t a, e;
+    uint32_t seg;
+};
+
+// cps: P.cps, wherever the caller holds it (seg comes back in the same kind of register; a and e are scalar)
+template <bool SEG>
+__device__ __forceinline__ cs_chunk cs_find(const cpm_soft_params &P, int64_t c, uint32_t cps)
+{
+    uint32_t seg = 0;
+    int64_t j = c;
+    if constexpr (SEG) {                             // (a launch of segments holds fewer than 2^31 chunks)
+        seg = (uint32_t)c / cps;
+        j = __builtin_amdgcn_readfirstlane((uint32_t)c - seg * cps);
+    }
+    const int64_t a = j * P.ch;
+    return cs_chunk{a, a + P.ch < P.n ? a + P.ch : P.n, seg};
+}
+
+// Wave-uniform values held in VECTOR registers from here on: the segments' per-wave offsets are added to per-lane indices
+// anyway, and the repair kernels have no scalar registers to spare.
+__device__ __forceinline__ int64_t cs_in_vgpr(int64_t v)
+{
+    asm("" : "+v"(v));
+    return v;
+}
+
+__device__ __forceinline__ uint32_t cs_in_vgpr(uint32_t v)
+{
+    asm("" : "+v"(v));
+    return v;
+}
+
+__device__ __forceinline__ const double2 *cs_in_vgpr(const double2 *global_ptr)       // (stays a pointer to global memory)
+{
+    uintptr_t v = reinterpret_cast<uintptr_t>(global_ptr);
+    asm("" : "+v"(v));
+    return (const double2 *)(const __attribute__((address_space(1))) double2 *)v;
 }
 
 __device__ __forceinline__ int cs_kv(const cpm_soft_params &P, int64_t n)
@@ -362,12 +423,18 @@ __device__ __forceinline__ void cs_fwd_chunk(const cs_lane<M, LP, AP> &L, const 
 }
 
 // ---- the four steps (wf_cpm_soft.hip describes them); smem: CS_WAVES * WAVE_BYTES, rot: 2 * CPM_ROT_SIN doubles -------------
-template <int M, int LP, bool AP>
+// SEG (plain only; wf_cpm_segments.hip): the launch's chunks are those of P.nch / P.cps independent segments (cs_find); rot then
+// holds CS_WAVES tables, one per wave.  Records and checkpoints are indexed by the launch's chunk in either case, the backward
+// records mirrored over the LAUNCH (record r = chunk nch - 1 - r): nch is a multiple of cps, so in both directions the records
+// r with r % cps == 0 are those of the chunks that start at their segment's edge - exact, as record 0 of a burst is: never
+// compared with a predecessor and never handed a repair.
+template <int M, int LP, bool AP, bool SEG = false>
 __device__ __forceinline__ void cs_bounds_body(char *smem, double *rot, const double2 *__restrict__ rows, const double2 *__restrict__ rot_cs,
                                                uint64_t *__restrict__ fedge, uint64_t *__restrict__ bedge, double *__restrict__ ckpt,
                                                const cpm_soft_params &P, const cpm_soft_prior &prior)
 {
-    cs_stage_rot(rot_cs, P, rot);
+    static_assert(!(AP && SEG), "the segments are the plain detector's");
+    if constexpr (!SEG) cs_stage_rot(rot_cs, P, rot);
     if (blockIdx.x == 0 && threadIdx.x < CPM_NLIST) {          // the repair lists of both directions: empty
         cpm_list_counts(fedge, P.nch, CS_REC)[threadIdx.x] = 0;
         cpm_list_counts(bedge, P.nch, CS_REC)[threadIdx.x] = 0;
@@ -376,8 +443,14 @@ __device__ __forceinline__ void cs_bounds_body(char *smem, double *rot, const do
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = (int64_t)blockIdx.x * CS_WAVES + wave;
     if (c >= P.nch) return;
+    const cs_chunk k = cs_find<SEG>(P, c, (uint32_t)P.cps);
+    if constexpr (SEG) {
+        rot += cs_in_vgpr((int64_t)wave * 2 * CPM_ROT_SIN);
+        rows += cs_in_vgpr((int64_t)k.seg * P.row_stride);
+        cs_stage_rot_wave(rot_cs + (int64_t)k.seg * P.rot_stride, P, rot);
+    }
     const cs_lane<M, LP, AP> L = cs_setup<M, LP, AP>(rows, P, smem + wave * cs_lane<M, LP, AP>::WAVE_BYTES, rot, prior);
-    const int64_t a = c * P.ch, e = a + P.ch < P.n ? a + P.ch : P.n;
+    const int64_t a = k.a, e = k.e;
 
     double m = L.active ? 0.0 : __builtin_inf();
     cs_sweep<M, LP, true>(L, P, a - P.W > 0 ? a - P.W : 0, a, [&](int64_t, int t, int tilt, int kv) __attribute__((always_inline)) { cs_fwd(L, P, t, tilt, kv, m); });
@@ -395,14 +468,15 @@ __device__ __forceinline__ void cs_bounds_body(char *smem, double *rot, const do
 }
 
 // Every record against its predecessor: a wave per record r >= 1, lane = state.  Failed records are LISTED (list 0) for
-// the repair launches, or (repair = 0) counted as unproven.
-__device__ __forceinline__ void cs_verify_body(uint64_t *__restrict__ edge, int64_t nch, int S, unsigned long long *__restrict__ unmerged, int repair)
+// the repair launches, or (repair = 0) counted as unproven.  cps != 0 (segments): the records r % cps == 0 are exact, not compared.
+__device__ __forceinline__ void cs_verify_body(uint64_t *__restrict__ edge, int64_t nch, int S, unsigned long long *__restrict__ unmerged, int repair,
+                                               int cps = 0)
 {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t r = idx / 64 + 1;
     const int s = (int)(idx & 63);
     bool bad = false;
-    if (r < nch && s < S) bad = edge[r * CS_REC + s] != edge[(r - 1) * CS_REC + 64 + s];
+    if (r < nch && s < S && (cps == 0 || r % cps != 0)) bad = edge[r * CS_REC + s] != edge[(r - 1) * CS_REC + 64 + s];
     const unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
     if (s == 0 && m) {
         if (repair) {
@@ -418,7 +492,7 @@ __device__ __forceinline__ void cs_verify_body(uint64_t *__restrict__ edge, int6
 // it is now (it becomes the record's start), run the chunk's calls again in the record's direction, rewrite its end (and,
 // forward, its checkpoints), and list the next record when the end changed.  finisher != 0: one workgroup that goes on,
 // round after round, until a round hands nothing on.
-template <int M, int LP, bool BWD, bool AP>
+template <int M, int LP, bool BWD, bool AP, bool SEG = false>
 __device__ __forceinline__ void cs_repair_body(char *smem, double *rot, const double2 *__restrict__ rows, const double2 *__restrict__ rot_cs,
                                                uint64_t *__restrict__ edge, double *__restrict__ ckpt, unsigned long long *__restrict__ unmerged,
                                                const cpm_soft_params &P, const cpm_soft_prior &prior, int lin, int lout, int finisher)
@@ -426,10 +500,21 @@ __device__ __forceinline__ void cs_repair_body(char *smem, double *rot, const do
     uint64_t *const counts = cpm_list_counts(edge, P.nch, CS_REC);
     int64_t cnt = (int64_t)__hip_atomic_load(&counts[lin], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (cnt == 0) return;                                      // (the whole grid)
-    cs_stage_rot(rot_cs, P, rot);
+    static_assert(!(AP && SEG), "the segments are the plain detector's");
+    if constexpr (!SEG) cs_stage_rot(rot_cs, P, rot);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const cs_lane<M, LP, AP> L = cs_setup<M, LP, AP>(rows, P, smem + wave * cs_lane<M, LP, AP>::WAVE_BYTES, rot, prior);
+    uint32_t cps = 0, rot_stride = 0;
+    int64_t row_stride = 0;
+    if constexpr (SEG) {
+        rot += cs_in_vgpr((int64_t)wave * 2 * CPM_ROT_SIN);
+        rows = cs_in_vgpr(rows);
+        rot_cs = cs_in_vgpr(rot_cs);
+        cps = cs_in_vgpr((uint32_t)P.cps);
+        rot_stride = cs_in_vgpr((uint32_t)P.rot_stride);
+        row_stride = cs_in_vgpr(P.row_stride);
+    }
+    cs_lane<M, LP, AP> L = cs_setup<M, LP, AP>(rows, P, smem + wave * cs_lane<M, LP, AP>::WAVE_BYTES, rot, prior);
     const int64_t stride = (int64_t)gridDim.x * CS_WAVES;
     for (;;) {
         const uint64_t *list = cpm_list(edge, P.nch, CS_REC, lin);
@@ -442,7 +527,12 @@ __device__ __forceinline__ void cs_repair_body(char *smem, double *rot, const do
             if (L.active) rec[L.lane] = w;
             double m = L.active ? __longlong_as_double((long long)w) : __builtin_inf();
             const int64_t c = BWD ? P.nch - 1 - r : r;
-            const int64_t a = c * P.ch, e = a + P.ch < P.n ? a + P.ch : P.n;
+            const cs_chunk k = cs_find<SEG>(P, c, cps);
+            if constexpr (SEG) {                               // this record's segment: its rows and its table
+                L.rows = rows + (int64_t)k.seg * row_stride;
+                cs_stage_rot_wave(rot_cs + k.seg * rot_stride, P, rot);
+            }
+            const int64_t a = k.a, e = k.e;
             if constexpr (BWD)
                 cs_sweep<M, LP, false>(L, P, a, e, [&](int64_t, int t, int tilt, int kv) __attribute__((always_inline)) { cs_bwd(L, P, t, tilt, kv, m); });
             else
@@ -454,7 +544,7 @@ __device__ __forceinline__ void cs_repair_body(char *smem, double *rot, const do
                 atomicAdd(unmerged + 1, 1ull);                 // [1]: chunk repairs run, [2]: ... that handed on
                 if (changed) {
                     atomicAdd(unmerged + 2, 1ull);
-                    if (r + 1 < P.nch)
+                    if (r + 1 < P.nch && (!SEG || (uint32_t)(r + 1) % cps != 0))     // (SEG: the next record opens another segment)
                         cpm_list(edge, P.nch, CS_REC, lout)[atomicAdd(reinterpret_cast<unsigned long long *>(&counts[lout]), 1ull)] = (uint64_t)(r + 1);
                 }
             }
@@ -475,21 +565,36 @@ __device__ __forceinline__ void cs_repair_body(char *smem, double *rot, const do
 
 // ring_all: CS_WAVES * CS_SUB * 64 doubles — ã of the sub-block, lane-private columns.  AP: out = λᵉ, bits = (λᵉ + π) < 0.
 // BR: lane s* of call k writes branch[k] and, where term is not NULL, term[k] (1 + 16 bytes a call).
-template <int M, int LP, bool AP, bool BR = false>
+// SEG: call k of segment seg goes to output call seg * out_stride + k, and the wave of a segment's last chunk writes its pad.
+template <int M, int LP, bool AP, bool BR = false, bool SEG = false>
 __device__ __forceinline__ void cs_llr_body(char *smem, double *ring_all, double *rot, const double2 *__restrict__ rows,
                                             const double2 *__restrict__ rot_cs, const uint64_t *__restrict__ bedge, const double *__restrict__ ckpt,
                                             double *__restrict__ llr, uint8_t *__restrict__ bits, const cpm_soft_params &P,
                                             const cpm_soft_prior &prior, uint8_t *__restrict__ branch = nullptr, double2 *__restrict__ term = nullptr)
 {
     constexpr int LGM = cs_lane<M, LP, AP>::LGM;
-    cs_stage_rot(rot_cs, P, rot);
+    static_assert(!(AP && SEG), "the segments are the plain detector's");
+    if constexpr (!SEG) cs_stage_rot(rot_cs, P, rot);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t c = (int64_t)blockIdx.x * CS_WAVES + wave;
     if (c >= P.nch) return;
+    const cs_chunk kc = cs_find<SEG>(P, c, (uint32_t)P.cps);
+    if constexpr (SEG) {
+        rot += cs_in_vgpr((int64_t)wave * 2 * CPM_ROT_SIN);
+        rows += cs_in_vgpr((int64_t)kc.seg * P.row_stride);
+        cs_stage_rot_wave(rot_cs + (int64_t)kc.seg * P.rot_stride, P, rot);
+        const int64_t o = cs_in_vgpr((int64_t)kc.seg * P.out_stride);
+        llr += LGM * o;
+        bits += LGM * o;
+        if constexpr (BR) {
+            branch += o;
+            if (term) term += o;
+        }
+    }
     const cs_lane<M, LP, AP> L = cs_setup<M, LP, AP>(rows, P, smem + wave * cs_lane<M, LP, AP>::WAVE_BYTES, rot, prior);
     double *ring = ring_all + wave * CS_SUB * 64 + L.lane;
-    const int64_t a = c * P.ch, e = a + P.ch < P.n ? a + P.ch : P.n;
+    const int64_t a = kc.a, e = kc.e;
     double b = L.active ? __longlong_as_double((long long)bedge[(P.nch - 1 - c) * CS_REC + L.lane]) : __builtin_inf();   // b̃_e, proven
     const double *ck = ckpt + (size_t)c * P.nsub * P.S;
     for (int j = (int)((e - a - 1) / CS_SUB); j >= 0; --j) {
@@ -523,6 +628,20 @@ __device__ __forceinline__ void cs_llr_body(char *smem, double *ring_all, double
             }
         });
     }
+    if constexpr (SEG) {
+        if (e == P.n)                                          // the segment's last chunk: the pad outputs, +0 / 0
+            for (int64_t r = P.n + L.lane; r < P.out_stride; r += 64) {
+#pragma unroll
+                for (int i = 0; i < LGM; ++i) {
+                    llr[LGM * r + i] = 0.0;
+                    bits[LGM * r + i] = 0;
+                }
+                if constexpr (BR) {
+                    branch[r] = 0;
+                    if (term) term[r] = make_double2(0.0, 0.0);
+                }
+            }
+    }
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -551,6 +670,16 @@ static int cs_check(const wf_cpm_detector_config *d, const char *who)
     return WF_OK;
 }
 
+// The scratch of a launch of nch chunks of ch calls (a burst: its own; segments: nseg times the chunks of one)
+static void cs_layout(cs_geom &g, int S)
+{
+    g.nsub = (g.ch + CS_SUB - 1) / CS_SUB;
+    const size_t rec = (cpm_edge_total_words(g.nch, CS_REC) + 1) / 2 * 2;
+    g.off_b = rec;
+    g.off_ck = 2 * rec;
+    g.words = g.off_ck + (size_t)g.nch * (size_t)g.nsub * (size_t)S;
+}
+
 static cs_geom cs_geometry(const wf_ctx *ctx, int S, int64_t n, int warmup)
 {
     cs_geom g;
@@ -564,12 +693,32 @@ static cs_geom cs_geometry(const wf_ctx *ctx, int S, int64_t n, int warmup)
     }
     g.ch = (int)ch;
     g.nch = (n + ch - 1) / ch;
-    g.nsub = (ch + CS_SUB - 1) / CS_SUB;
-    const size_t rec = (cpm_edge_total_words(g.nch, CS_REC) + 1) / 2 * 2;
-    g.off_b = rec;
-    g.off_ck = 2 * rec;
-    g.words = g.off_ck + (size_t)g.nch * (size_t)g.nsub * (size_t)S;
+    cs_layout(g, S);
     return g;
+}
+
+// The proof and repair launches behind the bounds launch, per direction (0 forward, 1 backward), as the hard detectors
+// (wf_cpm_wide.hip): verify and list, two parallel repair rounds and the finisher - or, under WF_OPT_DET_REPAIR = 1, only count;
+// WF_OPT_DET_FINAL_VERIFY adds a counting pass behind the repairs.  verify(dir, repair) and repair(dir, round, blocks, finisher)
+// launch the caller's own kernels.
+template <class V, class R>
+static int cs_proof_passes(wf_ctx *ctx, V &&verify, R &&repair)
+{
+    const int rep = ctx->opt[WF_OPT_DET_REPAIR] == 0 ? 1 : 0;
+    for (int dir = 0; dir < 2; ++dir) {
+        verify(dir, rep);
+        WF_LAUNCH_CHECK();
+        if (!rep) continue;
+        for (int round = 0; round < 3; ++round) {
+            repair(dir, round, round < 2 ? CPM_REPAIR_BLOCKS : 1, round == 2 ? 1 : 0);
+            WF_LAUNCH_CHECK();
+        }
+        if (ctx->opt[WF_OPT_DET_FINAL_VERIFY]) {
+            verify(dir, 0);
+            WF_LAUNCH_CHECK();
+        }
+    }
+    return WF_OK;
 }
 
 // The full-phase trellis, enumerated as cpm_oracle.c does (state s = v + p c, branch (s, u)).

@@ -89,30 +89,20 @@ static int cs_front(wf_ctx *ctx, const cpm_soft_params &P, const cs_geom &g, con
     hipLaunchKernelGGL((cpm_soft_bounds_kernel<M, LP>), dim3(grid), dim3(CS_THREADS), 0, s, rows, rot, fedge, bedge, ckpt, P);
     WF_LAUNCH_CHECK();
     if (g.nch > 1) {
-        // as the hard detectors (wf_cpm_wide.hip): verify and list, two parallel repair rounds and the finisher — or, under
-        // WF_OPT_DET_REPAIR = 1, only count; WF_OPT_DET_FINAL_VERIFY adds a counting pass behind the repairs
-        const int repair = ctx->opt[WF_OPT_DET_REPAIR] == 0 ? 1 : 0;
         const dim3 vgrid((unsigned)(((g.nch - 1) * 64 + 255) / 256));
-        for (int dir = 0; dir < 2; ++dir) {
-            uint64_t *edge = dir ? bedge : fedge;
-            hipLaunchKernelGGL(cpm_soft_verify_kernel, vgrid, dim3(256), 0, s, edge, g.nch, P.S, ctx->d_vit_unmerged, repair);
-            WF_LAUNCH_CHECK();
-            if (!repair) continue;
-            for (int round = 0; round < 3; ++round) {
-                const dim3 rgrid(round < 2 ? CPM_REPAIR_BLOCKS : 1);
+        return cs_proof_passes(
+            ctx,
+            [&](int dir, int repair) {
+                hipLaunchKernelGGL(cpm_soft_verify_kernel, vgrid, dim3(256), 0, s, dir ? bedge : fedge, g.nch, P.S, ctx->d_vit_unmerged, repair);
+            },
+            [&](int dir, int round, unsigned blocks, int finisher) {
                 if (dir)
-                    hipLaunchKernelGGL((cpm_soft_repair_kernel<M, LP, true>), rgrid, dim3(CS_THREADS), 0, s, rows, rot, edge, ckpt, ctx->d_vit_unmerged, P,
-                                       round, round + 1, round == 2 ? 1 : 0);
+                    hipLaunchKernelGGL((cpm_soft_repair_kernel<M, LP, true>), dim3(blocks), dim3(CS_THREADS), 0, s, rows, rot, bedge, ckpt,
+                                       ctx->d_vit_unmerged, P, round, round + 1, finisher);
                 else
-                    hipLaunchKernelGGL((cpm_soft_repair_kernel<M, LP, false>), rgrid, dim3(CS_THREADS), 0, s, rows, rot, edge, ckpt, ctx->d_vit_unmerged, P,
-                                       round, round + 1, round == 2 ? 1 : 0);
-                WF_LAUNCH_CHECK();
-            }
-            if (ctx->opt[WF_OPT_DET_FINAL_VERIFY]) {
-                hipLaunchKernelGGL(cpm_soft_verify_kernel, vgrid, dim3(256), 0, s, edge, g.nch, P.S, ctx->d_vit_unmerged, 0);
-                WF_LAUNCH_CHECK();
-            }
-        }
+                    hipLaunchKernelGGL((cpm_soft_repair_kernel<M, LP, false>), dim3(blocks), dim3(CS_THREADS), 0, s, rows, rot, fedge, ckpt,
+                                       ctx->d_vit_unmerged, P, round, round + 1, finisher);
+            });
     }
     return WF_OK;
 }

@@ -676,6 +676,47 @@ def cpm_soft_branch(rows, spec, first_call: int = 0, warmup: int = 0, ctx=None, 
     return llr[:n * lg], bits[:n * lg], branch[:n], (term[:n] if terms else None)
 
 
+def cpm_soft_branch_segments(rows, spec, nseg: int, seglen: int, row_stride: int, out_stride: int, d_rot, rot_stride: int = 0,
+                             first_call: int = 0, warmup: int = 0, ctx=None, terms: bool = True):
+    """``cpm_soft_branch`` over ``nseg`` independent segments in one set of launches (``wf_cpm_soft_branch_segments``;
+    include/wfhip.h states the definition) -> (llr f64[nseg out_stride lgM], bits u8[...], branch u8[nseg out_stride], term
+    f64[nseg out_stride, 2] or None).  Segment s reads rows s row_stride .. + seglen - 1 of ``rows`` (``row_stride`` 0: every
+    segment the same rows) under table s rot_stride of ``d_rot`` (device float64[ntab, 2p, 2]; ``rot_stride`` 0 or 1) and comes
+    out at call offset s out_stride bitwise as ``cpm_soft_branch`` of those rows and that table alone; the outputs of the
+    calls behind ``seglen`` in each stride are 0.  ``out_stride``: a multiple of 64, at least ``seglen``."""
+    nseg, seglen, row_stride, out_stride, rot_stride = int(nseg), int(seglen), int(row_stride), int(out_stride), int(rot_stride)
+    if not rows.is_contiguous() or not d_rot.is_contiguous():
+        raise ValueError("rows and tables must be contiguous")
+    per = 2 * spec.nfilt
+    if rows.numel() % per:
+        raise ValueError(f"{rows.numel()} doubles of rows are not a whole number of {spec.nfilt}-filter rows")
+    if nseg < 1 or seglen < 1 or (row_stride != 0 and row_stride < seglen) or rot_stride not in (0, 1) or out_stride < seglen or out_stride % 64:
+        raise ValueError("nseg and seglen must be at least 1, row_stride 0 or at least seglen, rot_stride 0 or 1, out_stride a multiple of 64 and at least seglen")
+    need = (nseg - 1) * row_stride + seglen
+    if rows.numel() // per < need:
+        raise ValueError(f"{rows.numel() // per} rows are fewer than the {need} that {nseg} segments at stride {row_stride} take")
+    ntab = (nseg - 1) * rot_stride + 1
+    if d_rot.numel() < ntab * 4 * spec.p:
+        raise ValueError(f"d_rot holds fewer than {ntab} tables of {2 * spec.p} (cos, sin) pairs")
+    n, lg = nseg * out_stride, spec.bits_per_symbol
+    llr = _hip.empty(n * lg, "float64")
+    bits = _hip.empty(n * lg + 16, "uint8")
+    branch = _hip.empty(n + 16, "uint8")
+    term = _hip.empty((n, 2), "float64") if terms else None
+    cfg = spec.c_config()
+    _hip.check(_hip.lib().wf_cpm_soft_branch_segments(_ctx(ctx), ctypes.byref(cfg), _hip.ptr(d_rot), rot_stride, _hip.ptr(rows), nseg, seglen,
+                                                      row_stride, out_stride, int(first_call), int(warmup), _hip.ptr(llr), _hip.ptr(bits),
+                                                      _hip.ptr(branch), _hip.ptr(term), _hip.stream()))
+    return llr, bits[:n * lg], branch[:n], term
+
+
+def cpm_soft_segments_geometry(spec, nseg: int, seglen: int, warmup: int = 0, ctx=None) -> dict:
+    """What ``cpm_soft_branch_segments`` launches for ``nseg`` segments of ``seglen`` calls on this context
+    (``wf_cpm_soft_segments_geometry``)."""
+    return _geometry("wf_cpm_soft_segments_geometry", ("chunk_calls", "chunks", "warmup", "scratch_bytes", "chunks_per_segment"), _ctx(ctx),
+                     ctypes.byref(spec.c_config()), int(nseg), int(seglen), int(warmup))
+
+
 def cpm_soft_apriori(rows, spec, apriori=None, apriori_scale: float = 1.0, first_call: int = 0, warmup: int = 0, ctx=None, d_rot=None):
     """``cpm_soft`` with a per-bit prior and extrinsic per-bit output (``wf_cpm_soft_apriori``; include/wfhip.h states the
     definition) -> (ext f64[n lgM], bits u8[n lgM]) on device.  ``apriori``: a contiguous device float32 tensor of n lgM

@@ -48,6 +48,12 @@ place of ``cpm_mf_rows``.  (The names are not ``timing`` / ``timing_recovery``: 
 ``TimingRecovery`` passed as ``clock_recovery`` is refused.)  ``clock_recovery`` needs a ``framing`` (the rows come back shifted
 by a whole number of periods of nh symbols, which the frame search absorbs), excludes ``carrier`` and ``recovery`` and must be
 for the link's design and sps.  Both default to None: the same calls as before.
+
+``CodedCPMLink`` and ``IterativeCPMLink`` also take ``joint``, a :class:`waveforms_amd.sync.joint_cpm.CPMJointAcquisition` that
+makes the rows from the noisy samples under BOTH impairments (``carrier=`` and ``clock=`` may be given beside it).  (The name is
+not ``acquisition``: that stays a TypeError on the CPM classes.)  It needs a ``framing`` (the pair comes back modulo the lattice
+of (nh sps, P/2) and (0, P): the rows may be a whole number of periods early or late), excludes ``recovery`` and
+``clock_recovery`` and must be for the link's design and sps.  Default None: the same calls as before.
 """
 from __future__ import annotations
 
@@ -219,6 +225,37 @@ class _Framed:
         if self.clock_recovery is None or self._clock_tau is None:
             raise RuntimeError("clock_result needs a clock_recovery and a block that ran")
         return (_hip.to_host(self._clock_tau), _hip.to_host(self._clock_choice), int(self._clock_grid.cpu())) + self._found(self.clock_recovery.timing_found)
+
+    def _joint_init(self, joint, spec, sps: int, framing, recovery, clock_recovery) -> None:
+        """``joint``: a ``waveforms_amd.sync.joint_cpm.CPMJointAcquisition`` that makes the detector's rows from the noisy samples
+        under a carrier AND a clock offset (``carrier=`` and ``clock=`` may both be given beside it).  None: nothing is added to
+        the chain.  Checked against the link's other keywords before anything touches the device."""
+        if joint is not None:
+            from ..sync.joint_cpm import CPMJointAcquisition
+
+            if not isinstance(joint, CPMJointAcquisition):
+                raise ValueError("joint is a waveforms_amd.sync.joint_cpm.CPMJointAcquisition")
+            if recovery is not None or clock_recovery is not None:
+                raise ValueError("joint excludes recovery and clock_recovery: it recovers the carrier and the timing itself")
+            if joint.spec != spec:
+                raise ValueError("the joint acquisition is for another design than the link's full-phase trellis")
+            if joint.sps != sps:
+                raise ValueError(f"the joint acquisition is for sps = {joint.sps}, the link has {sps}")
+            if framing is None:
+                raise ValueError("joint needs a framing: the instant and the phase are recovered modulo (nh sps, P/2) and (0, P), "
+                                 "and the frame search absorbs the shift")
+        self.joint = joint
+        self._joint = None
+
+    def joint_result(self):
+        """(tau float64[nwt] in samples per timing window, phase float64[nwc] in radians per carrier window - both modulo the
+        lattice of waveforms_amd/sync/joint_cpm.py; timing choice uint8[nwt]; carrier choice uint8[nwc]) of the last block's joint
+        acquisition - synchronises.  An acquisition with an ``anchor`` adds (the timing drift found in samples per window, the
+        rejected windows of the coarse timing track, the carrier drift found in radians per window, the rejected windows of the
+        coarse carrier track)."""
+        if self.joint is None or self._joint is None:
+            raise RuntimeError("joint_result needs a joint acquisition and a block that ran")
+        return tuple(_hip.to_host(v) for v in self._joint) + self._found(self.joint.timing_found, self.joint.carrier_found)
 
     def _rate_db(self) -> float:
         """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""
@@ -435,7 +472,7 @@ class _CPM(_Link):
     _lam0 = 0
     bits_per_symbol = property(lambda self: self.spec.bits_per_symbol)
 
-    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, *, clock=None, clock_recovery=None, **burst) -> None:
+    def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, *, clock=None, clock_recovery=None, joint=None, **burst) -> None:
         from ..viterbi import cpm
 
         if waveform not in CPM_WAVEFORMS:
@@ -444,6 +481,7 @@ class _CPM(_Link):
             raise ValueError(f"ARTM sends two bits per symbol: a code with an odd n_tx = {code.n_tx} is refused")
         self.waveform, self.spec = waveform, cpm.ARTM_64 if waveform == "multih" else cpm.PCMFM_20
         self._clock_init(clock, clock_recovery, self.spec, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
+        self._joint_init(joint, self.spec, int(sps), burst.get("framing"), burst.get("recovery"), clock_recovery)
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -488,6 +526,9 @@ class _CPM(_Link):
             rows, self._clock_tau, self._clock_choice, self._clock_grid = self.clock_recovery.recover(received, self._d_templates, self.start0,
                                                                                                      self.ncalls)
             return rows, syms
+        if self.joint is not None:
+            rows, *self._joint = self.joint.recover(received, self._d_templates, self.start0, self.ncalls)
+            return rows, syms
         rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
         return rows, syms
 
@@ -509,7 +550,7 @@ class _CPM(_Link):
         return dev.cpm_soft_apriori(rows, self.spec, prior, self.damping, 0, 0 if prior is None else self.prior_warmup, d_rot=self._d_rot)
 
     def count_uncoded(self, hard, tx, syms=None) -> None:
-        if self.clock_recovery is not None:         # (recovered rows may sit a period from the sent bits: nothing to compare at)
+        if self.clock_recovery is not None or self.joint is not None:      # (recovered rows may sit a period from the sent bits: nothing to compare at)
             return
         flat = tx.reshape(-1) if self.framing is None else self.sent
         dev.count_errors(hard, flat, hard, flat, self.nch, self.uncoded)     # (bits in both pairs: [1] is what is read)
@@ -517,6 +558,9 @@ class _CPM(_Link):
     def uncoded_result(self) -> tuple[int, int]:
         if self.clock_recovery is not None:
             raise RuntimeError("uncoded_result: a clock recovery leaves the rows a whole number of periods early or late in some "
+                               "bursts; the channel bits are not counted (the decoder's counts hold)")
+        if self.joint is not None:
+            raise RuntimeError("uncoded_result: a joint acquisition leaves the rows a whole number of periods early or late in some "
                                "bursts; the channel bits are not counted (the decoder's counts hold)")
         return super().uncoded_result()
 
@@ -582,10 +626,10 @@ class CodedCPMLink(_LDPC, _CPM):
     first codeword at most lgM channel errors (one decoder iteration when there is no noise)."""
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0, clock=None, clock_recovery=None, carrier=None, recovery=None) -> None:
+                 lead_bits: int = 0, clock=None, clock_recovery=None, joint=None, carrier=None, recovery=None) -> None:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
         super().__init__(code, ncw, waveform, sps, framing=framing, lead_bits=lead_bits, clock=clock, clock_recovery=clock_recovery,
-                         carrier=carrier, recovery=recovery)
+                         joint=joint, carrier=carrier, recovery=recovery)
 
 
 class _LDPCLoop:
@@ -779,13 +823,13 @@ class IterativeCPMLink(_LDPCLoop, CodedCPMLink):
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False,
                  prior_warmup: int = 512, framing=None, lead_bits: int = 0, marker_prior: float | None = None, clock=None,
-                 clock_recovery=None, carrier=None, recovery=None) -> None:
+                 clock_recovery=None, joint=None, carrier=None, recovery=None) -> None:
         if prior_warmup < 0:
             raise ValueError("prior_warmup must not be negative")
         self.prior_warmup = int(prior_warmup)
         super().__init__(code, ncw, waveform=waveform, sps=sps, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
                          ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, clock=clock,
-                         clock_recovery=clock_recovery, carrier=carrier, recovery=recovery)
+                         clock_recovery=clock_recovery, joint=joint, carrier=carrier, recovery=recovery)
 
     def begin(self, ncalls: int | None = None) -> None:
         """Fresh loop state of one block: prior 0 on every bit of every call, every codeword open, no iterations."""
