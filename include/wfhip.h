@@ -1295,6 +1295,41 @@ int wf_cpm_link_stream_chunk_phase(wf_ctx *ctx, const wf_cpm_link_config *cfg, i
                                    void *d_state, void *d_workspace, int64_t workspace_bytes, int64_t *d_counts,
                                    int64_t *h_compared, int phases, void *stream);
 
+/* ---- Coarse carrier frequency acquisition for SOQPSK-TG: feed-forward, one pass over the noisy samples ------------------
+ * (The reference has no synchroniser; these entry points are defined here.  waveforms_amd/sync/coarse.py restates each in
+ * numpy: line_samples_host, line_spectra_host, coarse_estimate_host, correct_host.)
+ * SOQPSK-TG is a CPM with h = 1/2: the square of the received signal carries two spectral lines at 2 nu ± (1 + eps) / (2 sps)
+ * cycles per sample (nu the carrier offset, eps the clock drift).  Inputs: r_k, k < n, complex128; sps 2 .. 64; S = smooth,
+ * 1 .. 1024; L = nfft, a power of two from 64 to 4096; R = search >= 1.
+ * 1. Line samples.  y_k = Σ_{j < S} r_{k+j} (j increasing);  z_k = y_k²;  nb = (n - S + 1) / sps (integer division);
+ *      u_σ[m] = Σ_{i < sps} z_{m sps + i} exp(jσπ ((m sps + i) mod 2 sps) / sps)   (i increasing),  m < nb,  σ ∈ {-1, +1}:
+ *    σ = -1 brings the upper line down to 2 nu, σ = +1 the lower line up.  The 2 sps rotations are a table, exp(jπ q / sps).
+ * 2. Line spectra.  nseg = nb / L (the tail is dropped; nseg < 1: WF_ERR_VALUE);
+ *      P_σ[b] = Σ_{s < nseg} |FFT_L(w ⊙ u_σ[s L : (s + 1) L])[b]|²   in fftshift order (bin L/2 is frequency 0),
+ *    w = d_window, L doubles (np.hanning(L) in the Python layer).  d_spectra = [P₋ | P₊], 2 L doubles.  Workgroup partials
+ *    (d_scratch: wf_coarse_scratch_doubles(n, sps, nfft, smooth) doubles; -1 where the arguments would be refused) are added
+ *    in a fixed order, with no floating-point atomics: two launches on the same input give the same bits.
+ * 3. Estimate (wf_coarse_estimate).  T = P₋ + P₊;  i* = the first maximum of T over the bins R + 1 .. L - R - 2;  per line
+ *    i_σ = the first maximum of P_σ over i* - R .. i* + R (a NaN never wins);  f_σ = i_σ + d with, on a, b, c = the natural
+ *    logs of the bins i_σ - 1, i_σ, i_σ + 1,   d = ½ (a - c) / ((a - b) + (c - b)),   d = 0 where that denominator is not negative
+ *    and finite or where any of the three bins is <= 0 or not finite.
+ *      d_found[0] = nu  = ((f₋ + f₊) / 2 - L / 2) / (2 L sps)   cycles per sample
+ *      d_found[1] = eps = (f₋ - f₊) / L       (a clock drift moves the two lines apart; reported, not used here)
+ *      d_found[2] = T[i*],  d_found[3] = the mean of T: a lock indicator for the caller, nothing here thresholds them.
+ *    search outside 1 .. L / 2 - 2: WF_ERR_VALUE.
+ * 4. Correction (wf_carrier_offset_dev_c128).  out_k = in_k exp(j 2π frac(nu (first_index + k))) with nu = gain * d_nu[0] read
+ *    from device memory (gain a host scalar: -1 removes the estimate): the operations of wf_carrier_offset_c128 with
+ *    theta0 = 0 in the same order, so the result is BITWISE what that entry point gives for the same value passed from the host.
+ *    In place (d_out_ri == d_in_ri) allowed; a partial overlap, or d_nu inside the output, is refused.
+ * A NULL pointer, samples not 16-byte or doubles not 8-byte aligned, an output that overlaps an input or the scratch, n
+ * outside 1 .. 2^40 (the correction: first_index + n <= 2^53), gain not finite: WF_ERR_VALUE before the context is touched. */
+int64_t wf_coarse_scratch_doubles(int64_t n, int sps, int nfft, int smooth);
+int wf_coarse_lines_c128(wf_ctx *ctx, const double *d_r_ri, int64_t n, int sps, int smooth, int nfft, const double *d_window,
+                         double *d_scratch, double *d_spectra, void *stream);
+int wf_coarse_estimate(wf_ctx *ctx, const double *d_spectra, int nfft, int sps, int search, double *d_found, void *stream);
+int wf_carrier_offset_dev_c128(wf_ctx *ctx, const double *d_in_ri, int64_t n, const double *d_nu, double gain,
+                               int64_t first_index, double *d_out_ri, void *stream);
+
 /* ---- data products of the reference's plotting helpers (no plotting) ------------------
  * Welch PSD exactly as Axes.psd / matplotlib.mlab.psd evaluates the call of
  * waveforms/viz/psd.py:36-41 (window d_window of nfft doubles, np.hanning for the reference;

@@ -66,7 +66,12 @@ window, ``--carrier-hyp`` hypotheses, ``--carrier-span``, ``--carrier-refine``).
 unframed CodedCPMLink and the recovery is ``CPMCarrierRecovery`` (``--carrier-hyp`` defaults to the class's 2).  It also prints the recovery's kernel times per
 block (device events around every stage, summed over the passes, ``--steps`` blocks after one warm-up) beside one plain soft
 detection of the same rows, and ``loss_db_at_fer_1e-2``: recovered minus genie, both interpolated in log FER (null where a
-curve does not cross 1e-2 inside the sweep).
+curve does not cross 1e-2 inside the sweep).  ``--coarse [--coarse-nfft N --coarse-smooth S]`` (SOQPSK-TG) adds two curves on the
+same blocks: ``coarse``, a ``CoarseFrequency`` in front of the same recovery, and ``reference``, that recovery at ``--carrier-freq
+0`` - with the estimates' statistics over the bursts, the bursts in which the coarse link loses codewords the reference keeps
+(with the burst's frequency error), the coarse stage's times and ``coarse_cost_db_at_fer_1e-2``: coarse minus reference.  Beside
+``--acquire`` it does the same around the acquisition (the anchored one with ``--anchor``), the reference under the same timing
+offset; the estimates are held against the frequency in cycles per RECEIVED sample, NU (1 + EPS), and against EPS.
 
 With ``--timing-offset TAU`` (samples) / ``--timing-drift EPS`` (samples per sample) and ``--recover-timing`` the tool does the
 same for the symbol timing of the framed SOQPSK-TG link: ``genie`` (no offset), ``impaired`` (``timing=(TAU, EPS)``, no recovery)
@@ -157,6 +162,19 @@ def _ebn0_at_fer(points, key, target=1e-2):
     return None
 
 
+def _coarse_point(found, lost, true_nu, true_eps):
+    """A point's part of the ``--coarse`` forms: the statistics of the bursts' estimates ``found`` (``coarse_result()`` per burst)
+    against the truth, and the bursts in which the coarse link loses codewords that the reference keeps (``lost``: the running
+    codeword errors after every burst, per link), each with its burst's frequency error."""
+    nu, eps = np.array([f[0] for f in found]) - true_nu, np.array([f[1] for f in found]) - true_eps
+    per_burst = {k: np.diff([0] + v) for k, v in lost.items()}
+    return {"coarse_estimates": {"bursts": len(found), "nu_error_mean": float(nu.mean()), "nu_error_max_abs": float(np.abs(nu).max()),
+                                 "eps_error_mean": float(eps.mean()), "eps_error_max_abs": float(np.abs(eps).max()),
+                                 "peak_over_mean_min": float(min(f[2] / f[3] for f in found))},
+            "coarse_lost_beyond_reference": [{"burst": i, "coarse": int(c), "reference": int(r), "nu_error": float(nu[i])}
+                                             for i, (c, r) in enumerate(zip(per_burst["coarse"], per_burst["reference"])) if c > r]}
+
+
 def main_carrier(args) -> None:
     """The ``--recover`` form: genie, impaired and recovered links on the same blocks (SOQPSK-TG: framed; ARTM, PCM/FM: not)."""
     import math
@@ -192,25 +210,52 @@ def main_carrier(args) -> None:
     links = {"genie": cls(code, per, **kw), "impaired": cls(code, per, carrier=carrier, **kw),
              "recovered": cls(code, per, carrier=carrier, recovery=rec, **kw)}
     sps = links["genie"].sps
+    coarse = None
+    if args.coarse:
+        # the coarse stage in front of the SAME fine recovery, and that recovery at --carrier-freq 0 as the reference curve
+        from waveforms_amd.sync.coarse import CoarseFrequency
+
+        coarse = CoarseFrequency(sps, nfft=args.coarse_nfft, smooth=args.coarse_smooth or None)
+        links["reference"] = cls(code, per, carrier=(carrier[0], 0.0), recovery=rec, **kw)
+        links["coarse"] = cls(code, per, carrier=carrier, recovery=rec, coarse=coarse, **kw)
     out = {"tool": "coded_ber", "form": "carrier", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
            "detector": None if cpm else args.detector, "block_codewords": per, "framed": framed,
            "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
                        "drift_turns_per_window": abs(args.carrier_freq) * sps * rec.window, "documented_limit_turns_per_window": limit},
            "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine}, "points": []}
+    if coarse is not None:
+        out["coarse"] = {"nfft": coarse.nfft, "smooth": coarse.smooth, "search": coarse.search}
     for e in args.ebn0:
         point = {"ebn0_info_db": e}
         b = 0
+        lost, found = {}, []
         for name, lk in links.items():
             lk.reset_counts()
             b = 0
             while b * per < args.codewords:
                 lk.run_block(e, seed=1, stream_id=b)
                 b += 1
+                if name in ("reference", "coarse"):                       # (per burst: these two synchronise after every block)
+                    lost.setdefault(name, []).append(lk.result()[1])
+                    if name == "coarse":
+                        found.append(lk.coarse_result())
             be, fe, nc, m, mean_it = lk.result()
             ue, um = lk.uncoded_result()
             point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
                            "mean_iters": round(mean_it, 3), "uncoded_ber": ue / um, "wrong_locks": None if cpm else lk.sync_result()[1]}
         point["codewords"] = b * per
+        if coarse is not None:
+            point.update(_coarse_point(found, lost, args.carrier_freq, 0.0))
+            lk = links["coarse"]
+            coarse.times, tot = True, {}
+            for s in range(args.steps + 1):
+                lk.front_end(dev.ldpc_encode(code, lk.info_bits(b)), e, 1, b)
+                t = coarse.stage_times()
+                if s:
+                    for k, v in t.items():
+                        tot[k] = tot.get(k, 0.0) + v
+            coarse.times = False
+            point["coarse_ms_per_block"] = {k: round(v / max(args.steps, 1), 4) for k, v in tot.items()}
         # the recovery's stages on one burst, each bracketed by device events, beside one plain soft detection
         lk = links["recovered"]
         rows, _ = lk.front_end(dev.ldpc_encode(code, lk.info_bits(b)), e, 1, b)
@@ -238,6 +283,11 @@ def main_carrier(args) -> None:
     g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
     out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
     out["loss_db_at_fer_1e-2"] = None if g is None or r is None else round(r - g, 3)
+    if coarse is not None:
+        # the coarse stage's cost: the distance between the coarse + fine curve and the same fine recovery at --carrier-freq 0
+        f, c = _ebn0_at_fer(out["points"], "reference"), _ebn0_at_fer(out["points"], "coarse")
+        out["ebn0_at_fer_1e-2"].update({"reference": f, "coarse": c})
+        out["coarse_cost_db_at_fer_1e-2"] = None if f is None or c is None else round(c - f, 3)
     print(json.dumps(out))
 
 
@@ -449,6 +499,16 @@ def main_acquire(args) -> None:
     if args.anchor:                                                       # the anchored curve beside the first acquired one, on the same blocks
         acqs["anchored"] = JointAcquisition(sps, carrier_hypotheses=args.acq_carrier_hyp[0], stack=args.acq_stack or None, anchor=args.anchor, **common)
         links["anchored"] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=acqs["anchored"], **kw)
+    coarse = None
+    if args.coarse:
+        # the coarse stage in front of the SAME acquisition (the anchored one with --anchor), and that acquisition at --carrier-freq 0
+        # under the same timing offset as the reference curve
+        from waveforms_amd.sync.coarse import CoarseFrequency
+
+        coarse = CoarseFrequency(sps, nfft=args.coarse_nfft, smooth=args.coarse_smooth or None)
+        fine = acqs["anchored" if args.anchor else "acquired"]
+        links["reference"] = CodedSOQPSKLink(code, per, carrier=(carrier[0], 0.0), timing=timing, acquisition=fine, **kw)
+        links["coarse"] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=fine, coarse=coarse, **kw)
     W = common["window"]
     out = {"tool": "coded_ber", "form": "acquire", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
            "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
@@ -458,9 +518,14 @@ def main_acquire(args) -> None:
                       "documented_limit_samples_per_window": MAX_DRIFT_SAMPLES},
            "acquisition": {**common, "carrier_hypotheses": args.acq_carrier_hyp, "stack": args.acq_stack or None, "stack_bytes": STACK_BYTES,
                            "anchor": args.anchor}, "points": []}
+    if coarse is not None:
+        # the clock reads the rotated signal: the carrier frequency in cycles per RECEIVED sample is nu (1 + eps)
+        true_nu = args.carrier_freq * (1.0 + args.timing_drift)
+        out["coarse"] = {"nfft": coarse.nfft, "smooth": coarse.smooth, "search": coarse.search, "true_nu_cycles_per_received_sample": true_nu}
     for e in args.ebn0:
         point = {"ebn0_info_db": e}
         b = 0
+        lost, estimates = {}, []
         for name, lk in links.items():
             lk.reset_counts()
             b, rejected = 0, [0, 0]
@@ -469,6 +534,10 @@ def main_acquire(args) -> None:
                 if name == "anchored":
                     found = lk.acquisition_result()[4:]
                     rejected = [rejected[0] + found[1], rejected[1] + found[3]]
+                if name in ("reference", "coarse"):                       # (per burst: these two synchronise after every block)
+                    lost.setdefault(name, []).append(lk.result()[1])
+                    if name == "coarse":
+                        estimates.append(lk.coarse_result())
                 b += 1
             be, fe, nc, m, mean_it = lk.result()
             point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
@@ -476,6 +545,8 @@ def main_acquire(args) -> None:
             if name == "anchored":
                 point[name]["rejected_windows"] = {"timing": rejected[0], "carrier": rejected[1]}
         point["codewords"] = b * per
+        if coarse is not None:
+            point.update(_coarse_point(estimates, lost, true_nu, args.timing_drift))
         out["points"].append(point)
     g = _ebn0_at_fer(out["points"], "genie")
     out["ebn0_at_fer_1e-2"] = {"genie": g}
@@ -484,6 +555,10 @@ def main_acquire(args) -> None:
         r = _ebn0_at_fer(out["points"], name)
         out["ebn0_at_fer_1e-2"][name] = r
         out["loss_db_at_fer_1e-2"][name] = None if g is None or r is None else round(r - g, 3)
+    if coarse is not None:
+        f, c = _ebn0_at_fer(out["points"], "reference"), _ebn0_at_fer(out["points"], "coarse")
+        out["ebn0_at_fer_1e-2"].update({"reference": f, "coarse": c})
+        out["coarse_cost_db_at_fer_1e-2"] = None if f is None or c is None else round(c - f, 3)
     # one acquisition, unstacked (the existing entry points per hypothesis) and stacked, in units of one plain soft detection
     acq_kw = dict(common, carrier_hypotheses=args.acq_carrier_hyp[0])
     stacks = {"stack_1": (1, 0), "stack_default": (args.acq_stack or None, 0)}
@@ -806,6 +881,10 @@ def main() -> None:
     ap.add_argument("--carrier-hyp", type=int, default=0, help="--recover: coarse hypotheses (0: 8 for SOQPSK-TG, the class's 2 for ARTM and PCM/FM)")
     ap.add_argument("--carrier-span", type=int, default=5, help="--recover: windows of the centred mean")
     ap.add_argument("--carrier-refine", type=int, default=1, help="--recover: refinement passes")
+    ap.add_argument("--coarse", action="store_true", help="--recover / --acquire (SOQPSK-TG): also a link with a CoarseFrequency in front of the recovery "
+                    "(of the acquisition: the anchored one with --anchor), and the same one at --carrier-freq 0 as its reference curve")
+    ap.add_argument("--coarse-nfft", type=int, default=4096, help="--coarse: bits per segment of the line periodograms")
+    ap.add_argument("--coarse-smooth", type=int, default=0, help="--coarse: samples of the boxcar in front of the squarer (0: sps // 2)")
     ap.add_argument("--timing-offset", type=float, default=0.0, help="timing offset of the modulated signal, samples")
     ap.add_argument("--timing-drift", type=float, default=0.0, help="timing drift, samples per sample")
     ap.add_argument("--recover-timing", action="store_true", help="genie, impaired and recovered framed links on the same blocks (TimingRecovery)")
@@ -824,6 +903,8 @@ def main() -> None:
     ap.add_argument("--acq-time-rows", type=int, nargs="*", default=[211_252, 10_000_000], help="--acquire: burst lengths one acquisition is timed at (ARTM, PCM/FM: the link's own and 1e6 calls)")
     ap.add_argument("--acq-out", default=str(ROOT / "profiles" / "joint_acquisition.json"), help="--acquire: where the result is also written ('' : nowhere)")
     args = ap.parse_args()
+    if args.coarse and (not (args.recover or args.acquire) or args.waveform != "soqpsk"):
+        ap.error("--coarse goes with --recover or --acquire on --waveform soqpsk (PCM/FM and ARTM have no usable lines)")
     if args.acquire:
         if args.code.startswith("conv") or args.outer or args.live_only or args.recover or args.recover_timing:
             ap.error("--acquire is the framed CodedSOQPSKLink's and CodedCPMLink's: an LDPC code, no --outer / --live-only / --recover / --recover-timing")

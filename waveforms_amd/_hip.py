@@ -147,6 +147,10 @@ SIGNATURES = {
     "wf_carrier_track_anchored": (c_int, [_P, _P, c_int, c_int64, c_int, c_double, c_int, c_double, c_double, _P, _P, _P, _P, _P]),
     "wf_rows_derotate_hyp": (c_int, [_P, _P, c_int64, c_int, c_int64, _P, _P]),
     "wf_viterbi4_soft_branch_segments": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "wf_coarse_scratch_doubles": (c_int64, [c_int64, c_int, c_int, c_int]),
+    "wf_coarse_lines_c128": (c_int, [_P, _P, c_int64, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "wf_coarse_estimate": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P]),
+    "wf_carrier_offset_dev_c128": (c_int, [_P, _P, c_int64, _P, c_double, c_int64, _P, _P]),
     "wf_cpm_mf_rows_resample_c128": (c_int, [_P, _P, c_int64, _P, c_int, c_int, c_int, c_int64, c_int, c_int64, c_int, _P, c_int64, c_double, _P, _P]),
     "wf_cpm_mf_rows_resample_geometry": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64)]),
     "wf_llr_stat": (c_int, [_P, _P, c_int64, c_int, c_int, _P, _P]),

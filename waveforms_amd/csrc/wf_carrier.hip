@@ -29,21 +29,14 @@
 #define CARRIER_THREADS 256
 #define CARRIER_WAVES (CARRIER_THREADS / WF_WAVE)
 #define TRACK_THREADS 1024          // carrier_track_kernel: ONE workgroup, as wide as a workgroup gets (its loops are latency-bound)
-static constexpr double kCarrierTwoPi = 6.28318530717958647692;
+static constexpr double kCarrierTwoPi = kSyncTwoPi;
 static constexpr double kCarrierPi = 3.14159265358979323846;
 
 __global__ __launch_bounds__(CARRIER_THREADS) void carrier_offset_kernel(const double2 *in, int64_t n, double theta0, double nu, int64_t first_index,
                                                                          double2 *out)
 {
     for (int64_t k = (int64_t)blockIdx.x * CARRIER_THREADS + threadIdx.x; k < n; k += (int64_t)gridDim.x * CARRIER_THREADS) {
-        const double t = nu * (double)(first_index + k);     // turns
-        const double fr = t - floor(t);                      // exact
-        const double w = kCarrierTwoPi * fr;
-        const double a = theta0 + w;
-        double sn, cs;
-        sincos(a, &sn, &cs);
-        const double2 z = in[k];
-        out[k] = make_double2(z.x * cs - z.y * sn, z.x * sn + z.y * cs);
+        out[k] = sync_carrier_turn(in[k], theta0, nu, first_index + k);
     }
 }
 

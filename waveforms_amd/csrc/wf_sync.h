@@ -31,6 +31,20 @@ __device__ __forceinline__ double sync_wrap(double x, double period)
     return x - m;
 }
 
+// The carrier impairment of one sample (wf_carrier_offset_c128 and wf_carrier_offset_dev_c128: ONE text, so the two are bitwise
+// each other): z exp(j (theta0 + 2π frac(nu idx))), the turn count reduced to its fraction before the product with 2π
+static constexpr double kSyncTwoPi = 6.28318530717958647692;
+__device__ __forceinline__ double2 sync_carrier_turn(double2 z, double theta0, double nu, int64_t idx)
+{
+    const double t = nu * (double)idx;                   // turns
+    const double fr = t - floor(t);                      // exact
+    const double w = kSyncTwoPi * fr;
+    const double a = theta0 + w;
+    double sn, cs;
+    sincos(a, &sn, &cs);
+    return make_double2(z.x * cs - z.y * sn, z.x * sn + z.y * cs);
+}
+
 // The trajectory's value at row k: traj[nwin] (a phase or an instant per window) interpolated between the centres
 // w W + (W - 1) / 2 of the windows of W rows, flat outside the first and the last (one division: W need not be a power of two)
 __device__ __forceinline__ double sync_traj_at(const double *__restrict__ traj, int64_t nwin, int W, int64_t k)
@@ -138,7 +152,6 @@ __device__ __forceinline__ double2 sync_rotate(double2 z, double cs, double sn)
 // order, takes the first largest, and does the anchor, the re-wrap and the mean.
 #define ANCHOR_THREADS 256      // sync_anchor_score: candidates per workgroup
 #define ANCHOR_MAX_K 1023       // the segment's phasors in LDS: 16 KiB
-static constexpr double kSyncTwoPi = 6.28318530717958647692;
 
 // What both entry points check and lay out: |i| <= n candidates, nseg segments, and the scratch in doubles:
 // z[nwin] (complex) | psi[nwin] | alpha[nwin] | score[nseg][2n + 1]

@@ -2,12 +2,12 @@
 // device: Welch power spectral density (what Axes.psd computes for
 // waveforms/viz/psd.py:36-41), phase-tree traces (waveforms/viz/tree.py:64-70) and eye-diagram
 // traces (waveforms/viz/eye.py:40-55).  No plotting here: the host mirror returns arrays.
-#include "wf_common.h"
+#include "wf_fft.h"
 
 #define VIZ_THREADS 256
-#define VIZ_MAX_LOG2 12          // segments of up to 4096 samples live in LDS (64 KB)
+#define VIZ_MAX_LOG2 FFT_MAX_LOG2
 
-// One workgroup per segment (grid-strided): window, radix-2 decimation-in-time FFT in LDS,
+// One workgroup per segment (grid-strided): window, radix-2 decimation-in-time FFT in LDS (wf_fft.h),
 // |X|^2 accumulated per bin in registers; partial sums per workgroup, reduced in a fixed order by
 // welch_reduce_kernel (no floating-point atomics: the result does not depend on scheduling).
 __global__ __launch_bounds__(VIZ_THREADS) void welch_kernel(const double2 *__restrict__ x, int64_t n, int64_t nseg, int nfft,
@@ -17,11 +17,7 @@ __global__ __launch_bounds__(VIZ_THREADS) void welch_kernel(const double2 *__res
     extern __shared__ __attribute__((aligned(16))) double2 s_buf[];
     double2 *s_tw = s_buf + nfft;
     const int t = threadIdx.x;
-    for (int j = t; j < nfft / 2; j += VIZ_THREADS) {
-        double sn, cs;
-        sincospi(-2.0 * (double)j / (double)nfft, &sn, &cs);
-        s_tw[j] = make_double2(cs, sn);
-    }
+    fft_twiddles<VIZ_THREADS>(s_tw, nfft, t);
     double acc[(1 << VIZ_MAX_LOG2) / VIZ_THREADS];
 #pragma unroll
     for (int q = 0; q < (1 << VIZ_MAX_LOG2) / VIZ_THREADS; ++q) acc[q] = 0.0;
@@ -32,20 +28,9 @@ __global__ __launch_bounds__(VIZ_THREADS) void welch_kernel(const double2 *__res
             double2 v = a < n ? x[a] : make_double2(0.0, 0.0);          // a short signal is zero-padded to one segment
             const double w = window[i];
             v = make_double2(v.x * scale * w, v.y * scale * w);
-            s_buf[__brev((unsigned)i) >> (32 - m)] = v;
+            s_buf[fft_brev(i, m)] = v;
         }
-        for (int s = 1; s <= m; ++s) {
-            __syncthreads();
-            const int half = 1 << (s - 1), tstep = nfft >> s;
-            for (int b = t; b < nfft / 2; b += VIZ_THREADS) {
-                const int pos = b & (half - 1);
-                const int i0 = ((b >> (s - 1)) << s) + pos, i1 = i0 + half;
-                const double2 w = s_tw[pos * tstep], a = s_buf[i0], c = s_buf[i1];
-                const double2 cw = make_double2(fma(c.x, w.x, -c.y * w.y), fma(c.x, w.y, c.y * w.x));
-                s_buf[i0] = make_double2(a.x + cw.x, a.y + cw.y);
-                s_buf[i1] = make_double2(a.x - cw.x, a.y - cw.y);
-            }
-        }
+        fft_stages<VIZ_THREADS>(s_buf, s_tw, nfft, m, t);
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < (1 << VIZ_MAX_LOG2) / VIZ_THREADS; ++q) {

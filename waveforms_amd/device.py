@@ -290,6 +290,73 @@ def carrier_offset(signal, theta0: float, nu: float, first_index: int = 0, out=N
     return out
 
 
+def _samples(name: str, signal) -> int:
+    """n of a sample argument: contiguous device float64[n, 2]."""
+    if signal.dtype != _hip.torch().float64 or not signal.is_contiguous() or signal.numel() % 2 or signal.numel() == 0:
+        raise ValueError(f"{name} must be contiguous float64[n, 2]")
+    return signal.numel() // 2
+
+
+def coarse_lines(received, sps: int, smooth: int, nfft: int, window, out=None, scratch=None, ctx=None):
+    """The periodograms of the two spectral lines of the squared SOQPSK-TG signal (``wf_coarse_lines_c128``; include/wfhip.h states
+    the definition) -> device float64[2, nfft] = (P₋, P₊) in fftshift order.  ``received``: contiguous device float64[n, 2];
+    ``window``: contiguous device float64[nfft]; ``scratch``: a contiguous device float64 tensor of at least
+    ``wf_coarse_scratch_doubles`` values to reuse (None: a new one per call).  A burst that does not fill one segment of ``nfft``
+    bits is a ValueError."""
+    torch = _hip.torch()
+    n = _samples("received", received)
+    if window.dtype != torch.float64 or not window.is_contiguous() or window.numel() != int(nfft):
+        raise ValueError(f"window must be contiguous float64[{int(nfft)}]")
+    words = _hip.lib().wf_coarse_scratch_doubles(n, int(sps), int(nfft), int(smooth))
+    if words < 1:
+        raise ValueError(f"coarse_lines: {n} samples at sps = {sps}, smooth = {smooth} do not fill one segment of nfft = {nfft} bits, or an "
+                         "argument is out of range (sps 2 .. 64, smooth 1 .. 1024, nfft a power of two from 64 to 4096)")
+    if out is None:
+        out = _hip.empty((2, int(nfft)), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 2 * int(nfft):
+        raise ValueError(f"out must be contiguous float64[2, {int(nfft)}]")
+    if scratch is None:
+        scratch = _hip.empty(words, "float64")
+    elif scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.numel() < words:
+        raise ValueError(f"scratch must be a contiguous float64 tensor of at least {words} values")
+    _hip.check(_hip.lib().wf_coarse_lines_c128(_ctx(ctx), _hip.ptr(received), n, int(sps), int(smooth), int(nfft), _hip.ptr(window),
+                                               _hip.ptr(scratch), _hip.ptr(out), _hip.stream()))
+    return out
+
+
+def coarse_estimate(spectra, sps: int, search: int, out=None, ctx=None):
+    """The carrier frequency from the two line periodograms (``wf_coarse_estimate``; include/wfhip.h states the definition) ->
+    device float64[4] = (nu in cycles per sample, eps, the peak of the summed periodogram, its mean).  ``spectra``: contiguous
+    device float64[2, nfft]."""
+    torch = _hip.torch()
+    if spectra.dtype != torch.float64 or not spectra.is_contiguous() or spectra.dim() != 2 or spectra.shape[0] != 2:
+        raise ValueError("spectra must be contiguous float64[2, nfft]")
+    if out is None:
+        out = _hip.empty(4, "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != 4:
+        raise ValueError("out must be contiguous float64[4]")
+    _hip.check(_hip.lib().wf_coarse_estimate(_ctx(ctx), _hip.ptr(spectra), int(spectra.shape[1]), int(sps), int(search), _hip.ptr(out),
+                                             _hip.stream()))
+    return out
+
+
+def carrier_offset_dev(signal, nu, gain: float = 1.0, first_index: int = 0, out=None, ctx=None):
+    """``carrier_offset`` with theta0 = 0 and the frequency ``gain`` * nu[0] read from device memory (``wf_carrier_offset_dev_c128``):
+    bitwise ``carrier_offset(signal, 0.0, gain * nu)`` for the same value, with nothing brought to the host.  ``nu``: a contiguous
+    device float64 tensor (its first value is read: ``coarse_estimate``'s output as it is); ``out=signal`` works in place."""
+    torch = _hip.torch()
+    n = _samples("signal", signal)
+    if nu.dtype != torch.float64 or not nu.is_contiguous() or nu.numel() < 1:
+        raise ValueError("nu must be a contiguous float64 tensor of at least one value")
+    if out is None:
+        out = _hip.empty((n, 2), "float64")
+    elif out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != signal.numel():
+        raise ValueError("out must be contiguous float64[n, 2]")
+    _hip.check(_hip.lib().wf_carrier_offset_dev_c128(_ctx(ctx), _hip.ptr(signal), n, _hip.ptr(nu), float(gain), int(first_index), _hip.ptr(out),
+                                                     _hip.stream()))
+    return out
+
+
 def viterbi_soft_branch(rows, differential: bool = True, warmup: int = 0, ctx=None):
     """``viterbi_soft`` on 48-byte rows with the decided branch of every row (``wf_viterbi4_soft_branch``; include/wfhip.h
     states the definition) -> (llr f64[ncalls], bits u8[ncalls], branch u8[ncalls]) on device.  llr and bits are bitwise

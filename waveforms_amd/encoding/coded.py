@@ -42,6 +42,15 @@ order is ``carrier_offset``, then ``timing_offset``, then the channel).  It need
 (sps, π/2) and (0, π): the rows may be a few rows early or late, and inverted) and excludes ``recovery`` and
 ``timing_recovery``.  Default None: the same calls as before.
 
+``CodedSOQPSKLink`` and ``IterativeSOQPSKLink`` also take ``coarse``, a :class:`waveforms_amd.sync.coarse.CoarseFrequency` that
+takes a carrier frequency offset far outside the fine recoveries' pull-in range off the noisy samples before anything else reads
+them: beside ``recovery`` the front end becomes ``awgn`` -> ``coarse.correct`` -> ``mf_bank`` -> ``recovery`` (the fused
+``awgn_mf_bank`` is used only without it), beside ``acquisition`` it becomes ``awgn`` -> ``coarse.correct`` ->
+``acquisition.recover``.  It needs one of the two (the residual phase is unknown), excludes ``timing_recovery`` (that path excludes
+a carrier) and must be for the link's sps.  Default None: the same calls as before.  On the CPM classes ``coarse`` stays a
+TypeError: PCM/FM and ARTM have no usable spectral lines of this kind (their 10th to 32nd power lines drown in the noise at any
+useful Eb/N0) and need another estimator.
+
 The two CPM classes take ``clock=(tau0, eps)``, the same impairment behind the carrier offset and in front of the channel, and
 ``clock_recovery``, a :class:`waveforms_amd.sync.timing_cpm.CPMTimingRecovery` that makes the rows from the noisy samples in
 place of ``cpm_mf_rows``.  (The names are not ``timing`` / ``timing_recovery``: those stay a TypeError on the CPM classes, and a
@@ -193,6 +202,31 @@ class _Framed:
         if self.acquisition is None or self._acq is None:
             raise RuntimeError("acquisition_result needs an acquisition and a block that ran")
         return tuple(_hip.to_host(v) for v in self._acq) + self._found(self.acquisition.timing_found, self.acquisition.carrier_found)
+
+    def _coarse_init(self, coarse, sps: int, recovery, timing_recovery, acquisition) -> None:
+        """``coarse``: a ``waveforms_amd.sync.coarse.CoarseFrequency`` that estimates the carrier frequency of the noisy samples and
+        takes it off in front of ``recovery``'s matched filters or of ``acquisition``.  None: nothing is added to the chain.
+        Checked against the link's other keywords before anything touches the device."""
+        if coarse is not None:
+            from ..sync.coarse import CoarseFrequency
+
+            if not isinstance(coarse, CoarseFrequency):
+                raise ValueError("coarse is a waveforms_amd.sync.coarse.CoarseFrequency")
+            if timing_recovery is not None:
+                raise ValueError("coarse excludes timing_recovery: that path has no carrier recovery behind it")
+            if recovery is None and acquisition is None:
+                raise ValueError("coarse needs a recovery or an acquisition: it leaves the residual frequency and the phase to them")
+            if coarse.sps != sps:
+                raise ValueError(f"the coarse acquisition is for sps = {coarse.sps}, the link has {sps}")
+        self.coarse = coarse
+        self._coarse_found = None
+
+    def coarse_result(self):
+        """(nu in cycles per sample, eps, the peak of the summed line periodogram, its mean) of the last block's coarse
+        acquisition, as floats - synchronises."""
+        if self.coarse is None or self._coarse_found is None:
+            raise RuntimeError("coarse_result needs a coarse acquisition and a block that ran")
+        return tuple(float(v) for v in _hip.to_host(self._coarse_found))
 
     def _clock_init(self, clock, clock_recovery, spec, sps: int, framing, carrier, recovery) -> None:
         """``clock=(tau0, eps)`` and ``clock_recovery`` of the CPM links: ``_timing_init``'s pair for the generic CPM trellis, with
@@ -386,12 +420,14 @@ class _SOQPSK(_Link):
 
     bits_per_symbol, _lam0 = 1, 1
 
-    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", *, timing=None, timing_recovery=None, acquisition=None, **burst) -> None:
+    def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", *, timing=None, timing_recovery=None, acquisition=None, coarse=None,
+                 **burst) -> None:
         if detector not in TIMING_OFFSET:
             raise ValueError(f"unknown detector {detector!r}")
         self.detector = detector
         self._timing_init(timing, timing_recovery, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
         self._acquisition_init(acquisition, int(sps), burst.get("framing"), burst.get("recovery"), timing_recovery)
+        self._coarse_init(coarse, int(sps), burst.get("recovery"), timing_recovery, acquisition)
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -426,8 +462,12 @@ class _SOQPSK(_Link):
             received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
             rows, self._timing_tau, self._timing_choice = self.timing_recovery.recover(received, self._d_taps, first, ncols, True)
             return rows, syms
-        if self.acquisition is not None:
+        if self.acquisition is not None or self.coarse is not None:
             received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
+            if self.coarse is not None:
+                received, self._coarse_found = self.coarse.correct(received, out=received)
+            if self.acquisition is None:                                   # (coarse beside recovery: the plain bank on the corrected samples)
+                return dev.mf_bank(received, self._d_taps, first, self.sps, ncols), syms
             rows, *self._acq = self.acquisition.recover(received, self._d_taps, first, ncols, True)
             return rows, syms
         rows = dev.awgn_mf_bank(sig, self._d_taps, first, self.sps, ncols, self.sigma(ebn0_db), seed, stream_id, 0,
@@ -603,10 +643,10 @@ class CodedSOQPSKLink(_LDPC, _SOQPSK):
     is paired with the soft detector's λ_{j+1} (include/wfhip.h, wf_viterbi4_soft).  ``ebn0_db=None`` is noiseless."""
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, max_iter: int = 50, framing=None,
-                 lead_bits: int = 0, carrier=None, recovery=None, timing=None, timing_recovery=None, acquisition=None) -> None:
+                 lead_bits: int = 0, carrier=None, recovery=None, timing=None, timing_recovery=None, acquisition=None, coarse=None) -> None:
         self.alpha, self.max_iter = float(alpha), int(max_iter)
-        super().__init__(code, ncw, sps, detector, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition, framing=framing,
-                         lead_bits=lead_bits, carrier=carrier, recovery=recovery)
+        super().__init__(code, ncw, sps, detector, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition, coarse=coarse,
+                         framing=framing, lead_bits=lead_bits, carrier=carrier, recovery=recovery)
 
 
 class CodedCPMLink(_LDPC, _CPM):
@@ -738,13 +778,13 @@ class IterativeSOQPSKLink(_LDPCLoop, CodedSOQPSKLink):
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", alpha: float = 0.75, outer: int = 8, inner: int = 5,
                  damping: float = 0.7, ext_clip: float | None = None, ext_sat: float | None = None, per_pass: bool = False, framing=None,
                  lead_bits: int = 0, marker_prior: float | None = None, live_only: bool = False, guard: int = DEFAULT_GUARD, carrier=None,
-                 recovery=None, timing=None, timing_recovery=None, acquisition=None) -> None:
+                 recovery=None, timing=None, timing_recovery=None, acquisition=None, coarse=None) -> None:
         if int(guard) < 0:
             raise ValueError(f"guard = {guard} must not be negative")
         self.live_only, self.guard = bool(live_only), int(guard)
         super().__init__(code, ncw, sps=sps, detector=detector, alpha=alpha, outer=outer, inner=inner, damping=damping, ext_clip=ext_clip,
                          ext_sat=ext_sat, per_pass=per_pass, framing=framing, lead_bits=lead_bits, marker_prior=marker_prior, carrier=carrier,
-                         recovery=recovery, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition)
+                         recovery=recovery, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition, coarse=coarse)
         self.live_counts = _hip.zeros((self.outer, 3), "int64") if self.live_only else None
         self.windows = _hip.zeros(4 + 2 * self.ncw, "int64") if self.live_only else None
         self._live_out, self._live_first = None, 0          # the block's ext / bits buffers; first passes run
