@@ -5,10 +5,11 @@ and ``CPMLink`` are not used and not changed.
 
 A link class is a waveform, a code and a kind of loop, each stated once:
 
-    ``_Framed``   the burst around the codewords: sync marker, randomiser, frame search; carrier offset and recovery
+    ``_Framed``   the burst around the codewords: sync marker, randomiser, frame search; the synchroniser slots and their results
     ``_Link``     what every link does: PN23 information bits, ``channel_llrs`` through the ``encode`` hook, the counters, the
-                  view of the detector's output as codewords (``_coded``) and of the prior buffer (``_prior_coded``), ``detect``
-    ``_SOQPSK``   SOQPSK-TG: pad, tables, PT / PAM front end, ``viterbi_soft`` (``_apriori``), the uncoded count, λ offset 1
+                  view of the detector's output as codewords (``_coded``) and of the prior buffer (``_prior_coded``), ``detect``,
+                  and the front end: modulated signal -> impairments -> noisy samples (``samples``) -> rows
+    ``_SOQPSK``   SOQPSK-TG: pad, tables, PT / PAM bank, ``viterbi_soft`` (``_apriori``), the uncoded count, λ offset 1
     ``_CPM``      ARTM multi-h and PCM/FM on the generic CPM trellis: the same list with ``cpm_soft`` (``_apriori``), λ offset 0
     ``_LDPC``     one ``ldpc_decode`` per block: ``CodedSOQPSKLink`` = ``_LDPC`` on ``_SOQPSK``, ``CodedCPMLink`` = ``_LDPC`` on ``_CPM``
     ``_LDPCLoop`` the loop with frozen codewords: ``IterativeSOQPSKLink`` (adds ``live_only``), ``IterativeCPMLink`` (``prior_warmup``)
@@ -22,51 +23,48 @@ codewords itself: ``frame_search`` over the whole burst's λ, ``frame_gather`` i
 ``frame_scatter`` of the decoder's extrinsic output (and the marker as a known-bits prior) back into the detector's prior
 buffer (``_Framed``).  With ``framing=None`` every class does exactly what it did without the keyword.
 
-The two SOQPSK-TG classes also take ``carrier=(theta0, nu)``, a carrier phase and frequency offset applied to the modulated
-signal (``carrier_offset``), and ``recovery``, a :class:`waveforms_amd.sync.carrier.CarrierRecovery` the rows pass through in
-front of the detector; ``recovery`` needs a ``framing`` (the phase comes back modulo π).  Both default to None: the same calls
-as before.  The two CPM classes take the same pair with a :class:`waveforms_amd.sync.carrier_cpm.CPMCarrierRecovery`, which
-needs no framing: the phase comes back modulo 2π/p, a rotation that relabels the trellis's phase states and leaves the data
-alone.  Either class refuses the other's recovery.
+They also take two impairments of the modulated signal, applied in this order in front of the unchanged channel, and the
+synchronisers that undo them.  Every keyword defaults to None: the same calls as without it.
 
-The two SOQPSK-TG classes also take ``timing=(tau0, eps)``, a symbol timing offset and drift in samples applied to the modulated
-signal (``timing_offset``: the signal read at n + tau0 + eps n) in front of the unchanged channel, and ``timing_recovery``, a
-:class:`waveforms_amd.sync.timing.TimingRecovery`: the noisy samples are then materialised (``awgn``, the same rotation and the
-same noise coordinates as the fused front end's) and the recovery makes the detector's rows from them.  It needs a ``framing``
-(the instant comes back modulo two symbols: the rows may be two early or late) and excludes ``carrier`` and ``recovery``.  Both
-default to None: the same calls as before.
+    ``carrier=(theta0, nu)``   all four: rotated by theta0 + 2π nu k (``carrier_offset``, in place; nu in cycles per sample)
+    ``timing=(tau0, eps)``     SOQPSK-TG: read at n + tau0 + eps n (``timing_offset``; symbol timing offset and drift, in samples)
+    ``clock=(tau0, eps)``      CPM: the same impairment
 
-``CodedSOQPSKLink`` and ``IterativeSOQPSKLink`` also take ``acquisition``, a :class:`waveforms_amd.sync.joint.JointAcquisition`
-that makes the rows from the noisy samples under BOTH impairments (``carrier=`` and ``timing=`` may be given beside it; the
-order is ``carrier_offset``, then ``timing_offset``, then the channel).  It needs a ``framing`` (the pair comes back modulo
-(sps, π/2) and (0, π): the rows may be a few rows early or late, and inverted) and excludes ``recovery`` and
-``timing_recovery``.  Default None: the same calls as before.
+A synchroniser sits at one of three places: it corrects the noisy samples, makes the detector's rows from them in place of the
+plain bank, or turns the bank's rows in front of the detector.  As soon as one reads samples they are materialised (``awgn``,
+the same rotation and the same noise coordinates as the fused front end's); SOQPSK-TG's fused ``awgn_mf_bank`` is used only
+when none does.  Each must be built for the link's sps (the CPM ones for its design too; ``CarrierRecovery`` has no sps), and
+one that leaves the rows shifted needs a ``framing`` whose search absorbs what it leaves open.  ``_SOQPSK._slots`` and
+``_CPM._slots`` state the same as data.
 
-``CodedSOQPSKLink`` and ``IterativeSOQPSKLink`` also take ``coarse``, a :class:`waveforms_amd.sync.coarse.CoarseFrequency` that
+    keyword, waveform             class under waveforms_amd.sync     place     excludes                   comes back modulo
+    ``recovery``         SOQPSK   carrier.CarrierRecovery            turns     -                          π: framing (its polarity)
+    ``recovery``         CPM      carrier_cpm.CPMCarrierRecovery     turns     -                          2π/p: no framing needed
+    ``timing_recovery``  SOQPSK   timing.TimingRecovery              rows      carrier, recovery          two symbols: framing
+    ``acquisition``      SOQPSK   joint.JointAcquisition             rows      recovery, timing_recovery  (sps, π/2) and (0, π): framing
+    ``coarse``           SOQPSK   coarse.CoarseFrequency             samples   timing_recovery            - (needs recovery or acquisition)
+    ``clock_recovery``   CPM      timing_cpm.CPMTimingRecovery       rows      carrier, recovery          nh symbols: framing
+    ``joint``            CPM      joint_cpm.CPMJointAcquisition      rows      recovery, clock_recovery   (nh sps, P/2) and (0, P): framing
+
+``recovery``: 2π/p is a rotation that relabels the trellis's phase states and leaves the data alone.  Either waveform refuses
+the other's recovery.  ``timing_recovery``: the rows may be two early or late.  ``acquisition`` / ``joint`` work under BOTH
+impairments (``carrier=`` and ``timing=`` / ``clock=`` may be given beside them); the SOQPSK-TG rows may be a few rows early or
+late, and inverted, the CPM rows a whole number of periods of nh symbols early or late, as ``clock_recovery``'s.  ``coarse``
 takes a carrier frequency offset far outside the fine recoveries' pull-in range off the noisy samples before anything else reads
-them: beside ``recovery`` the front end becomes ``awgn`` -> ``coarse.correct`` -> ``mf_bank`` -> ``recovery`` (the fused
-``awgn_mf_bank`` is used only without it), beside ``acquisition`` it becomes ``awgn`` -> ``coarse.correct`` ->
-``acquisition.recover``.  It needs one of the two (the residual phase is unknown), excludes ``timing_recovery`` (that path excludes
-a carrier) and must be for the link's sps.  Default None: the same calls as before.  On the CPM classes ``coarse`` stays a
-TypeError: PCM/FM and ARTM have no usable spectral lines of this kind (their 10th to 32nd power lines drown in the noise at any
-useful Eb/N0) and need another estimator.
+them: beside ``recovery`` the front end becomes ``awgn`` -> ``coarse.correct`` -> ``mf_bank`` -> ``recovery``, beside
+``acquisition`` it becomes ``awgn`` -> ``coarse.correct`` -> ``acquisition.recover``.  It needs one of the two (the residual phase
+is unknown) and excludes ``timing_recovery`` (that path excludes a carrier).
 
-The two CPM classes take ``clock=(tau0, eps)``, the same impairment behind the carrier offset and in front of the channel, and
-``clock_recovery``, a :class:`waveforms_amd.sync.timing_cpm.CPMTimingRecovery` that makes the rows from the noisy samples in
-place of ``cpm_mf_rows``.  (The names are not ``timing`` / ``timing_recovery``: those stay a TypeError on the CPM classes, and a
-``TimingRecovery`` passed as ``clock_recovery`` is refused.)  ``clock_recovery`` needs a ``framing`` (the rows come back shifted
-by a whole number of periods of nh symbols, which the frame search absorbs), excludes ``carrier`` and ``recovery`` and must be
-for the link's design and sps.  Both default to None: the same calls as before.
-
-``CodedCPMLink`` and ``IterativeCPMLink`` also take ``joint``, a :class:`waveforms_amd.sync.joint_cpm.CPMJointAcquisition` that
-makes the rows from the noisy samples under BOTH impairments (``carrier=`` and ``clock=`` may be given beside it).  (The name is
-not ``acquisition``: that stays a TypeError on the CPM classes.)  It needs a ``framing`` (the pair comes back modulo the lattice
-of (nh sps, P/2) and (0, P): the rows may be a whole number of periods early or late), excludes ``recovery`` and
-``clock_recovery`` and must be for the link's design and sps.  Default None: the same calls as before.
+A keyword of the other waveform is a TypeError.  That is why the CPM names are ``clock`` / ``clock_recovery`` and ``joint``, not
+``timing`` / ``timing_recovery`` and ``acquisition`` (and a ``TimingRecovery`` passed as ``clock_recovery`` is refused).  ``coarse``
+stays a TypeError on the CPM classes: PCM/FM and ARTM have no usable spectral lines of this kind (their 10th to 32nd power lines
+drown in the noise at any useful Eb/N0) and need another estimator.
 """
 from __future__ import annotations
 
+import importlib
 import math
+from typing import NamedTuple
 
 import numpy as np
 
@@ -83,6 +81,42 @@ TIMING_OFFSET = {"PT": -1, "PAM": 0}      # SOQPSK-TG (examples/soqpsk_detection
 PAD_BITS = 16                             # tail after the burst's last codeword: every coded bit gets its λ
 PAD_SYMS = 8                              # CPM chains: zero symbols after the burst's last codeword
 CPM_WAVEFORMS = {"multih": 1, "pcmfm": 2}  # -> symbol_map kind (the reference's natural-binary mappers)
+DEROTATION = np.exp(-1j * np.pi / 4)      # of the channel's output, in ``awgn`` and in the fused ``awgn_mf_bank``
+
+
+class _Slot(NamedTuple):
+    """One synchroniser keyword of a waveform's links (``_SOQPSK._slots``, ``_CPM._slots``): what ``_sync_init`` checks, in this
+    order, where ``front_end`` puts it and what its ``*_result`` hands back."""
+
+    name: str                     # the keyword and the attribute
+    a: str                        # "<name>_result needs <a> and a block that ran"
+    noun: str                     # what the refusals call it
+    stage: str                    # "samples": corrects the noisy samples; "rows": makes the rows from them; "turns": turns the bank's rows
+    returns: tuple                # what recover / correct returns beyond the rows (the samples), by ``_HOST``
+    found: tuple = ()             # which of timing_found / carrier_found the result appends
+    cls: str | None = None        # module.Class under waveforms_amd.sync, imported when the keyword is used; None: ``_check_recovery``
+    excludes: tuple = ()          # keywords it cannot stand beside,
+    why: str = ""                 # and why
+    needs: tuple = ()             # the keywords one of which it needs beside it,
+    needs_what: str = ""          # and the refusal's words for them and for why
+    design: bool = False          # built for the link's design (``spec``) beside its sps
+    framing: str | None = None    # why it needs a framing: what comes back modulo what
+    shifted: str | None = None    # how it leaves the rows, where that keeps the channel bits from being counted (``uncoded_result``'s words)
+
+
+_HOST = {"array": lambda t: (_hip.to_host(t),), "int": lambda t: (int(t.cpu()),), "floats": lambda t: tuple(float(v) for v in _hip.to_host(t))}
+_ACQUIRES = "it recovers the carrier and the timing itself"
+_NOT_JOINT = "joint timing and carrier acquisition is not implemented"
+
+
+def _pair(name: str, parts: str, value):
+    """An impairment ``name=(a, b)`` as two finite floats, or None."""
+    if value is None:
+        return None
+    a, b = (float(v) for v in value)
+    if not (math.isfinite(a) and math.isfinite(b)):
+        raise ValueError(f"{name} = ({parts}) must be finite")
+    return a, b
 
 
 class _Framed:
@@ -109,19 +143,34 @@ class _Framed:
         self._true_lock = _hip.to_device(np.array([self.lead_bits, 1], dtype=np.int64))
         self._llr_in = _hip.empty((self.ncw, self.code.n_tx), "float64")
 
-    def _carrier_init(self, carrier, recovery) -> None:
-        """``carrier=(theta0, nu)``: the modulated signal is rotated by theta0 + 2π nu k (``carrier_offset``, nu in cycles per
-        sample) in front of the unchanged channel; ``recovery``: a ``waveforms_amd.sync.carrier.CarrierRecovery`` the rows pass
-        through before the detector.  Both None: nothing is added to the chain."""
-        if carrier is not None:
-            theta0, nu = (float(v) for v in carrier)
-            if not (math.isfinite(theta0) and math.isfinite(nu)):
-                raise ValueError("carrier = (theta0, nu) must be finite")
-            carrier = (theta0, nu)
-        if recovery is not None:
-            self._check_recovery(recovery)
-        self.carrier, self.recovery = carrier, recovery
-        self._carrier_phase = self._carrier_choice = None
+    def _sync_init(self, sps: int, given: dict) -> None:
+        """The waveform's own keywords out of ``given`` (every keyword of the constructor by name), checked in the order of
+        ``_slots`` before anything touches the device: the timing impairment ``_drift``, then per slot the class, what it excludes,
+        what it needs, the link's design and sps, the framing.  ``recovery`` is not checked here: ``_Link.__init__`` does that
+        behind the framing (``_check_recovery``).  Nothing is left of a last block."""
+        setattr(self, self._drift, _pair(self._drift, "tau0, eps", given[self._drift]))
+        for slot in (s for s in self._slots if s.cls):
+            sync = given[slot.name]
+            if sync is not None:
+                module, cls = slot.cls.split(".")
+                if not isinstance(sync, getattr(importlib.import_module(f"..sync.{module}", __package__), cls)):
+                    raise ValueError(f"{slot.name} is a waveforms_amd.sync.{slot.cls}")
+                if any(given.get(k) is not None for k in slot.excludes):
+                    raise ValueError(f"{slot.name} excludes {' and '.join(slot.excludes)}: {slot.why}")
+                if slot.needs and all(given.get(k) is None for k in slot.needs):
+                    raise ValueError(f"{slot.name} needs {slot.needs_what}")
+                if slot.design and sync.spec != self.spec:
+                    raise ValueError(f"the {slot.noun} is for another design than the link's full-phase trellis")
+                if sync.sps != sps:
+                    raise ValueError(f"the {slot.noun} is for sps = {sync.sps}, the link has {sps}")
+                if slot.framing and given.get("framing") is None:
+                    raise ValueError(f"{slot.name} needs a framing: {slot.framing}")
+            setattr(self, slot.name, sync)
+        used = [s for s in self._slots if s.cls and getattr(self, s.name) is not None]
+        self._correctors = [s for s in used if s.stage == "samples"]
+        self._row_maker = next((s for s in used if s.stage == "rows"), None)     # (at most one: they exclude each other)
+        self._shifts = next((s for s in used if s.shifted), None)
+        self._sync_last = {}                                                           # slot name -> what its last recover / correct returned
 
     @staticmethod
     def _found(*found):
@@ -129,157 +178,45 @@ class _Framed:
         (the drift in the tracker's unit per window, the number of rejected windows); nothing without an anchor."""
         return tuple(v for f in found if f is not None for v in (float(f[0].cpu()), int(f[1].sum().cpu())))
 
+    def _sync_result(self, name: str, asked: str):
+        """What the slot ``name`` left of the last block, on the host, plus what its anchored tracks found; a synchroniser and a
+        block that ran, else RuntimeError."""
+        sync = getattr(self, name)
+        slot = next(s for s in self._slots if s.name == name)
+        last = None if sync is None else self._sync_last.get(name)
+        if last is None:
+            raise RuntimeError(f"{asked} needs {slot.a} and a block that ran")
+        return tuple(v for kind, t in zip(slot.returns, last) for v in _HOST[kind](t)) + self._found(*(getattr(sync, f) for f in slot.found))
+
     def carrier_result(self):
         """(phase float64[nwin] in radians, modulo π - modulo 2π/p on the CPM links; choice uint8[nwin]) of the last block's
         recovery - synchronises.  A recovery with an ``anchor`` adds (the drift found in radians per window, the number of
         rejected windows) of its coarse track."""
-        if self.recovery is None or self._carrier_phase is None:
-            raise RuntimeError("carrier_result needs a recovery and a block that ran")
-        return (_hip.to_host(self._carrier_phase), _hip.to_host(self._carrier_choice)) + self._found(self.recovery.carrier_found)
-
-    def _recovered(self, rows):
-        if self.recovery is None:
-            return rows
-        rows, self._carrier_phase, self._carrier_choice = self._recover(rows)
-        return rows
-
-    def _timing_init(self, timing, timing_recovery, sps: int, framing, carrier, recovery) -> None:
-        """``timing=(tau0, eps)``: the modulated signal is read at n + tau0 + eps n (``timing_offset``, in samples) in front of the
-        unchanged channel; ``timing_recovery``: a ``waveforms_amd.sync.timing.TimingRecovery`` that makes the detector's rows from
-        the noisy samples.  Both None: nothing is added to the chain.  Checked against the link's other keywords before anything
-        touches the device."""
-        if timing is not None:
-            tau0, eps = (float(v) for v in timing)
-            if not (math.isfinite(tau0) and math.isfinite(eps)):
-                raise ValueError("timing = (tau0, eps) must be finite")
-            timing = (tau0, eps)
-        if timing_recovery is not None:
-            from ..sync.timing import TimingRecovery
-
-            if not isinstance(timing_recovery, TimingRecovery):
-                raise ValueError("timing_recovery is a waveforms_amd.sync.timing.TimingRecovery")
-            if recovery is not None or carrier is not None:
-                raise ValueError("timing_recovery excludes carrier and recovery: joint timing and carrier acquisition is not implemented")
-            if timing_recovery.sps != sps:
-                raise ValueError(f"the timing recovery is for sps = {timing_recovery.sps}, the link has {sps}")
-            if framing is None:
-                raise ValueError("timing_recovery needs a framing: the instant is recovered modulo two symbols and the frame search absorbs the shift")
-        self.timing, self.timing_recovery = timing, timing_recovery
-        self._timing_tau = self._timing_choice = None
+        return self._sync_result("recovery", "carrier_result")
 
     def timing_result(self):
         """(tau float64[nwin] in samples, modulo two symbols; choice uint8[nwin]) of the last block's timing recovery -
         synchronises.  A recovery with an ``anchor`` adds (the drift found in samples per window, the number of rejected windows)
         of its coarse track."""
-        if self.timing_recovery is None or self._timing_tau is None:
-            raise RuntimeError("timing_result needs a timing_recovery and a block that ran")
-        return (_hip.to_host(self._timing_tau), _hip.to_host(self._timing_choice)) + self._found(self.timing_recovery.timing_found)
-
-    def _acquisition_init(self, acquisition, sps: int, framing, recovery, timing_recovery) -> None:
-        """``acquisition``: a ``waveforms_amd.sync.joint.JointAcquisition`` that makes the detector's rows from the noisy samples
-        under a carrier AND a timing offset (``carrier=`` and ``timing=`` may both be given beside it).  None: nothing is added to
-        the chain.  Checked against the link's other keywords before anything touches the device."""
-        if acquisition is not None:
-            from ..sync.joint import JointAcquisition
-
-            if not isinstance(acquisition, JointAcquisition):
-                raise ValueError("acquisition is a waveforms_amd.sync.joint.JointAcquisition")
-            if recovery is not None or timing_recovery is not None:
-                raise ValueError("acquisition excludes recovery and timing_recovery: it recovers the carrier and the timing itself")
-            if acquisition.sps != sps:
-                raise ValueError(f"the acquisition is for sps = {acquisition.sps}, the link has {sps}")
-            if framing is None:
-                raise ValueError("acquisition needs a framing: the instant and the phase are recovered modulo (sps, π/2) and (0, π), "
-                                 "and the frame search absorbs the shift and the polarity")
-        self.acquisition = acquisition
-        self._acq = None
+        return self._sync_result("timing_recovery", "timing_result")
 
     def acquisition_result(self):
         """(tau float64[nwin] in samples, phase float64[nwin] in radians - both modulo the lattice of waveforms_amd/sync/joint.py;
         timing choice uint8[nwin]; carrier choice uint8[nwin]) of the last block's acquisition - synchronises.  An acquisition with
         an ``anchor`` adds (the timing drift found in samples per window, the rejected windows of the coarse timing track, the carrier
         drift found in radians per window, the rejected windows of the coarse carrier track)."""
-        if self.acquisition is None or self._acq is None:
-            raise RuntimeError("acquisition_result needs an acquisition and a block that ran")
-        return tuple(_hip.to_host(v) for v in self._acq) + self._found(self.acquisition.timing_found, self.acquisition.carrier_found)
-
-    def _coarse_init(self, coarse, sps: int, recovery, timing_recovery, acquisition) -> None:
-        """``coarse``: a ``waveforms_amd.sync.coarse.CoarseFrequency`` that estimates the carrier frequency of the noisy samples and
-        takes it off in front of ``recovery``'s matched filters or of ``acquisition``.  None: nothing is added to the chain.
-        Checked against the link's other keywords before anything touches the device."""
-        if coarse is not None:
-            from ..sync.coarse import CoarseFrequency
-
-            if not isinstance(coarse, CoarseFrequency):
-                raise ValueError("coarse is a waveforms_amd.sync.coarse.CoarseFrequency")
-            if timing_recovery is not None:
-                raise ValueError("coarse excludes timing_recovery: that path has no carrier recovery behind it")
-            if recovery is None and acquisition is None:
-                raise ValueError("coarse needs a recovery or an acquisition: it leaves the residual frequency and the phase to them")
-            if coarse.sps != sps:
-                raise ValueError(f"the coarse acquisition is for sps = {coarse.sps}, the link has {sps}")
-        self.coarse = coarse
-        self._coarse_found = None
+        return self._sync_result("acquisition", "acquisition_result")
 
     def coarse_result(self):
         """(nu in cycles per sample, eps, the peak of the summed line periodogram, its mean) of the last block's coarse
         acquisition, as floats - synchronises."""
-        if self.coarse is None or self._coarse_found is None:
-            raise RuntimeError("coarse_result needs a coarse acquisition and a block that ran")
-        return tuple(float(v) for v in _hip.to_host(self._coarse_found))
-
-    def _clock_init(self, clock, clock_recovery, spec, sps: int, framing, carrier, recovery) -> None:
-        """``clock=(tau0, eps)`` and ``clock_recovery`` of the CPM links: ``_timing_init``'s pair for the generic CPM trellis, with
-        a ``waveforms_amd.sync.timing_cpm.CPMTimingRecovery``.  Checked before anything touches the device."""
-        if clock is not None:
-            tau0, eps = (float(v) for v in clock)
-            if not (math.isfinite(tau0) and math.isfinite(eps)):
-                raise ValueError("clock = (tau0, eps) must be finite")
-            clock = (tau0, eps)
-        if clock_recovery is not None:
-            from ..sync.timing_cpm import CPMTimingRecovery
-
-            if not isinstance(clock_recovery, CPMTimingRecovery):
-                raise ValueError("clock_recovery is a waveforms_amd.sync.timing_cpm.CPMTimingRecovery")
-            if recovery is not None or carrier is not None:
-                raise ValueError("clock_recovery excludes carrier and recovery: joint timing and carrier acquisition is not implemented")
-            if clock_recovery.spec != spec:
-                raise ValueError("the clock recovery is for another design than the link's full-phase trellis")
-            if clock_recovery.sps != sps:
-                raise ValueError(f"the clock recovery is for sps = {clock_recovery.sps}, the link has {sps}")
-            if framing is None:
-                raise ValueError("clock_recovery needs a framing: the instant is recovered modulo nh symbols and the frame search absorbs the shift")
-        self.clock, self.clock_recovery = clock, clock_recovery
-        self._clock_tau = self._clock_choice = self._clock_grid = None
+        return self._sync_result("coarse", "coarse_result")
 
     def clock_result(self):
         """(tau float64[nwin] in samples, modulo nh symbols; choice uint8[nwin]; grid 0 / 1) of the last block's clock recovery -
         synchronises.  A recovery with an ``anchor`` adds (the drift found in samples per window, the number of rejected windows)
         of its coarse track."""
-        if self.clock_recovery is None or self._clock_tau is None:
-            raise RuntimeError("clock_result needs a clock_recovery and a block that ran")
-        return (_hip.to_host(self._clock_tau), _hip.to_host(self._clock_choice), int(self._clock_grid.cpu())) + self._found(self.clock_recovery.timing_found)
-
-    def _joint_init(self, joint, spec, sps: int, framing, recovery, clock_recovery) -> None:
-        """``joint``: a ``waveforms_amd.sync.joint_cpm.CPMJointAcquisition`` that makes the detector's rows from the noisy samples
-        under a carrier AND a clock offset (``carrier=`` and ``clock=`` may both be given beside it).  None: nothing is added to
-        the chain.  Checked against the link's other keywords before anything touches the device."""
-        if joint is not None:
-            from ..sync.joint_cpm import CPMJointAcquisition
-
-            if not isinstance(joint, CPMJointAcquisition):
-                raise ValueError("joint is a waveforms_amd.sync.joint_cpm.CPMJointAcquisition")
-            if recovery is not None or clock_recovery is not None:
-                raise ValueError("joint excludes recovery and clock_recovery: it recovers the carrier and the timing itself")
-            if joint.spec != spec:
-                raise ValueError("the joint acquisition is for another design than the link's full-phase trellis")
-            if joint.sps != sps:
-                raise ValueError(f"the joint acquisition is for sps = {joint.sps}, the link has {sps}")
-            if framing is None:
-                raise ValueError("joint needs a framing: the instant and the phase are recovered modulo (nh sps, P/2) and (0, P), "
-                                 "and the frame search absorbs the shift")
-        self.joint = joint
-        self._joint = None
+        return self._sync_result("clock_recovery", "clock_result")
 
     def joint_result(self):
         """(tau float64[nwt] in samples per timing window, phase float64[nwc] in radians per carrier window - both modulo the
@@ -287,9 +224,14 @@ class _Framed:
         acquisition - synchronises.  An acquisition with an ``anchor`` adds (the timing drift found in samples per window, the
         rejected windows of the coarse timing track, the carrier drift found in radians per window, the rejected windows of the
         coarse carrier track)."""
-        if self.joint is None or self._joint is None:
-            raise RuntimeError("joint_result needs a joint acquisition and a block that ran")
-        return tuple(_hip.to_host(v) for v in self._joint) + self._found(self.joint.timing_found, self.joint.carrier_found)
+        return self._sync_result("joint", "joint_result")
+
+    def _recovered(self, rows):
+        """The bank's rows through ``recovery``, the slot that turns rows."""
+        if self.recovery is None:
+            return rows
+        rows, *self._sync_last["recovery"] = self.recovery.recover(rows, *self._differential)
+        return rows
 
     def _rate_db(self) -> float:
         """10 log10 of information bits per channel bit: Eb/N0 is per information bit and pays for the marker."""
@@ -332,12 +274,15 @@ class _Link(_Framed):
     """What every coded link does, whatever its waveform, its code and its loop: one block = ``ncw`` codewords of ``code`` sent
     back to back as ONE burst, PN23 information bits by ``stream_id``, Eb/N0 per INFORMATION bit (``_rate_db``).
 
-    The waveform base under this class supplies ``bits_per_symbol``, ``_wave_init`` (pad, ``nsym``, device tables), ``front_end``,
-    ``sigma``, the detector calls ``_soft`` / ``_soft_apriori``, ``count_uncoded`` and ``_lam0``: transmitted bit j pairs with the
-    detector's λ[j + _lam0], and ``_coded`` / ``_prior_coded`` are the only two places that use it.  The code supplies ``encode``
-    and ``_ncounts``, the width of ``counts``."""
+    The waveform base under this class supplies ``bits_per_symbol``, ``_wave_init`` (pad, ``nsym``, device tables, the bank's
+    filters ``_d_bank``), its synchroniser keywords (``_slots``, ``_drift``, ``_differential``, ``_check_recovery``), its part of
+    the front end (``_symbols``, ``_geometry``, ``_bank``, ``_fused_bank`` where it has one), ``sigma``, the detector calls
+    ``_soft`` / ``_soft_apriori``, ``_compare`` and ``_lam0``: transmitted bit j pairs with the detector's λ[j + _lam0], and
+    ``_coded`` / ``_prior_coded`` are the only two places that use it.  The code supplies ``encode`` and ``_ncounts``, the
+    width of ``counts``."""
 
     _ncounts = 4
+    _fused_bank = None
 
     def __init__(self, code, ncw: int, sps: int, framing=None, lead_bits: int = 0, carrier=None, recovery=None) -> None:
         if ncw < 1:
@@ -346,7 +291,10 @@ class _Link(_Framed):
         self.llr_scale = 1.0                    # (max-log-MAP and normalized min-sum do not depend on it)
         self.nbits = self.ncw * code.n_tx
         self._frame_init(framing, lead_bits, self.bits_per_symbol)
-        self._carrier_init(carrier, recovery)
+        self.carrier = _pair("carrier", "theta0, nu", carrier)
+        if recovery is not None:
+            self._check_recovery(recovery)
+        self.recovery = recovery
         self._wave_init()
         self._mask = generate_mask(23)
         self.counts = _hip.zeros(self._ncounts, "int64")
@@ -370,6 +318,46 @@ class _Link(_Framed):
         n = self.ncw * self.code.k
         bits, _ = dev.lfsr_bits(23, self._mask, (1 << 23) - 1, n, skip=int(stream_id) * n)
         return bits
+
+    def impaired(self, sig):
+        """A modulated signal -> (the signal under the link's impairments: ``carrier_offset`` in place, then ``timing_offset``;
+        where the bank reads it: the waveform's ``_geometry``)."""
+        if self.carrier is not None:
+            dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
+        drift = getattr(self, self._drift)
+        if drift is not None:
+            sig = dev.timing_offset(sig, drift[0], drift[1], 0)
+        return sig, self._geometry(sig)
+
+    def noisy(self, sig, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """A signal -> the channel's noisy samples, derotated."""
+        return dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, DEROTATION)
+
+    def _sent(self, tx, stream_id: int):
+        """Coded bits -> (the burst's impaired signal, where the bank reads it, its symbols); ``sent`` keeps the burst's bits."""
+        bits = self.sent = _hip.torch().cat((self.channel_bits(tx, stream_id), self._pad))
+        syms = self._symbols(bits)
+        return *self.impaired(dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)), syms
+
+    def samples(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """Coded bits (device ncw x n_tx) -> (the noisy samples of the burst, where the bank reads them, its symbols)."""
+        sig, at, syms = self._sent(tx, stream_id)
+        return self.noisy(sig, ebn0_db, seed, stream_id), at, syms
+
+    def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
+        """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst, its symbols): the plain bank's rows, or those a
+        synchroniser makes from the samples, behind those that correct the samples."""
+        sig, at, syms = self._sent(tx, stream_id)
+        if self._fused_bank is not None and not self._correctors and self._row_maker is None:      # (nothing reads samples)
+            return self._fused_bank(sig, *at, self.sigma(ebn0_db), seed, stream_id), syms
+        received = self.noisy(sig, ebn0_db, seed, stream_id)
+        for slot in self._correctors:
+            received, *self._sync_last[slot.name] = getattr(self, slot.name).correct(received, out=received)
+        if self._row_maker is None:
+            return self._bank(received, *at), syms
+        slot = self._row_maker
+        rows, *self._sync_last[slot.name] = getattr(self, slot.name).recover(received, self._d_bank, *at, *self._differential)
+        return rows, syms
 
     def _coded(self, lam, bits, search: bool = True):
         """A detector's (λ, bits) of the whole burst -> (λ of the coded bits, ncw x n_tx view; hard decisions of the channel bits
@@ -409,8 +397,17 @@ class _Link(_Framed):
         if self.framing is not None:
             self.sync.zero_()
 
+    def count_uncoded(self, hard, tx, syms=None) -> None:
+        """The detector's hard decisions against the channel bits in front of the pad, into ``uncoded`` - unless a synchroniser
+        leaves the rows shifted against the sent bits: there is then nothing to compare at."""
+        if self._shifts is None:
+            self._compare(hard, tx, syms)
+
     def uncoded_result(self) -> tuple[int, int]:
         """(bit errors of λ < 0 against the channel bits in front of the pad, bits compared) over the same blocks."""
+        if self._shifts is not None:
+            raise RuntimeError(f"uncoded_result: {self._shifts.shifted}; "
+                               "the channel bits are not counted (the decoder's counts hold)")
         return int(self.uncoded.cpu()[1]), self.blocks * self.nch
 
 
@@ -419,15 +416,29 @@ class _SOQPSK(_Link):
     bank and ``viterbi_soft`` (``CodedSOQPSKLink`` states the conventions)."""
 
     bits_per_symbol, _lam0 = 1, 1
+    _drift, _differential = "timing", (True,)                 # (the synchronisers' ``differential`` argument)
+    _slots = (
+        _Slot("timing_recovery", "a timing_recovery", "timing recovery", "rows", ("array", "array"), ("timing_found",), "timing.TimingRecovery",
+              excludes=("carrier", "recovery"), why=_NOT_JOINT,
+              framing="the instant is recovered modulo two symbols and the frame search absorbs the shift",
+              shifted="a timing recovery leaves the rows two rows early or late in some bursts"),
+        _Slot("acquisition", "an acquisition", "acquisition", "rows", ("array",) * 4, ("timing_found", "carrier_found"), "joint.JointAcquisition",
+              excludes=("recovery", "timing_recovery"), why=_ACQUIRES,
+              framing="the instant and the phase are recovered modulo (sps, π/2) and (0, π), and the frame search absorbs the shift and the polarity",
+              shifted="an acquisition leaves the rows a few rows early or late, and inverted, in some bursts"),
+        _Slot("coarse", "a coarse acquisition", "coarse acquisition", "samples", ("floats",), (), "coarse.CoarseFrequency",
+              excludes=("timing_recovery",), why="that path has no carrier recovery behind it",
+              needs=("recovery", "acquisition"),
+              needs_what="a recovery or an acquisition: it leaves the residual frequency and the phase to them"),
+        _Slot("recovery", "a recovery", "recovery", "turns", ("array", "array"), ("carrier_found",)),
+    )
 
     def __init__(self, code, ncw: int, sps: int = 8, detector: str = "PT", *, timing=None, timing_recovery=None, acquisition=None, coarse=None,
                  **burst) -> None:
         if detector not in TIMING_OFFSET:
             raise ValueError(f"unknown detector {detector!r}")
         self.detector = detector
-        self._timing_init(timing, timing_recovery, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
-        self._acquisition_init(acquisition, int(sps), burst.get("framing"), burst.get("recovery"), timing_recovery)
-        self._coarse_init(coarse, int(sps), burst.get("recovery"), timing_recovery, acquisition)
+        self._sync_init(int(sps), dict(burst, timing=timing, timing_recovery=timing_recovery, acquisition=acquisition, coarse=coarse))
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -436,7 +447,7 @@ class _SOQPSK(_Link):
         taps = (pt_matched_filter_taps if self.detector == "PT" else pam_matched_filter_taps)(pulse, 0.25, self.sps)
         self._d_h = _hip.to_device(np.array([0.25]))
         self._d_pulse = _hip.to_device(pulse)
-        self._d_taps = _hip.to_device(np.ascontiguousarray(taps))
+        self._d_taps = self._d_bank = _hip.to_device(np.ascontiguousarray(taps))
         self._tables = SOQPSKTrellis4x2DiffEncoded.dense_tables()
         self._pad = _hip.zeros(PAD_BITS, "uint8")
 
@@ -445,34 +456,20 @@ class _SOQPSK(_Link):
             return 0.0
         return sigma_for_ebn0(float(ebn0_db) + self._rate_db(), self.sps)
 
-    def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
-        """Coded bits (device ncw x n_tx) -> matched-filter rows of the burst."""
-        torch = _hip.torch()
-        bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
-        syms, _ = dev.fsm_encode(*self._tables, bits)
-        sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
-        if self.carrier is not None:
-            dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
-        if self.timing is not None:
-            sig = dev.timing_offset(sig, self.timing[0], self.timing[1], 0)
+    def _symbols(self, bits):
+        return dev.fsm_encode(*self._tables, bits)[0]
+
+    def _geometry(self, sig):
         first, ncols = dev.decimation(int(sig.shape[0]), self.sps, 2, TIMING_OFFSET[self.detector])
         if ncols < self.nch + 1:
             raise RuntimeError(f"{ncols} detector rows for {self.nch} channel bits")
-        if self.timing_recovery is not None:
-            received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
-            rows, self._timing_tau, self._timing_choice = self.timing_recovery.recover(received, self._d_taps, first, ncols, True)
-            return rows, syms
-        if self.acquisition is not None or self.coarse is not None:
-            received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
-            if self.coarse is not None:
-                received, self._coarse_found = self.coarse.correct(received, out=received)
-            if self.acquisition is None:                                   # (coarse beside recovery: the plain bank on the corrected samples)
-                return dev.mf_bank(received, self._d_taps, first, self.sps, ncols), syms
-            rows, *self._acq = self.acquisition.recover(received, self._d_taps, first, ncols, True)
-            return rows, syms
-        rows = dev.awgn_mf_bank(sig, self._d_taps, first, self.sps, ncols, self.sigma(ebn0_db), seed, stream_id, 0,
-                                np.exp(-1j * np.pi / 4))
-        return rows, syms
+        return first, ncols
+
+    def _bank(self, received, first: int, ncols: int):
+        return dev.mf_bank(received, self._d_taps, first, self.sps, ncols)
+
+    def _fused_bank(self, sig, first: int, ncols: int, sigma: float, seed: int, stream_id: int):
+        return dev.awgn_mf_bank(sig, self._d_taps, first, self.sps, ncols, sigma, seed, stream_id, 0, DEROTATION)
 
     def _check_recovery(self, recovery) -> None:
         from ..sync.carrier import CarrierRecovery
@@ -482,27 +479,14 @@ class _SOQPSK(_Link):
         if self.framing is None:
             raise ValueError("recovery needs a framing: the phase is recovered modulo π and the frame search's polarity resolves the rest")
 
-    def _recover(self, rows):
-        return self.recovery.recover(rows, True)
-
     def _soft(self, rows):
         return dev.viterbi_soft(rows, True)
 
     def _soft_apriori(self, rows, prior):
         return dev.viterbi_soft_apriori(rows, prior, self.damping)
 
-    def count_uncoded(self, hard, tx, syms) -> None:
-        if self.timing_recovery is None and self.acquisition is None:      # (recovered rows may sit a row or two from the sent bits: nothing to compare at)
-            dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
-
-    def uncoded_result(self) -> tuple[int, int]:
-        if self.timing_recovery is not None:
-            raise RuntimeError("uncoded_result: a timing recovery leaves the rows two rows early or late in some bursts; "
-                               "the channel bits are not counted (the decoder's counts hold)")
-        if self.acquisition is not None:
-            raise RuntimeError("uncoded_result: an acquisition leaves the rows a few rows early or late, and inverted, in some bursts; "
-                               "the channel bits are not counted (the decoder's counts hold)")
-        return super().uncoded_result()
+    def _compare(self, hard, tx, syms) -> None:
+        dev.count_errors(syms, syms, hard, self.sent, self.nch, self.uncoded)
 
 
 class _CPM(_Link):
@@ -511,6 +495,18 @@ class _CPM(_Link):
 
     _lam0 = 0
     bits_per_symbol = property(lambda self: self.spec.bits_per_symbol)
+    _drift, _differential = "clock", ()
+    _slots = (
+        _Slot("clock_recovery", "a clock_recovery", "clock recovery", "rows", ("array", "array", "int"), ("timing_found",),
+              "timing_cpm.CPMTimingRecovery", excludes=("carrier", "recovery"), why=_NOT_JOINT, design=True,
+              framing="the instant is recovered modulo nh symbols and the frame search absorbs the shift",
+              shifted="a clock recovery leaves the rows a whole number of periods early or late in some bursts"),
+        _Slot("joint", "a joint acquisition", "joint acquisition", "rows", ("array",) * 4, ("timing_found", "carrier_found"),
+              "joint_cpm.CPMJointAcquisition", excludes=("recovery", "clock_recovery"), why=_ACQUIRES, design=True,
+              framing="the instant and the phase are recovered modulo (nh sps, P/2) and (0, P), and the frame search absorbs the shift",
+              shifted="a joint acquisition leaves the rows a whole number of periods early or late in some bursts"),
+        _Slot("recovery", "a recovery", "recovery", "turns", ("array", "array"), ("carrier_found",)),
+    )
 
     def __init__(self, code, ncw: int, waveform: str = "multih", sps: int = 8, *, clock=None, clock_recovery=None, joint=None, **burst) -> None:
         from ..viterbi import cpm
@@ -520,8 +516,7 @@ class _CPM(_Link):
         if waveform == "multih" and code.n_tx % 2:
             raise ValueError(f"ARTM sends two bits per symbol: a code with an odd n_tx = {code.n_tx} is refused")
         self.waveform, self.spec = waveform, cpm.ARTM_64 if waveform == "multih" else cpm.PCMFM_20
-        self._clock_init(clock, clock_recovery, self.spec, int(sps), burst.get("framing"), burst.get("carrier"), burst.get("recovery"))
-        self._joint_init(joint, self.spec, int(sps), burst.get("framing"), burst.get("recovery"), clock_recovery)
+        self._sync_init(int(sps), dict(burst, clock=clock, clock_recovery=clock_recovery, joint=joint))
         super().__init__(code, ncw, sps, **burst)
 
     def _wave_init(self) -> None:
@@ -540,7 +535,7 @@ class _CPM(_Link):
             raise RuntimeError(f"{self.ncalls} detector calls for {self.nch} channel bits")
         self._d_h = _hip.to_device(spec.mod_index)
         self._d_pulse = _hip.to_device(pulse)
-        self._d_templates = _hip.to_device(cpm.matched_filter_templates(pulse, self.sps, cpm.full_phase(spec)))
+        self._d_templates = self._d_bank = _hip.to_device(cpm.matched_filter_templates(pulse, self.sps, cpm.full_phase(spec)))
         self._d_rot = _hip.to_device(cpm.rotation_table(spec))
         self._pad = _hip.zeros(PAD_SYMS * lg, "uint8")
 
@@ -551,26 +546,15 @@ class _CPM(_Link):
             return 0.0
         return cpm_sigma(float(ebn0_db) + self._rate_db(), self.sps, self.spec.bits_per_symbol)
 
-    def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
-        """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst float64[ncalls, nfilt, 2], its symbols)."""
-        torch = _hip.torch()
-        bits = self.sent = torch.cat((self.channel_bits(tx, stream_id), self._pad))
-        syms = dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
-        sig = dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)
-        if self.carrier is not None:
-            dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
-        if self.clock is not None:
-            sig = dev.timing_offset(sig, self.clock[0], self.clock[1], 0)
-        received = dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, np.exp(-1j * np.pi / 4))
-        if self.clock_recovery is not None:
-            rows, self._clock_tau, self._clock_choice, self._clock_grid = self.clock_recovery.recover(received, self._d_templates, self.start0,
-                                                                                                     self.ncalls)
-            return rows, syms
-        if self.joint is not None:
-            rows, *self._joint = self.joint.recover(received, self._d_templates, self.start0, self.ncalls)
-            return rows, syms
-        rows = dev.cpm_mf_rows(received, self._d_templates, self.start0, self.sps, self.ncalls)
-        return rows, syms
+    def _symbols(self, bits):
+        return dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
+
+    def _geometry(self, sig):
+        return self.start0, self.ncalls
+
+    def _bank(self, received, start0: int, ncalls: int):
+        """Rows float64[ncalls, nfilt, 2]."""
+        return dev.cpm_mf_rows(received, self._d_templates, start0, self.sps, ncalls)
 
     def _check_recovery(self, recovery) -> None:
         from ..sync.carrier_cpm import CPMCarrierRecovery
@@ -580,29 +564,15 @@ class _CPM(_Link):
         if recovery.spec != self.spec:
             raise ValueError(f"the recovery is for another design than the link's {self.waveform!r} full-phase trellis")
 
-    def _recover(self, rows):
-        return self.recovery.recover(rows)
-
     def _soft(self, rows):
         return dev.cpm_soft(rows, self.spec, 0, 0, d_rot=self._d_rot)
 
     def _soft_apriori(self, rows, prior):
         return dev.cpm_soft_apriori(rows, self.spec, prior, self.damping, 0, 0 if prior is None else self.prior_warmup, d_rot=self._d_rot)
 
-    def count_uncoded(self, hard, tx, syms=None) -> None:
-        if self.clock_recovery is not None or self.joint is not None:      # (recovered rows may sit a period from the sent bits: nothing to compare at)
-            return
+    def _compare(self, hard, tx, syms) -> None:
         flat = tx.reshape(-1) if self.framing is None else self.sent
         dev.count_errors(hard, flat, hard, flat, self.nch, self.uncoded)     # (bits in both pairs: [1] is what is read)
-
-    def uncoded_result(self) -> tuple[int, int]:
-        if self.clock_recovery is not None:
-            raise RuntimeError("uncoded_result: a clock recovery leaves the rows a whole number of periods early or late in some "
-                               "bursts; the channel bits are not counted (the decoder's counts hold)")
-        if self.joint is not None:
-            raise RuntimeError("uncoded_result: a joint acquisition leaves the rows a whole number of periods early or late in some "
-                               "bursts; the channel bits are not counted (the decoder's counts hold)")
-        return super().uncoded_result()
 
 
 class _LDPC:
