@@ -1330,6 +1330,33 @@ int wf_coarse_estimate(wf_ctx *ctx, const double *d_spectra, int nfft, int sps, 
 int wf_carrier_offset_dev_c128(wf_ctx *ctx, const double *d_in_ri, int64_t n, const double *d_nu, double gain,
                                int64_t first_index, double *d_out_ri, void *stream);
 
+/* ---- Multi-symbol noncoherent soft detector for PCM/FM (Osborne and Luntz) ------------------
+ * (The reference has no such detector; the entry points are defined here.  waveforms_amd/viterbi/noncoherent.py restates them in
+ * numpy: noncoherent_templates_host, noncoherent_soft_host.)
+ * Per bit, N symbols of samples are correlated with the noise-free signal of every N-bit hypothesis and the correlation
+ * MAGNITUDES are compared: no carrier phase is needed, and a frequency offset costs only what it turns within one window.
+ * Inputs: r_k, k < n, complex128; N odd, 3 .. 7; K = N sps; c = (N - 1) / 2; the table T, complex128[2^N][K], row-major.
+ * Table (built on the host and uploaded; any table is taken as it is).  Row p, sample k:
+ *      T[p][k] = exp(j 2π h Σ_{i < N} a_i q[k + offset - i sps]),   a_i = 2 bit_{N-1-i}(p) - 1   (MSB first, as wf_cpm_soft
+ *    numbers a symbol's bits),   q[m] = (Σ_{l <= m} pulse[l]) / sps, 0 for m < 0 and its last value behind the pulse:
+ *    samples offset .. offset + K - 1 of the modulator's output for the N bits of p alone, without the initial phase and the
+ *    channel's derotation (magnitudes do not see them).  0 <= offset <= sps.
+ * Detector.  Bit j's window begins at sample w_j = start + (j - c) sps;  r_k = 0 for k outside [0, n);
+ *      z_p = Σ_{k < K} r[w_j + k] conj(T[p][k])
+ *      λ_j = max_{p: bit c of p is 0} |z_p| - max_{p: bit c of p is 1} |z_p|        d_llr[j]
+ *      d_bits[j] = λ_j < 0
+ *    λ > 0 favours bit 0 (the sign of wf_cpm_soft).  The magnitude, not its square: the max-log form of ln I0(2 |z| / N0).  An
+ *    all-zero window gives λ = +0 and bit 0.  The host statement adds k increasing; the kernel runs the product on the fp64
+ *    matrix cores as four real chains per hypothesis and joins them, so it agrees to rounding - |λ - λ_host| <=
+ *    2 · 8 (K + 8) 2^-53 Σ_k |r[w_j + k]| - and not bit for bit.  Input is taken to be finite.
+ * wf_noncoherent_geometry: h_geom[0] bits per tile (one workgroup), [1] workgroups launched for nbits, [2] LDS bytes each.
+ * N other than 3, 5, 7, sps other than 4, 8, 10, 16, 20 (the kernel's instantiations), n or nbits outside 1 .. 2^40, |start| >
+ * 2^40, a NULL pointer, samples or table not 16-byte or d_llr not 8-byte aligned, outputs that overlap each other or an input:
+ * WF_ERR_VALUE before the context is touched. */
+int wf_noncoherent_geometry(wf_ctx *ctx, int N, int sps, int64_t nbits, int64_t *h_geom);
+int wf_noncoherent_soft_c128(wf_ctx *ctx, const double *d_received_ri, int64_t n, const double *d_templates_ri, int N, int sps,
+                             int64_t start, int64_t nbits, double *d_llr, uint8_t *d_bits, void *stream);
+
 /* ---- data products of the reference's plotting helpers (no plotting) ------------------
  * Welch PSD exactly as Axes.psd / matplotlib.mlab.psd evaluates the call of
  * waveforms/viz/psd.py:36-41 (window d_window of nfft doubles, np.hanning for the reference;

@@ -357,6 +357,48 @@ def carrier_offset_dev(signal, nu, gain: float = 1.0, first_index: int = 0, out=
     return out
 
 
+def noncoherent_templates(pulse, h: float, sps: int, N: int, offset: int | None = None):
+    """The multi-symbol noncoherent detector's hypothesis table on the device: float64[2^N, N sps, 2], a host build
+    (``viterbi.noncoherent.noncoherent_templates_host``, which states the definition) and one upload.  ``offset=None``:
+    ``DEFAULT_OFFSET``."""
+    from .viterbi import noncoherent as nc
+
+    return _hip.to_device(nc.noncoherent_templates_host(pulse, h, sps, N, nc.DEFAULT_OFFSET if offset is None else offset))
+
+
+def noncoherent_geometry(N: int, sps: int, nbits: int, ctx=None) -> dict:
+    """What ``noncoherent_soft`` launches (``wf_noncoherent_geometry``): bits per tile (one workgroup), workgroups, LDS bytes each."""
+    return _geometry("wf_noncoherent_geometry", ("tile_bits", "workgroups", "lds_bytes"), _ctx(ctx), int(N), int(sps), int(nbits))
+
+
+def noncoherent_soft(received, templates, sps: int, start: int, nbits: int, out=None, ctx=None):
+    """The multi-symbol noncoherent soft detector (``wf_noncoherent_soft_c128``; include/wfhip.h states the definition) -> (λ
+    float64[nbits], bits uint8[nbits]) on the device.  ``received``: contiguous device float64[n, 2]; ``templates``: contiguous
+    device float64[2^N, N sps, 2] (``noncoherent_templates``); bit j's window begins at sample ``start`` + (j - (N - 1) / 2) sps and
+    samples outside the burst read as zero.  λ > 0 favours bit 0, bits = λ < 0.  ``out``: a (λ, bits) pair of contiguous device
+    tensors of ``nbits`` values to write into."""
+    torch = _hip.torch()
+    n, sps, nbits = _samples("received", received), int(sps), int(nbits)
+    if templates.dtype != torch.float64 or not templates.is_contiguous() or templates.dim() != 3 or templates.shape[2] != 2:
+        raise ValueError("templates must be contiguous float64[2^N, N sps, 2]")
+    rows, K = int(templates.shape[0]), int(templates.shape[1])
+    N = K // sps if sps > 0 else 0
+    if N not in (3, 5, 7) or N * sps != K or rows != 1 << N:
+        raise ValueError(f"templates float64[{rows}, {K}, 2] are not float64[2^N, N sps, 2] with N odd and 3 .. 7 at sps = {sps}")
+    if nbits < 1:
+        raise ValueError("nbits must be at least 1")
+    if out is None:
+        llr, bits = _hip.empty(nbits, "float64"), _hip.empty(nbits, "uint8")
+    else:
+        llr, bits = out
+        if llr.dtype != torch.float64 or bits.dtype != torch.uint8 or not llr.is_contiguous() or not bits.is_contiguous() or \
+                llr.numel() != nbits or bits.numel() != nbits:
+            raise ValueError(f"out must be (contiguous float64[{nbits}], contiguous uint8[{nbits}])")
+    _hip.check(_hip.lib().wf_noncoherent_soft_c128(_ctx(ctx), _hip.ptr(received), n, _hip.ptr(templates), N, sps, int(start), nbits, _hip.ptr(llr),
+                                                   _hip.ptr(bits), _hip.stream()))
+    return llr, bits
+
+
 def viterbi_soft_branch(rows, differential: bool = True, warmup: int = 0, ctx=None):
     """``viterbi_soft`` on 48-byte rows with the decided branch of every row (``wf_viterbi4_soft_branch``; include/wfhip.h
     states the definition) -> (llr f64[ncalls], bits u8[ncalls], branch u8[ncalls]) on device.  llr and bits are bitwise
