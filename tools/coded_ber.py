@@ -98,6 +98,7 @@ import argparse
 import json
 import sys
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -175,537 +176,402 @@ def _coarse_point(found, lost, true_nu, true_eps):
                                              for i, (c, r) in enumerate(zip(per_burst["coarse"], per_burst["reference"])) if c > r]}
 
 
-def main_carrier(args) -> None:
-    """The ``--recover`` form: genie, impaired and recovered links on the same blocks (SOQPSK-TG: framed; ARTM, PCM/FM: not)."""
-    import math
-
+def _setup(args):
+    """What every LDPC form starts from: the device, the code and the codewords per burst."""
     import torch
 
-    from waveforms_amd import device as dev
     from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CodedCPMLink, CodedSOQPSKLink
-    from waveforms_amd.encoding.framing import Framing
-    from waveforms_amd.sync.carrier import MAX_DRIFT_TURNS, CarrierRecovery
-    from waveforms_amd.sync.carrier_cpm import DEFAULT_HYPOTHESES, MAX_DRIFT_PERIODS, CPMCarrierRecovery
 
     torch.cuda.set_device(0)
     code = ldpc.demo_code(128 if args.code == "demo" else 1024)
-    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
+    return code, min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
+
+
+def _rounds(steps, nev, body):
+    """``body(ev)`` ``steps`` + 1 times, the first a warm-up: it records the ``nev`` device events ``ev`` in order and may return
+    its stage times (name -> ms) -> (the ms between consecutive events, the stage times), summed over the ``steps`` timed rounds."""
+    import torch
+
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(nev)]
+    ms, stages = [0.0] * max(nev - 1, 0), {}
+    for s in range(steps + 1):
+        t = body(ev)
+        if ev:
+            torch.cuda.synchronize()
+        if s:                                                             # (the first round warms up)
+            ms = [m + a.elapsed_time(b) for m, a, b in zip(ms, ev, ev[1:])]
+            for k, v in (t or {}).items():
+                stages[k] = stages.get(k, 0.0) + v
+    return ms, stages
+
+
+def _mean(total, steps):
+    return round(total / max(steps, 1), 4)
+
+
+def _stage_means(sync, steps, body, nev=0, total=True):
+    """``_rounds`` with ``sync.times`` on -> (the mean ms between the events, the mean stage times per block with their total)."""
+    sync.times = True
+    ms, tot = _rounds(steps, nev, body)
+    sync.times = False
+    stages = {k: _mean(v, steps) for k, v in tot.items()}
+    if total:
+        stages["total"] = _mean(sum(tot.values()), steps)
+    return [_mean(v, steps) for v in ms], stages
+
+
+class _Form(NamedTuple):
+    """One synchroniser form of the tool, as ``main_sync`` runs it."""
+
+    s: object                     # ``_sync_setup``'s
+    links: dict                   # curve name -> link, in the order they run and print: genie, impaired, the synchronised ones
+    out: dict                     # the header, ending in "points": [] (and "coarse")
+    entry: tuple                  # a curve's entries beyond the counts (``_curve_entry``)
+    compared: list                # the curves whose Eb/N0 at FER 1e-2 is interpolated,
+    losses: object                # and loss(name) -> the header's loss entries
+    truth: tuple = ()             # --coarse: the true (nu, eps) the estimates are held against
+    point: object = None          # (point, ebn0, first free burst): the form's timed sections and finds, into the point
+    after: object = None          # () -> entries behind the summary (the timed acquisitions); the result then goes to --acq-out,
+    acq_key: str | None = None    # under this key of the file (None: it is the file)
+    rejected: object = None       # anchored link -> the windows its coarse tracks rejected in the last burst,
+    rejected_windows: object = None   # and the list of those per burst -> the curve's "rejected_windows"
+
+
+def _sync_setup(args, framed=True):
+    """What the synchroniser forms share: ``_setup``, the framing, the two impairments from the flags, the waveform's link class
+    with the keywords every link of the form gets (``link``), and the names of its links' synchroniser keywords and results."""
+    import math
+    from types import SimpleNamespace
+
+    from waveforms_amd.encoding.coded import CodedCPMLink, CodedSOQPSKLink
+    from waveforms_amd.encoding.framing import Framing
+
+    code, per = _setup(args)
     cpm = args.waveform != "soqpsk"
-    carrier = (math.radians(args.carrier_phase), args.carrier_freq)
+    fr = Framing(code)
+    kw = dict(alpha=args.alpha, max_iter=args.max_iter, **(dict(framing=fr, lead_bits=args.lead_bits) if framed else {}))
     if cpm:
         from waveforms_amd.viterbi import cpm as vc
 
-        spec = vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
-        rec = CPMCarrierRecovery(spec, args.carrier_window, args.carrier_span, args.carrier_hyp or DEFAULT_HYPOTHESES, args.carrier_refine)
-        cls, kw, limit = CodedCPMLink, dict(waveform=args.waveform, alpha=args.alpha, max_iter=args.max_iter), MAX_DRIFT_PERIODS / spec.p
-        recover, soft = rec.recover, lambda rows: dev.cpm_soft(rows, spec, 0, 0, d_rot=links["genie"]._d_rot)
-        framed = None
+        cls, kw["waveform"], spec = CodedCPMLink, args.waveform, vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
+        names = dict(drift="clock", timing_slot=("clock_recovery", "clock_result", ("grid",)), joint_slot=("joint", "joint_result"), unit="calls")
     else:
-        fr = Framing(code)
+        cls, kw["detector"], spec = CodedSOQPSKLink, args.detector, None
+        names = dict(drift="timing", timing_slot=("timing_recovery", "timing_result", ()), joint_slot=("acquisition", "acquisition_result"), unit="rows")
+    return SimpleNamespace(code=code, per=per, sps=8, cpm=cpm, spec=spec, link=lambda **sync: cls(code, per, **sync, **kw),
+                           carrier=(math.radians(args.carrier_phase), args.carrier_freq), timing=(args.timing_offset, args.timing_drift),
+                           head=lambda form, **first: {"tool": "coded_ber", "form": form, **first, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx},
+                           framed={"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits} if framed else None, **names)
+
+
+def _coarse_links(args, s, links, carrier, **fine):
+    """``--coarse``: the coarse stage in front of the SAME fine synchroniser ``fine`` (``links["coarse"]``), and that synchroniser at
+    --carrier-freq 0 as the reference curve -> (the ``CoarseFrequency``, its header entry)."""
+    from waveforms_amd.sync.coarse import CoarseFrequency
+
+    coarse = CoarseFrequency(s.sps, nfft=args.coarse_nfft, smooth=args.coarse_smooth or None)
+    links["reference"] = s.link(carrier=(carrier[0], 0.0), **fine)
+    links["coarse"] = s.link(carrier=carrier, coarse=coarse, **fine)
+    return coarse, {"nfft": coarse.nfft, "smooth": coarse.smooth, "search": coarse.search}
+
+
+def _carrier_form(args):
+    """The ``--recover`` form: genie, impaired and recovered links on the same blocks (SOQPSK-TG: framed; ARTM, PCM/FM: not)."""
+    s = _sync_setup(args, framed=args.waveform == "soqpsk")
+    if s.cpm:
+        from waveforms_amd.sync.carrier_cpm import DEFAULT_HYPOTHESES, MAX_DRIFT_PERIODS, CPMCarrierRecovery
+
+        rec = CPMCarrierRecovery(s.spec, args.carrier_window, args.carrier_span, args.carrier_hyp or DEFAULT_HYPOTHESES, args.carrier_refine)
+        limit = MAX_DRIFT_PERIODS / s.spec.p
+    else:
+        from waveforms_amd.sync.carrier import MAX_DRIFT_TURNS as limit, CarrierRecovery
+
         rec = CarrierRecovery(args.carrier_window, args.carrier_span, args.carrier_hyp or 8, args.carrier_refine)
-        cls, kw, limit = CodedSOQPSKLink, dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits), MAX_DRIFT_TURNS
-        recover, soft = lambda rows: rec.recover(rows, True), lambda rows: dev.viterbi_soft(rows, True)
-        framed = {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits}
-    links = {"genie": cls(code, per, **kw), "impaired": cls(code, per, carrier=carrier, **kw),
-             "recovered": cls(code, per, carrier=carrier, recovery=rec, **kw)}
-    sps = links["genie"].sps
+    links = {"genie": s.link(), "impaired": s.link(carrier=s.carrier), "recovered": s.link(carrier=s.carrier, recovery=rec)}
+    out = {**s.head("carrier", waveform=args.waveform), "detector": None if s.cpm else args.detector, "block_codewords": s.per,
+           "framed": s.framed,
+           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
+                       "drift_turns_per_window": abs(args.carrier_freq) * s.sps * rec.window, "documented_limit_turns_per_window": limit},
+           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine}, "points": []}
     coarse = None
     if args.coarse:
-        # the coarse stage in front of the SAME fine recovery, and that recovery at --carrier-freq 0 as the reference curve
-        from waveforms_amd.sync.coarse import CoarseFrequency
+        coarse, out["coarse"] = _coarse_links(args, s, links, s.carrier, recovery=rec)
 
-        coarse = CoarseFrequency(sps, nfft=args.coarse_nfft, smooth=args.coarse_smooth or None)
-        links["reference"] = cls(code, per, carrier=(carrier[0], 0.0), recovery=rec, **kw)
-        links["coarse"] = cls(code, per, carrier=carrier, recovery=rec, coarse=coarse, **kw)
-    out = {"tool": "coded_ber", "form": "carrier", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
-           "detector": None if cpm else args.detector, "block_codewords": per, "framed": framed,
-           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
-                       "drift_turns_per_window": abs(args.carrier_freq) * sps * rec.window, "documented_limit_turns_per_window": limit},
-           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine}, "points": []}
-    if coarse is not None:
-        out["coarse"] = {"nfft": coarse.nfft, "smooth": coarse.smooth, "search": coarse.search}
+    def point(p, e, b):
+        """The coarse stage's times over the front end of its link, then the recovery's stages on one burst, each bracketed by
+        device events, beside one plain soft detection of the same rows."""
+        if coarse is not None:
+            ck = links["coarse"]
+
+            def front_end(ev):
+                ck.front_end(ck.encode(ck.info_bits(b)), e, 1, b)
+                return coarse.stage_times()
+
+            _, p["coarse_ms_per_block"] = _stage_means(coarse, args.steps, front_end, total=False)
+        lk = links["recovered"]
+        rows, _ = lk.front_end(lk.encode(lk.info_bits(b)), e, 1, b)
+
+        def body(ev):
+            rec.recover(rows, *lk._differential)
+            t = rec.stage_times()
+            ev[0].record()
+            lk._soft(rows)
+            ev[1].record()
+            return t
+
+        (soft_ms,), stages = _stage_means(rec, args.steps, body, 2)
+        p.update({"recovery_ms_per_block": stages, "soft_detector_ms": soft_ms, "burst_rows": int(rows.shape[0])})
+
+    return _Form(s=s, links=links, out=out, entry=("uncoded_ber", "wrong_locks"), truth=(args.carrier_freq, 0.0), point=point,
+                 compared=["genie", "recovered"], losses=lambda loss: {"loss_db_at_fer_1e-2": loss("recovered")})
+
+
+def _timing_form(args):
+    """The ``--recover-timing`` form: genie, impaired and recovered FRAMED links on the same blocks - SOQPSK-TG with a
+    ``TimingRecovery``, ARTM and PCM/FM (``--waveform multih|pcmfm``) with a ``CPMTimingRecovery``; the anchored one with ``--anchor``."""
+    from functools import partial
+
+    s = _sync_setup(args)
+    if s.cpm:
+        from waveforms_amd.sync.timing_cpm import MAX_DRIFT_SAMPLES, CPMTimingRecovery
+
+        make = partial(CPMTimingRecovery, s.spec, s.sps, args.timing_window, args.timing_span, args.timing_hyp, args.timing_refine, args.timing_delta)
+        limit = MAX_DRIFT_SAMPLES[args.waveform]
+    else:
+        from waveforms_amd.sync.timing import MAX_DRIFT_SAMPLES as limit, TimingRecovery
+
+        make = partial(TimingRecovery, s.sps, args.timing_window or 256, args.timing_span, args.timing_hyp or 8, args.timing_refine,
+                       args.timing_delta or 2.0)
+    keyword, result, beyond = s.timing_slot
+    rec = make()
+    syncs = {"recovered": rec, **({"anchored": make(anchor=args.anchor)} if args.anchor else {})}
+    links = {"genie": s.link(), "impaired": s.link(**{s.drift: s.timing})}
+    links.update((name, s.link(**{s.drift: s.timing, keyword: sync})) for name, sync in syncs.items())
+    out = {**s.head("timing", waveform=args.waveform), "detector": None if s.cpm else args.detector, "block_codewords": s.per,
+           "framed": s.framed,
+           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * s.sps * rec.window,
+                      "documented_limit_samples_per_window": limit},
+           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine, "delta": rec.delta,
+                        "anchor": args.anchor}, "points": []}
+
+    def point(p, e, b):
+        """The recovery's stages on one burst's noisy samples, each bracketed by device events, beside the plain front end (channel
+        + bank, what the genie link runs) and one plain soft detection of its rows; then what the last burst's recovery found."""
+        lk = links["recovered"]
+        sig, at, _ = lk.signal(lk.encode(lk.info_bits(b)), b)
+        received = lk.noisy(sig, e, 1, b)
+
+        def body(ev):
+            rec.recover(received, lk._d_bank, *at, *lk._differential)
+            t = rec.stage_times()
+            ev[0].record()
+            if lk._fused_bank is not None:
+                rows = lk._fused_bank(sig, *at, lk.sigma(e), 1, b)
+            else:
+                rows = lk._bank(lk.noisy(sig, e, 1, b), *at)
+            ev[1].record()
+            lk._soft(rows)
+            ev[2].record()
+            return t
+
+        (front_ms, soft_ms), p["recovery_ms_per_block"] = _stage_means(rec, args.steps, body, 3)
+        p.update({"fused_front_end_ms": front_ms, "soft_detector_ms": soft_ms, "burst_rows": int(at[1])})
+        tau, _choice, *found = getattr(lk, result)()
+        p["tau_samples"] = {"first": round(float(tau[0]), 3), "last": round(float(tau[-1]), 3), "windows": int(tau.size)}
+        p.update(zip(beyond, found))
+
+    def losses(loss):
+        return {"loss_db_at_fer_1e-2": loss("recovered"), **({"anchored_loss_db_at_fer_1e-2": loss("anchored")} if args.anchor else {})}
+
+    return _Form(s=s, links=links, out=out, entry=("uncoded_ber", "wrong_locks", "last_lock"), point=point, compared=["genie", *syncs],
+                 losses=losses, rejected=lambda lk: getattr(lk, result)()[-1], rejected_windows=sum)
+
+
+def _time_acquisition(lk, make, stacks, length, ebn0, steps, unit, stack_of):
+    """One acquisition of a burst of about ``length`` rows or calls (PN bits, the link's own impairments and channel) per entry of
+    ``stacks`` (name -> (stack, anchor)): device events around the whole call, ``steps`` calls after one warm-up, beside one plain
+    soft detection of as many rows -> {unit, "soft_detector_ms", name: {"stack", "ms", "launches", "in_soft_detections", "stages_ms"}}."""
+    from waveforms_amd import device as dev
+
+    bits = dev.lfsr_bits(23, lk._mask, (1 << 23) - 1, int(length) * lk.bits_per_symbol)[0]
+    sig = lk.impaired(lk.modulated(bits)[0])
+    at = lk._geometry(sig, int(length))                                   # (not the link's own burst: the geometry of this length)
+    received = lk.noisy(sig, ebn0, 1, 0)
+    del sig
+    plain = lk._bank(received, *at)
+
+    def soft(ev):
+        ev[0].record()
+        lk._soft(plain)
+        ev[1].record()
+
+    (soft_ms,), _ = _rounds(steps, 2, soft)
+    del plain
+    n = max(steps, 1)
+    out = {unit: int(at[1]), "soft_detector_ms": round(soft_ms / n, 4)}
+    for name, (stack, anchor) in stacks.items():
+        acq = make(stack=stack, anchor=anchor)
+
+        def once(ev):
+            acq.times = False
+            ev[0].record()
+            acq.recover(received, lk._d_bank, *at, *lk._differential)
+            ev[1].record()
+
+        (ms,), _ = _rounds(steps, 2, once)
+        acq.times = True                                                  # (the stages from a call of their own: the events cost time)
+        acq.recover(received, lk._d_bank, *at, *lk._differential)
+        stages = {k: round(v, 4) for k, v in acq.stage_times().items()}
+        out[name] = {"stack": stack_of(acq, stack, at[1]), "ms": round(ms / n, 4), "launches": acq.launches,
+                     "in_soft_detections": round(ms / n / (soft_ms / n), 2), "stages_ms": stages}
+    return out
+
+
+def _acquire_form(args):
+    """The ``--acquire`` form: genie, impaired and acquired FRAMED links on the same blocks under a carrier offset AND a timing
+    offset, the anchored curve with ``--anchor``, and the time of one acquisition, unstacked and stacked.  SOQPSK-TG: a
+    ``JointAcquisition``, one more acquired curve per further value of ``--acq-carrier-hyp``, timed on bursts of ``--acq-time-rows``
+    rows.  ARTM and PCM/FM: a ``CPMJointAcquisition``, timed on the link's own burst and on bursts of ``--acq-time-rows`` calls; the
+    result goes under the waveform's key of ``--acq-out``, beside what the file holds for the other waveform."""
+    from functools import partial
+
+    s = _sync_setup(args)
+    stack = args.acq_stack or None
+    hyp = args.acq_carrier_hyp
+    if s.cpm:
+        from waveforms_amd.sync.joint_cpm import MAX_DRIFT_PERIODS, MAX_DRIFT_SAMPLES, CPMJointAcquisition
+
+        common = dict(timing_window=args.timing_window, carrier_window=args.carrier_window, span=args.timing_span, timing_hypotheses=args.timing_hyp,
+                      carrier_hypotheses=args.carrier_hyp or 2, refine=args.timing_refine, delta=args.timing_delta)
+        first = partial(CPMJointAcquisition, s.spec, s.sps, **common)
+        further = {}
+        # timed unstacked (cpm_soft_branch per table and per buffer) and stacked, on the link's own burst and on 1e6 calls
+        timed = dict(stacks={"stack_1": (1, 0), "stacked": (None, 0), **({"stacked_anchored": (None, args.anchor)} if args.anchor else {})},
+                     lengths=lambda lk: [lk.ncalls] + ([1_000_000] if args.acq_time_rows == [211_252, 10_000_000] else args.acq_time_rows),
+                     stack_of=lambda acq, stack, n: stack)
+    else:
+        from waveforms_amd.sync.joint import MAX_DRIFT_SAMPLES, MAX_DRIFT_TURNS, STACK_BYTES, JointAcquisition
+
+        common = dict(window=args.timing_window or 256, span=args.timing_span, timing_hypotheses=args.acq_timing_hyp, refine=args.timing_refine,
+                      delta=args.timing_delta or 2.0)
+        make = partial(JointAcquisition, s.sps, **common)
+        first = partial(make, carrier_hypotheses=hyp[0])
+        further = {f"acquired_hc{hc}": partial(make, carrier_hypotheses=hc) for hc in hyp[1:]}
+        # timed unstacked (the existing entry points per hypothesis) and stacked
+        timed = dict(stacks={"stack_1": (1, 0), "stack_default": (stack, 0), **({"stack_default_anchored": (stack, args.anchor)} if args.anchor else {})},
+                     lengths=lambda lk: args.acq_time_rows, stack_of=lambda acq, stack, n: acq.stack_for(n))
+    keyword, result = s.joint_slot
+    acqs = {"acquired": first(stack=stack), **{name: f(stack=stack) for name, f in further.items()}}
+    if args.anchor:                                                       # the anchored curve beside the first acquired one, on the same blocks
+        acqs["anchored"] = first(stack=stack, anchor=args.anchor)
+    both = {"carrier": s.carrier, s.drift: s.timing}
+    links = {"genie": s.link(), "impaired": s.link(**both)}
+    links.update((name, s.link(**both, **{keyword: acq})) for name, acq in acqs.items())
+    carrier = {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq}
+    timing = {"tau0_samples": args.timing_offset, "eps": args.timing_drift}
+    if s.cpm:
+        a = acqs["acquired"]
+        out = {**s.head("acquire", waveform=args.waveform), "block_codewords": s.per, "burst_calls": links["genie"].ncalls, "framed": s.framed,
+               "carrier": {**carrier, "drift_turns_per_carrier_window": abs(args.carrier_freq) * s.sps * a.carrier_window,
+                           "documented_limit_turns_per_carrier_window": MAX_DRIFT_PERIODS / s.spec.p},
+               "timing": {**timing, "drift_samples_per_timing_window": abs(args.timing_drift) * s.sps * a.timing_window,
+                          "documented_limit_samples_per_timing_window": MAX_DRIFT_SAMPLES[args.waveform]},
+               "acquisition": {"timing_window": a.timing_window, "carrier_window": a.carrier_window, "span": a.span, "timing_hypotheses": a.timing_hypotheses,
+                               "carrier_hypotheses": a.carrier_hypotheses, "refine": a.refine, "delta": a.delta, "stack": a.stack, "anchor": args.anchor},
+               "points": []}
+    else:
+        W = common["window"]
+        out = {**s.head("acquire"), "detector": args.detector, "block_codewords": s.per, "framed": s.framed,
+               "carrier": {**carrier, "drift_turns_per_window": abs(args.carrier_freq) * s.sps * W, "documented_limit_turns_per_window": MAX_DRIFT_TURNS},
+               "timing": {**timing, "drift_samples_per_window": abs(args.timing_drift) * s.sps * W, "documented_limit_samples_per_window": MAX_DRIFT_SAMPLES},
+               "acquisition": {**common, "carrier_hypotheses": hyp, "stack": stack, "stack_bytes": STACK_BYTES, "anchor": args.anchor}, "points": []}
+    # --coarse: the clock reads the rotated signal, so the carrier frequency in cycles per RECEIVED sample is nu (1 + eps)
+    true_nu = args.carrier_freq * (1.0 + args.timing_drift)
+    if args.coarse:
+        fine = {s.drift: s.timing, keyword: acqs["anchored" if args.anchor else "acquired"]}
+        _, out["coarse"] = _coarse_links(args, s, links, s.carrier, **fine)
+        out["coarse"]["true_nu_cycles_per_received_sample"] = true_nu
+
+    def after():
+        """One acquisition in units of one plain soft detection."""
+        lk = links["acquired"]
+        return {"one_acquisition": [_time_acquisition(lk, first, timed["stacks"], n, args.ebn0[-1], args.steps, s.unit, timed["stack_of"])
+                                    for n in timed["lengths"](lk)]}
+
+    return _Form(s=s, links=links, out=out, entry=("wrong_locks", "last_lock"), truth=(true_nu, args.timing_drift), compared=["genie", *acqs],
+                 losses=lambda loss: {"loss_db_at_fer_1e-2": {name: loss(name) for name in acqs}}, after=after,
+                 rejected=lambda lk: getattr(lk, result)()[5::2],
+                 rejected_windows=lambda found: dict(zip(("timing", "carrier"), map(sum, zip(*found)))),
+                 acq_key=args.waveform if s.cpm else None)
+
+
+def _curve_entry(lk, ncw, keys):
+    """A link's counts over the point's ``ncw`` codewords, and the form's further entries ``keys``."""
+    def uncoded_ber():
+        try:
+            ue, um = lk.uncoded_result()
+        except RuntimeError:                                              # (its synchroniser leaves the rows shifted: it does not count channel bits)
+            return None
+        return ue / um
+
+    further = {"uncoded_ber": uncoded_ber, "wrong_locks": lambda: None if lk.framing is None else lk.sync_result()[1],
+               "last_lock": lambda: lk.sync_result()[2][0]}
+    be, fe, nc, m, mean_it = lk.result()
+    return {"coded_ber": be / m, "fer": fe / ncw, "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc, "mean_iters": round(mean_it, 3),
+            **{k: further[k]() for k in keys}}
+
+
+def main_sync(args, make_form) -> None:
+    """The synchroniser forms (``_carrier_form``, ``_timing_form``, ``_acquire_form``): every link of the form on the same blocks,
+    point by point; per point the form's own timed sections; the Eb/N0 at FER 1e-2 of the curves the form compares, and the losses."""
+    form = make_form(args)
+    s, links, out = form.s, form.links, form.out
     for e in args.ebn0:
         point = {"ebn0_info_db": e}
         b = 0
         lost, found = {}, []
         for name, lk in links.items():
             lk.reset_counts()
-            b = 0
-            while b * per < args.codewords:
+            b, rejected = 0, []
+            while b * s.per < args.codewords:
                 lk.run_block(e, seed=1, stream_id=b)
                 b += 1
+                if name == "anchored":                                    # the windows its coarse tracks rejected in this burst
+                    rejected.append(form.rejected(lk))
                 if name in ("reference", "coarse"):                       # (per burst: these two synchronise after every block)
                     lost.setdefault(name, []).append(lk.result()[1])
                     if name == "coarse":
                         found.append(lk.coarse_result())
-            be, fe, nc, m, mean_it = lk.result()
-            ue, um = lk.uncoded_result()
-            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
-                           "mean_iters": round(mean_it, 3), "uncoded_ber": ue / um, "wrong_locks": None if cpm else lk.sync_result()[1]}
-        point["codewords"] = b * per
-        if coarse is not None:
-            point.update(_coarse_point(found, lost, args.carrier_freq, 0.0))
-            lk = links["coarse"]
-            coarse.times, tot = True, {}
-            for s in range(args.steps + 1):
-                lk.front_end(dev.ldpc_encode(code, lk.info_bits(b)), e, 1, b)
-                t = coarse.stage_times()
-                if s:
-                    for k, v in t.items():
-                        tot[k] = tot.get(k, 0.0) + v
-            coarse.times = False
-            point["coarse_ms_per_block"] = {k: round(v / max(args.steps, 1), 4) for k, v in tot.items()}
-        # the recovery's stages on one burst, each bracketed by device events, beside one plain soft detection
-        lk = links["recovered"]
-        rows, _ = lk.front_end(dev.ldpc_encode(code, lk.info_bits(b)), e, 1, b)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        tot, soft_ms = {}, 0.0
-        rec.times = True
-        for s in range(args.steps + 1):
-            recover(rows)
-            t = rec.stage_times()
-            ev[0].record()
-            soft(rows)
-            ev[1].record()
-            torch.cuda.synchronize()
-            if s:                                                         # (the first round warms up)
-                soft_ms += ev[0].elapsed_time(ev[1])
-                for k, v in t.items():
-                    tot[k] = tot.get(k, 0.0) + v
-        rec.times = False
-        n = max(args.steps, 1)
-        point["recovery_ms_per_block"] = {k: round(v / n, 4) for k, v in tot.items()}
-        point["recovery_ms_per_block"]["total"] = round(sum(tot.values()) / n, 4)
-        point["soft_detector_ms"] = round(soft_ms / n, 4)
-        point["burst_rows"] = int(rows.shape[0])
-        out["points"].append(point)
-    g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
-    out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
-    out["loss_db_at_fer_1e-2"] = None if g is None or r is None else round(r - g, 3)
-    if coarse is not None:
-        # the coarse stage's cost: the distance between the coarse + fine curve and the same fine recovery at --carrier-freq 0
-        f, c = _ebn0_at_fer(out["points"], "reference"), _ebn0_at_fer(out["points"], "coarse")
-        out["ebn0_at_fer_1e-2"].update({"reference": f, "coarse": c})
-        out["coarse_cost_db_at_fer_1e-2"] = None if f is None or c is None else round(c - f, 3)
-    print(json.dumps(out))
-
-
-def main_timing(args) -> None:
-    """The ``--recover-timing`` form: genie, impaired and recovered FRAMED links on the same blocks - SOQPSK-TG with a
-    ``TimingRecovery``, ARTM and PCM/FM (``--waveform multih|pcmfm``) with a ``CPMTimingRecovery``."""
-    import torch
-
-    from waveforms_amd import device as dev
-    from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CPM_WAVEFORMS, TIMING_OFFSET, CodedCPMLink, CodedSOQPSKLink
-    from waveforms_amd.encoding.framing import Framing
-
-    torch.cuda.set_device(0)
-    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
-    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
-    timing = (args.timing_offset, args.timing_drift)
-    fr = Framing(code)
-    sps = 8
-    cpm = args.waveform != "soqpsk"
-    if cpm:
-        from waveforms_amd.sync.timing_cpm import MAX_DRIFT_SAMPLES, CPMTimingRecovery
-        from waveforms_amd.viterbi import cpm as vc
-
-        spec = vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
-        rec_args = (spec, sps, args.timing_window, args.timing_span, args.timing_hyp, args.timing_refine, args.timing_delta)
-        rec = CPMTimingRecovery(*rec_args)
-        kw = dict(waveform=args.waveform, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
-        links = {"genie": CodedCPMLink(code, per, **kw), "impaired": CodedCPMLink(code, per, clock=timing, **kw),
-                 "recovered": CodedCPMLink(code, per, clock=timing, clock_recovery=rec, **kw)}
-        if args.anchor:
-            links["anchored"] = CodedCPMLink(code, per, clock=timing, clock_recovery=CPMTimingRecovery(*rec_args, anchor=args.anchor), **kw)
-        limit = MAX_DRIFT_SAMPLES[args.waveform]
-    else:
-        from waveforms_amd.sync.timing import MAX_DRIFT_SAMPLES as limit, TimingRecovery
-
-        kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
-        rec_args = (sps, args.timing_window or 256, args.timing_span, args.timing_hyp or 8, args.timing_refine, args.timing_delta or 2.0)
-        rec = TimingRecovery(*rec_args)
-        links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, timing=timing, **kw),
-                 "recovered": CodedSOQPSKLink(code, per, timing=timing, timing_recovery=rec, **kw)}
-        if args.anchor:
-            links["anchored"] = CodedSOQPSKLink(code, per, timing=timing, timing_recovery=TimingRecovery(*rec_args, anchor=args.anchor), **kw)
-    out = {"tool": "coded_ber", "form": "timing", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
-           "detector": None if cpm else args.detector, "block_codewords": per,
-           "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
-           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * sps * rec.window,
-                      "documented_limit_samples_per_window": limit},
-           "recovery": {"window": rec.window, "span": rec.span, "hypotheses": rec.hypotheses, "refine": rec.refine, "delta": rec.delta,
-                        "anchor": args.anchor}, "points": []}
-    for e in args.ebn0:
-        point = {"ebn0_info_db": e}
-        b = 0
-        for name, lk in links.items():
-            lk.reset_counts()
-            b, rejected = 0, 0
-            while b * per < args.codewords:
-                lk.run_block(e, seed=1, stream_id=b)
-                if name == "anchored":
-                    rejected += (lk.clock_result() if cpm else lk.timing_result())[-1]
-                b += 1
-            be, fe, nc, m, mean_it = lk.result()
-            ue, um = (None, None) if name in ("recovered", "anchored") else lk.uncoded_result()     # (a recovered link does not count channel bits)
-            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
-                           "mean_iters": round(mean_it, 3), "uncoded_ber": None if um is None else ue / um, "wrong_locks": lk.sync_result()[1],
-                           "last_lock": lk.sync_result()[2][0]}
+            point[name] = _curve_entry(lk, b * s.per, form.entry)
             if name == "anchored":
-                point[name]["rejected_windows"] = rejected
-        point["codewords"] = b * per
-        # the recovery's stages on one burst's noisy samples, each bracketed by device events, beside the fused front end
-        # (channel + bank, what the genie link runs) and one plain soft detection of its rows
-        lk = links["recovered"]
-        tx = dev.ldpc_encode(code, lk.info_bits(b))
-        bits = torch.cat((lk.channel_bits(tx, b), lk._pad))
-        syms = dev.symbol_map(CPM_WAVEFORMS[args.waveform], bits) if cpm else dev.fsm_encode(*lk._tables, bits)[0]
-        sig = dev.timing_offset(dev.cpm_modulate(syms, lk._d_h, lk._d_pulse, sps), *timing)
-        if cpm:
-            ncols = lk.ncalls
-        else:
-            first, ncols = dev.decimation(int(sig.shape[0]), sps, 2, TIMING_OFFSET[args.detector])
-        received = dev.awgn(sig, int(sig.shape[0]), lk.sigma(e), 1, b, 0, np.exp(-1j * np.pi / 4))
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        tot, front_ms, soft_ms = {}, 0.0, 0.0
-        rec.times = True
-        for s in range(args.steps + 1):
-            if cpm:
-                rec.recover(received, lk._d_templates, lk.start0, ncols)
-            else:
-                rec.recover(received, lk._d_taps, first, ncols, True)
-            t = rec.stage_times()
-            ev[0].record()
-            if cpm:                                                       # (the genie link's front end: the channel, then the matched filters)
-                noisy = dev.awgn(sig, int(sig.shape[0]), lk.sigma(e), 1, b, 0, np.exp(-1j * np.pi / 4))
-                rows = dev.cpm_mf_rows(noisy, lk._d_templates, lk.start0, sps, ncols)
-            else:
-                rows = dev.awgn_mf_bank(sig, lk._d_taps, first, sps, ncols, lk.sigma(e), 1, b, 0, np.exp(-1j * np.pi / 4))
-            ev[1].record()
-            if cpm:
-                dev.cpm_soft(rows, lk.spec, 0, 0, d_rot=lk._d_rot)
-            else:
-                dev.viterbi_soft(rows, True)
-            ev[2].record()
-            torch.cuda.synchronize()
-            if s:                                                         # (the first round warms up)
-                front_ms += ev[0].elapsed_time(ev[1])
-                soft_ms += ev[1].elapsed_time(ev[2])
-                for k, v in t.items():
-                    tot[k] = tot.get(k, 0.0) + v
-        rec.times = False
-        n = max(args.steps, 1)
-        point["recovery_ms_per_block"] = {k: round(v / n, 4) for k, v in tot.items()}
-        point["recovery_ms_per_block"]["total"] = round(sum(tot.values()) / n, 4)
-        point["fused_front_end_ms"] = round(front_ms / n, 4)
-        point["soft_detector_ms"] = round(soft_ms / n, 4)
-        point["burst_rows"] = int(ncols)
-        res = links["recovered"].clock_result() if cpm else links["recovered"].timing_result()
-        tau = res[0]
-        point["tau_samples"] = {"first": round(float(tau[0]), 3), "last": round(float(tau[-1]), 3), "windows": int(tau.size)}
-        if cpm:
-            point["grid"] = res[2]
+                point[name]["rejected_windows"] = form.rejected_windows(rejected)
+        point["codewords"] = b * s.per
+        if "coarse" in links:
+            point.update(_coarse_point(found, lost, *form.truth))
+        if form.point is not None:
+            form.point(point, e, b)
         out["points"].append(point)
-    g, r = _ebn0_at_fer(out["points"], "genie"), _ebn0_at_fer(out["points"], "recovered")
-    out["ebn0_at_fer_1e-2"] = {"genie": g, "recovered": r}
-    out["loss_db_at_fer_1e-2"] = None if g is None or r is None else round(r - g, 3)
-    if args.anchor:
-        a = _ebn0_at_fer(out["points"], "anchored")
-        out["ebn0_at_fer_1e-2"]["anchored"] = a
-        out["anchored_loss_db_at_fer_1e-2"] = None if g is None or a is None else round(a - g, 3)
+    at = out["ebn0_at_fer_1e-2"] = {name: _ebn0_at_fer(out["points"], name) for name in form.compared}
+
+    def loss(name, over="genie"):
+        return None if at[over] is None or at[name] is None else round(at[name] - at[over], 3)
+
+    out.update(form.losses(loss))
+    if "coarse" in links:
+        # the coarse stage's cost: the distance between the coarse + fine curve and the same fine synchroniser at --carrier-freq 0
+        at.update({name: _ebn0_at_fer(out["points"], name) for name in ("reference", "coarse")})
+        out["coarse_cost_db_at_fer_1e-2"] = loss("coarse", "reference")
+    if form.after is not None:
+        out.update(form.after())
     print(json.dumps(out))
-
-
-def _time_acquisition(lk, acq_kw, stacks, nrows, carrier, timing, ebn0, steps):
-    """One acquisition of a burst of about ``nrows`` rows (PN bits, the links' own impairment and channel) per entry of
-    ``stacks`` (name -> (stack, anchor)): device events around the whole call, ``steps`` calls after one warm-up, beside one plain soft detection of as
-    many rows -> {"rows", "soft_detector_ms", name: {"stack", "ms", "launches", "in_soft_detections", "stages_ms"}}."""
-    import torch
-
-    from waveforms_amd import device as dev
-    from waveforms_amd.encoding.coded import TIMING_OFFSET
-    from waveforms_amd.sync.joint import JointAcquisition
-
-    sps = lk.sps
-    bits = dev.lfsr_bits(23, lk._mask, (1 << 23) - 1, int(nrows))[0]
-    sig = dev.cpm_modulate(dev.fsm_encode(*lk._tables, bits)[0], lk._d_h, lk._d_pulse, sps)
-    dev.carrier_offset(sig, carrier[0], carrier[1], 0, out=sig)
-    sig = dev.timing_offset(sig, timing[0], timing[1], 0)
-    first, ncols = dev.decimation(int(sig.shape[0]), sps, 2, TIMING_OFFSET[lk.detector])
-    received = dev.awgn(sig, int(sig.shape[0]), lk.sigma(ebn0), 1, 0, 0, np.exp(-1j * np.pi / 4))
-    del sig
-    plain = dev.mf_bank(received, lk._d_taps, first, sps, ncols)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    soft_ms = 0.0
-    for s in range(steps + 1):
-        ev[0].record()
-        dev.viterbi_soft(plain, True)
-        ev[1].record()
-        torch.cuda.synchronize()
-        soft_ms += ev[0].elapsed_time(ev[1]) if s else 0.0
-    del plain
-    n = max(steps, 1)
-    out = {"rows": int(ncols), "soft_detector_ms": round(soft_ms / n, 4)}
-    for name, (stack, anchor) in stacks.items():
-        acq = JointAcquisition(sps, stack=stack, anchor=anchor, **acq_kw)
-        ms, stages = 0.0, {}
-        for s in range(steps + 1):
-            acq.times = False
-            ev[0].record()
-            res = acq.recover(received, lk._d_taps, first, ncols, True)
-            ev[1].record()
-            torch.cuda.synchronize()
-            ms += ev[0].elapsed_time(ev[1]) if s else 0.0
-            del res
-        acq.times = True                                                  # (the stages from a call of their own: the events cost time)
-        acq.recover(received, lk._d_taps, first, ncols, True)
-        stages = {k: round(v, 4) for k, v in acq.stage_times().items()}
-        out[name] = {"stack": acq.stack_for(ncols), "ms": round(ms / n, 4), "launches": acq.launches,
-                     "in_soft_detections": round(ms / n / (soft_ms / n), 2), "stages_ms": stages}
-    return out
-
-
-def main_acquire(args) -> None:
-    """The ``--acquire`` form: genie, impaired and acquired FRAMED CodedSOQPSKLink on the same blocks under a carrier offset AND a
-    timing offset (``JointAcquisition``), one more acquired curve per further value of ``--acq-carrier-hyp``, and the time of one
-    acquisition, unstacked and stacked, on bursts of ``--acq-time-rows`` rows."""
-    import math
-
-    import torch
-
-    from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CodedSOQPSKLink
-    from waveforms_amd.encoding.framing import Framing
-    from waveforms_amd.sync.joint import MAX_DRIFT_SAMPLES, MAX_DRIFT_TURNS, STACK_BYTES, JointAcquisition
-
-    torch.cuda.set_device(0)
-    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
-    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
-    carrier, timing = (math.radians(args.carrier_phase), args.carrier_freq), (args.timing_offset, args.timing_drift)
-    fr = Framing(code)
-    sps = 8
-    common = dict(window=args.timing_window or 256, span=args.timing_span, timing_hypotheses=args.acq_timing_hyp, refine=args.timing_refine,
-                  delta=args.timing_delta or 2.0)
-    kw = dict(detector=args.detector, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
-    links = {"genie": CodedSOQPSKLink(code, per, **kw), "impaired": CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, **kw)}
-    acqs = {}
-    for i, hc in enumerate(args.acq_carrier_hyp):
-        name = "acquired" if i == 0 else f"acquired_hc{hc}"
-        acqs[name] = JointAcquisition(sps, carrier_hypotheses=hc, stack=args.acq_stack or None, **common)
-        links[name] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=acqs[name], **kw)
-    if args.anchor:                                                       # the anchored curve beside the first acquired one, on the same blocks
-        acqs["anchored"] = JointAcquisition(sps, carrier_hypotheses=args.acq_carrier_hyp[0], stack=args.acq_stack or None, anchor=args.anchor, **common)
-        links["anchored"] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=acqs["anchored"], **kw)
-    coarse = None
-    if args.coarse:
-        # the coarse stage in front of the SAME acquisition (the anchored one with --anchor), and that acquisition at --carrier-freq 0
-        # under the same timing offset as the reference curve
-        from waveforms_amd.sync.coarse import CoarseFrequency
-
-        coarse = CoarseFrequency(sps, nfft=args.coarse_nfft, smooth=args.coarse_smooth or None)
-        fine = acqs["anchored" if args.anchor else "acquired"]
-        links["reference"] = CodedSOQPSKLink(code, per, carrier=(carrier[0], 0.0), timing=timing, acquisition=fine, **kw)
-        links["coarse"] = CodedSOQPSKLink(code, per, carrier=carrier, timing=timing, acquisition=fine, coarse=coarse, **kw)
-    W = common["window"]
-    out = {"tool": "coded_ber", "form": "acquire", "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx, "detector": args.detector,
-           "block_codewords": per, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
-           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
-                       "drift_turns_per_window": abs(args.carrier_freq) * sps * W, "documented_limit_turns_per_window": MAX_DRIFT_TURNS},
-           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_window": abs(args.timing_drift) * sps * W,
-                      "documented_limit_samples_per_window": MAX_DRIFT_SAMPLES},
-           "acquisition": {**common, "carrier_hypotheses": args.acq_carrier_hyp, "stack": args.acq_stack or None, "stack_bytes": STACK_BYTES,
-                           "anchor": args.anchor}, "points": []}
-    if coarse is not None:
-        # the clock reads the rotated signal: the carrier frequency in cycles per RECEIVED sample is nu (1 + eps)
-        true_nu = args.carrier_freq * (1.0 + args.timing_drift)
-        out["coarse"] = {"nfft": coarse.nfft, "smooth": coarse.smooth, "search": coarse.search, "true_nu_cycles_per_received_sample": true_nu}
-    for e in args.ebn0:
-        point = {"ebn0_info_db": e}
-        b = 0
-        lost, estimates = {}, []
-        for name, lk in links.items():
-            lk.reset_counts()
-            b, rejected = 0, [0, 0]
-            while b * per < args.codewords:
-                lk.run_block(e, seed=1, stream_id=b)
-                if name == "anchored":
-                    found = lk.acquisition_result()[4:]
-                    rejected = [rejected[0] + found[1], rejected[1] + found[3]]
-                if name in ("reference", "coarse"):                       # (per burst: these two synchronise after every block)
-                    lost.setdefault(name, []).append(lk.result()[1])
-                    if name == "coarse":
-                        estimates.append(lk.coarse_result())
-                b += 1
-            be, fe, nc, m, mean_it = lk.result()
-            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
-                           "mean_iters": round(mean_it, 3), "wrong_locks": lk.sync_result()[1], "last_lock": lk.sync_result()[2][0]}
-            if name == "anchored":
-                point[name]["rejected_windows"] = {"timing": rejected[0], "carrier": rejected[1]}
-        point["codewords"] = b * per
-        if coarse is not None:
-            point.update(_coarse_point(estimates, lost, true_nu, args.timing_drift))
-        out["points"].append(point)
-    g = _ebn0_at_fer(out["points"], "genie")
-    out["ebn0_at_fer_1e-2"] = {"genie": g}
-    out["loss_db_at_fer_1e-2"] = {}
-    for name in acqs:
-        r = _ebn0_at_fer(out["points"], name)
-        out["ebn0_at_fer_1e-2"][name] = r
-        out["loss_db_at_fer_1e-2"][name] = None if g is None or r is None else round(r - g, 3)
-    if coarse is not None:
-        f, c = _ebn0_at_fer(out["points"], "reference"), _ebn0_at_fer(out["points"], "coarse")
-        out["ebn0_at_fer_1e-2"].update({"reference": f, "coarse": c})
-        out["coarse_cost_db_at_fer_1e-2"] = None if f is None or c is None else round(c - f, 3)
-    # one acquisition, unstacked (the existing entry points per hypothesis) and stacked, in units of one plain soft detection
-    acq_kw = dict(common, carrier_hypotheses=args.acq_carrier_hyp[0])
-    stacks = {"stack_1": (1, 0), "stack_default": (args.acq_stack or None, 0)}
-    if args.anchor:
-        stacks["stack_default_anchored"] = (args.acq_stack or None, args.anchor)
-    out["one_acquisition"] = [_time_acquisition(links["acquired"], acq_kw, stacks, n, carrier, timing, args.ebn0[-1], args.steps) for n in args.acq_time_rows]
-    text = json.dumps(out)
-    if args.acq_out:
-        Path(args.acq_out).parent.mkdir(parents=True, exist_ok=True)
-        Path(args.acq_out).write_text(json.dumps(out, indent=1) + "\n")
-    print(text)
-
-
-def _time_acquisition_cpm(lk, acq_kw, stacks, ncalls, carrier, timing, ebn0, steps):
-    """``_time_acquisition`` for the CPM links: one ``CPMJointAcquisition`` of a burst of about ``ncalls`` calls per entry of
-    ``stacks`` (name -> (stack, anchor)), beside one plain ``cpm_soft`` of as many calls."""
-    import torch
-
-    from waveforms_amd import device as dev
-    from waveforms_amd.encoding.coded import CPM_WAVEFORMS
-    from waveforms_amd.sync.joint_cpm import CPMJointAcquisition
-    from waveforms_amd.viterbi import cpm as vc
-
-    sps, spec = lk.sps, lk.spec
-    nsym = int(ncalls)
-    bits = dev.lfsr_bits(23, lk._mask, (1 << 23) - 1, nsym * spec.bits_per_symbol)[0]
-    sig = dev.cpm_modulate(dev.symbol_map(CPM_WAVEFORMS[lk.waveform], bits), lk._d_h, lk._d_pulse, sps)
-    dev.carrier_offset(sig, carrier[0], carrier[1], 0, out=sig)
-    sig = dev.timing_offset(sig, timing[0], timing[1], 0)
-    geo = vc.filter_geometry(int(lk._d_pulse.numel()), sps, spec, nsym)
-    start0, ncalls = int(geo["start0"]), int(geo["ncalls"])
-    received = dev.awgn(sig, int(sig.shape[0]), lk.sigma(ebn0), 1, 0, 0, np.exp(-1j * np.pi / 4))
-    del sig
-    plain = dev.cpm_mf_rows(received, lk._d_templates, start0, sps, ncalls)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    soft_ms = 0.0
-    for s in range(steps + 1):
-        ev[0].record()
-        dev.cpm_soft(plain, spec, 0, 0, d_rot=lk._d_rot)
-        ev[1].record()
-        torch.cuda.synchronize()
-        soft_ms += ev[0].elapsed_time(ev[1]) if s else 0.0
-    del plain
-    n = max(steps, 1)
-    out = {"calls": ncalls, "soft_detector_ms": round(soft_ms / n, 4)}
-    for name, (stack, anchor) in stacks.items():
-        acq = CPMJointAcquisition(spec, sps, stack=stack, anchor=anchor, **acq_kw)
-        ms = 0.0
-        for s in range(steps + 1):
-            acq.times = False
-            ev[0].record()
-            res = acq.recover(received, lk._d_templates, start0, ncalls)
-            ev[1].record()
-            torch.cuda.synchronize()
-            ms += ev[0].elapsed_time(ev[1]) if s else 0.0
-            del res
-        acq.times = True                                                  # (the stages from a call of their own: the events cost time)
-        acq.recover(received, lk._d_templates, start0, ncalls)
-        stages = {k: round(v, 4) for k, v in acq.stage_times().items()}
-        out[name] = {"stack": stack, "ms": round(ms / n, 4), "launches": acq.launches, "in_soft_detections": round(ms / n / (soft_ms / n), 2),
-                     "stages_ms": stages}
-    return out
-
-
-def main_acquire_cpm(args) -> None:
-    """The ``--acquire`` form for ``--waveform multih|pcmfm``: genie, impaired and acquired FRAMED CodedCPMLink on the same blocks
-    under a carrier offset AND a clock offset (``CPMJointAcquisition``), the anchored curve with ``--anchor``, and the time of one
-    acquisition, unstacked and stacked, on the link's own burst and on bursts of ``--acq-time-rows`` calls.  The result goes
-    under the waveform's key of ``--acq-out``, beside what the file holds for the other waveform."""
-    import math
-
-    import torch
-
-    from waveforms_amd.encoding import ldpc
-    from waveforms_amd.encoding.coded import CodedCPMLink
-    from waveforms_amd.encoding.framing import Framing
-    from waveforms_amd.sync.joint_cpm import MAX_DRIFT_PERIODS, MAX_DRIFT_SAMPLES, CPMJointAcquisition
-    from waveforms_amd.viterbi import cpm as vc
-
-    torch.cuda.set_device(0)
-    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
-    per = min(args.block_codewords or max(1, int(1e7) // code.n_tx), args.codewords)
-    carrier, timing = (math.radians(args.carrier_phase), args.carrier_freq), (args.timing_offset, args.timing_drift)
-    fr = Framing(code)
-    sps = 8
-    spec = vc.ARTM_64 if args.waveform == "multih" else vc.PCMFM_20
-    common = dict(timing_window=args.timing_window, carrier_window=args.carrier_window, span=args.timing_span, timing_hypotheses=args.timing_hyp,
-                  carrier_hypotheses=args.carrier_hyp or 2, refine=args.timing_refine, delta=args.timing_delta)
-    kw = dict(waveform=args.waveform, alpha=args.alpha, max_iter=args.max_iter, framing=fr, lead_bits=args.lead_bits)
-    acqs = {"acquired": CPMJointAcquisition(spec, sps, stack=args.acq_stack or None, **common)}
-    if args.anchor:
-        acqs["anchored"] = CPMJointAcquisition(spec, sps, stack=args.acq_stack or None, anchor=args.anchor, **common)
-    links = {"genie": CodedCPMLink(code, per, **kw), "impaired": CodedCPMLink(code, per, carrier=carrier, clock=timing, **kw)}
-    for name, acq in acqs.items():
-        links[name] = CodedCPMLink(code, per, carrier=carrier, clock=timing, joint=acq, **kw)
-    a = acqs["acquired"]
-    out = {"tool": "coded_ber", "form": "acquire", "waveform": args.waveform, "code": args.code, "n": code.n, "k": code.k, "n_tx": code.n_tx,
-           "block_codewords": per, "burst_calls": links["genie"].ncalls, "framed": {"marker_bits": fr.L, "period": fr.period, "lead_bits": args.lead_bits},
-           "carrier": {"phase_deg": args.carrier_phase, "nu_cycles_per_sample": args.carrier_freq,
-                       "drift_turns_per_carrier_window": abs(args.carrier_freq) * sps * a.carrier_window,
-                       "documented_limit_turns_per_carrier_window": MAX_DRIFT_PERIODS / spec.p},
-           "timing": {"tau0_samples": args.timing_offset, "eps": args.timing_drift, "drift_samples_per_timing_window": abs(args.timing_drift) * sps * a.timing_window,
-                      "documented_limit_samples_per_timing_window": MAX_DRIFT_SAMPLES[args.waveform]},
-           "acquisition": {"timing_window": a.timing_window, "carrier_window": a.carrier_window, "span": a.span, "timing_hypotheses": a.timing_hypotheses,
-                           "carrier_hypotheses": a.carrier_hypotheses, "refine": a.refine, "delta": a.delta, "stack": a.stack, "anchor": args.anchor},
-           "points": []}
-    for e in args.ebn0:
-        point = {"ebn0_info_db": e}
-        b = 0
-        for name, lk in links.items():
-            lk.reset_counts()
-            b, rejected = 0, [0, 0]
-            while b * per < args.codewords:
-                lk.run_block(e, seed=1, stream_id=b)
-                if name == "anchored":
-                    found = lk.joint_result()[4:]
-                    rejected = [rejected[0] + found[1], rejected[1] + found[3]]
-                b += 1
-            be, fe, nc, m, mean_it = lk.result()
-            point[name] = {"coded_ber": be / m, "fer": fe / (b * per), "info_bit_errors": be, "codeword_errors": fe, "not_converged": nc,
-                           "mean_iters": round(mean_it, 3), "wrong_locks": lk.sync_result()[1], "last_lock": lk.sync_result()[2][0]}
-            if name == "anchored":
-                point[name]["rejected_windows"] = {"timing": rejected[0], "carrier": rejected[1]}
-        point["codewords"] = b * per
-        out["points"].append(point)
-    g = _ebn0_at_fer(out["points"], "genie")
-    out["ebn0_at_fer_1e-2"] = {"genie": g}
-    out["loss_db_at_fer_1e-2"] = {}
-    for name in acqs:
-        r = _ebn0_at_fer(out["points"], name)
-        out["ebn0_at_fer_1e-2"][name] = r
-        out["loss_db_at_fer_1e-2"][name] = None if g is None or r is None else round(r - g, 3)
-    # one acquisition, unstacked (cpm_soft_branch per table and per buffer) and stacked, in units of one plain soft detection
-    stacks = {"stack_1": (1, 0), "stacked": (None, 0)}
-    if args.anchor:
-        stacks["stacked_anchored"] = (None, args.anchor)
-    lengths = [links["genie"].ncalls] + ([1_000_000] if args.acq_time_rows == [211_252, 10_000_000] else args.acq_time_rows)
-    out["one_acquisition"] = [_time_acquisition_cpm(links["acquired"], common, stacks, n, carrier, timing, args.ebn0[-1], args.steps) for n in lengths]
-    print(json.dumps(out))
-    if args.acq_out:
+    if form.after is not None and args.acq_out:                           # --acq-out: the forms that time an acquisition
         path = Path(args.acq_out)
-        if path.name == "joint_acquisition.json":                         # (the SOQPSK-TG form's default)
-            path = path.with_name("joint_acquisition_cpm.json")
+        if form.acq_key is not None:                                      # under the waveform's key, beside what the file holds for the other
+            if path.name == "joint_acquisition.json":                     # (the SOQPSK-TG form's default)
+                path = path.with_name("joint_acquisition_cpm.json")
+            out = {**(json.loads(path.read_text()) if path.exists() else {}), form.acq_key: out}
         path.parent.mkdir(parents=True, exist_ok=True)
-        held = json.loads(path.read_text()) if path.exists() else {}
-        held[args.waveform] = out
-        path.write_text(json.dumps(held, indent=1) + "\n")
+        path.write_text(json.dumps(out, indent=1) + "\n")
 
 
 def main_conv(args) -> None:
@@ -908,19 +774,19 @@ def main() -> None:
     if args.acquire:
         if args.code.startswith("conv") or args.outer or args.live_only or args.recover or args.recover_timing:
             ap.error("--acquire is the framed CodedSOQPSKLink's and CodedCPMLink's: an LDPC code, no --outer / --live-only / --recover / --recover-timing")
-        return main_acquire(args) if args.waveform == "soqpsk" else main_acquire_cpm(args)
+        return main_sync(args, _acquire_form)
     if args.recover_timing or args.timing_offset or args.timing_drift:
         if not args.recover_timing:
             ap.error("--timing-offset / --timing-drift go with --recover-timing")
         if args.code.startswith("conv") or args.outer or args.live_only or args.recover:
             ap.error("--recover-timing is the framed CodedSOQPSKLink's and CodedCPMLink's: an LDPC code, no --outer / --live-only / --recover")
-        return main_timing(args)
+        return main_sync(args, _timing_form)
     if args.recover or args.carrier_phase or args.carrier_freq:
         if not args.recover:
             ap.error("--carrier-phase / --carrier-freq go with --recover")
         if args.code.startswith("conv") or args.outer or args.live_only:
             ap.error("--recover is CodedSOQPSKLink's (framed) and CodedCPMLink's: an LDPC code, no --outer / --live-only")
-        return main_carrier(args)
+        return main_sync(args, _carrier_form)
     if args.live_only and (args.waveform != "soqpsk" or args.outer < 1):
         ap.error("--live-only is the SOQPSK-TG loop's: it needs --waveform soqpsk and --outer N")
     if args.code.startswith("conv"):
@@ -935,13 +801,9 @@ def main() -> None:
     import torch
 
     from waveforms_amd import device as dev
-    from waveforms_amd.encoding import ldpc
     from waveforms_amd.encoding.coded import CodedCPMLink, CodedSOQPSKLink, IterativeCPMLink, IterativeSOQPSKLink
 
-    torch.cuda.set_device(0)
-    code = ldpc.demo_code(128 if args.code == "demo" else 1024)
-    per = args.block_codewords or max(1, int(1e7) // code.n_tx)
-    per = min(per, args.codewords)
+    code, per = _setup(args)
     cpm = args.waveform != "soqpsk"
     which = {"waveform": args.waveform} if cpm else {"detector": args.detector}
     link = (CodedCPMLink if cpm else CodedSOQPSKLink)(code, per, alpha=args.alpha, max_iter=args.max_iter, **which)

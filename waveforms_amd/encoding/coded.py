@@ -8,7 +8,8 @@ A link class is a waveform, a code and a kind of loop, each stated once:
     ``_Framed``   the burst around the codewords: sync marker, randomiser, frame search; the synchroniser slots and their results
     ``_Link``     what every link does: PN23 information bits, ``channel_llrs`` through the ``encode`` hook, the counters, the
                   view of the detector's output as codewords (``_coded``) and of the prior buffer (``_prior_coded``), ``detect``,
-                  and the front end: modulated signal -> impairments -> noisy samples (``samples``) -> rows
+                  and the front end: modulated signal (``modulated``) -> impairments (``impaired``; of a block: ``signal``) ->
+                  noisy samples (``noisy``; of a block: ``samples``) -> rows
     ``_SOQPSK``   SOQPSK-TG: pad, tables, PT / PAM bank, ``viterbi_soft`` (``_apriori``), the uncoded count, λ offset 1
     ``_CPM``      ARTM multi-h and PCM/FM on the generic CPM trellis: the same list with ``cpm_soft`` (``_apriori``), λ offset 0
     ``_LDPC``     one ``ldpc_decode`` per block: ``CodedSOQPSKLink`` = ``_LDPC`` on ``_SOQPSK``, ``CodedCPMLink`` = ``_LDPC`` on ``_CPM``
@@ -320,34 +321,40 @@ class _Link(_Framed):
         return bits
 
     def impaired(self, sig):
-        """A modulated signal -> (the signal under the link's impairments: ``carrier_offset`` in place, then ``timing_offset``;
-        where the bank reads it: the waveform's ``_geometry``)."""
+        """A modulated signal -> the signal under the link's impairments: ``carrier_offset`` in place, then ``timing_offset``."""
         if self.carrier is not None:
             dev.carrier_offset(sig, self.carrier[0], self.carrier[1], 0, out=sig)
         drift = getattr(self, self._drift)
         if drift is not None:
             sig = dev.timing_offset(sig, drift[0], drift[1], 0)
-        return sig, self._geometry(sig)
+        return sig
 
     def noisy(self, sig, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
         """A signal -> the channel's noisy samples, derotated."""
         return dev.awgn(sig, int(sig.shape[0]), self.sigma(ebn0_db), seed, stream_id, 0, DEROTATION)
 
-    def _sent(self, tx, stream_id: int):
-        """Coded bits -> (the burst's impaired signal, where the bank reads it, its symbols); ``sent`` keeps the burst's bits."""
-        bits = self.sent = _hip.torch().cat((self.channel_bits(tx, stream_id), self._pad))
+    def modulated(self, bits):
+        """A burst's bits, pad included -> (its modulated signal, its symbols)."""
         syms = self._symbols(bits)
-        return *self.impaired(dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps)), syms
+        return dev.cpm_modulate(syms, self._d_h, self._d_pulse, self.sps), syms
+
+    def signal(self, tx, stream_id: int = 0):
+        """Coded bits -> (the burst's impaired signal, where the bank reads it: the waveform's ``_geometry``, its symbols); ``sent``
+        keeps the burst's bits."""
+        bits = self.sent = _hip.torch().cat((self.channel_bits(tx, stream_id), self._pad))
+        sig, syms = self.modulated(bits)
+        sig = self.impaired(sig)
+        return sig, self._geometry(sig), syms
 
     def samples(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
         """Coded bits (device ncw x n_tx) -> (the noisy samples of the burst, where the bank reads them, its symbols)."""
-        sig, at, syms = self._sent(tx, stream_id)
+        sig, at, syms = self.signal(tx, stream_id)
         return self.noisy(sig, ebn0_db, seed, stream_id), at, syms
 
     def front_end(self, tx, ebn0_db: float | None, seed: int = 1, stream_id: int = 0):
         """Coded bits (device ncw x n_tx) -> (matched-filter rows of the burst, its symbols): the plain bank's rows, or those a
         synchroniser makes from the samples, behind those that correct the samples."""
-        sig, at, syms = self._sent(tx, stream_id)
+        sig, at, syms = self.signal(tx, stream_id)
         if self._fused_bank is not None and not self._correctors and self._row_maker is None:      # (nothing reads samples)
             return self._fused_bank(sig, *at, self.sigma(ebn0_db), seed, stream_id), syms
         received = self.noisy(sig, ebn0_db, seed, stream_id)
@@ -459,9 +466,10 @@ class _SOQPSK(_Link):
     def _symbols(self, bits):
         return dev.fsm_encode(*self._tables, bits)[0]
 
-    def _geometry(self, sig):
+    def _geometry(self, sig, nsym: int | None = None):
+        """Where the bank reads ``sig``: the link's own burst, or (``nsym``) a burst of another length."""
         first, ncols = dev.decimation(int(sig.shape[0]), self.sps, 2, TIMING_OFFSET[self.detector])
-        if ncols < self.nch + 1:
+        if nsym is None and ncols < self.nch + 1:
             raise RuntimeError(f"{ncols} detector rows for {self.nch} channel bits")
         return first, ncols
 
@@ -549,8 +557,13 @@ class _CPM(_Link):
     def _symbols(self, bits):
         return dev.symbol_map(CPM_WAVEFORMS[self.waveform], bits)
 
-    def _geometry(self, sig):
-        return self.start0, self.ncalls
+    def _geometry(self, sig, nsym: int | None = None):
+        if nsym is None:
+            return self.start0, self.ncalls
+        from ..viterbi import cpm
+
+        geo = cpm.filter_geometry(int(self._d_pulse.numel()), self.sps, self.spec, int(nsym))
+        return int(geo["start0"]), int(geo["ncalls"])
 
     def _bank(self, received, start0: int, ncalls: int):
         """Rows float64[ncalls, nfilt, 2]."""
